@@ -11,21 +11,31 @@ HBM as a 3-slot ring of packed states; at this batch size the library runs them 
 wavefront keeps its rod).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nodes-per-rod N] [--dtype f64|f32]
-                    [--scaling weak|strong] [--chunks C] [--no-cpu] [--no-extra]
+                    [--scaling weak|strong] [--chunks C] [--dump-outputs DIR] [--full [--no-cpu] [--no-extra]]
 
-The batch is ONE trajectory per rod from the straight rod: `settle` + W untimed steps, then C (default 5) consecutive
-chunks of K timed steps, each chunk bracketed by barrier + synchronize; `value` is the MEDIAN chunk (min / median / max /
-first are reported in `timed_chunks`).  W is what the command line asks for; `settle` (reported separately) tops the
-untimed part up to 30 steps, the time the start-value predictor of the solver needs to reach its steady state.  What
-a cold start costs is reported next to it (`cold_start`: T = 64 and T = 200 from the straight rod, no hand-over).
-Rods 0..31 of the timed batch are compared with the CPU oracle over the untimed AND the first timed steps.
+The batch is ONE trajectory per rod from the straight rod: `settle` + W untimed steps, then consecutive chunks of K
+steps, each chunk bracketed by barrier + synchronize; `value` is the MEDIAN timed chunk (min / median / max / first are
+reported in `timed_chunks`).  W is what the command line asks for; `settle` (reported separately) tops the untimed part
+up to 30 steps, the time the start-value predictor of the solver needs to reach its steady state.
+
+A plain run measures the headline and nothing else: two untimed warm chunks of K steps in the timed kernel's own form
+(the first launch of that form carries a fixed cost later chunks do not), then ONE timed chunk of K steps (C = 1
+unless --chunks says otherwise), so that --steps is the number of timed steps.  --dump-outputs DIR then writes what the
+last timed step returned to its caller (tips, status, base wrench, the rods' last state unpacked into y / z) as
+DIR/<name>.npy; the inputs are fixed by the seed, so two builds can be compared output for output.
+
+--full adds everything else, as every run did before the option existed: C = 5 timed chunks by default (no warm chunk),
+the CPU baseline (NumPy port and scalar C port), what a cold start costs (`cold_start`: T = 64 and T = 200 from the
+straight rod, no hand-over), the comparison of rods 0..31 of the timed batch with the CPU oracle over the untimed AND the
+first timed steps, and the legs of the other BASELINE configurations under `extra` (--no-cpu / --no-extra leave out the
+first three / the last).
 
 N>1: launched by torch.distributed.run, one rank per GPU; rods are sharded (weak scaling by default: 1024 rods on every
 GPU, no data-path collective - the only collectives of the forward leg are the timing barrier and the MAX over ranks
-of the elapsed time; `--scaling strong` splits 1024 rods over the GPUs, the mode not chosen is reported under `extra`).
-Then BASELINE cfg4 runs as `extra.train_dp`: 4096 trajectories sharded over the ranks, 28->512->25, 50 epochs, ONE
-all-reduce (SUM) of the flat fp32 gradient + loss buffer per epoch - RCCL over xGMI with the nccl backend - and the
-single-rank repeat of the same global batch on rank 0 as the parity check.
+of the elapsed time; `--scaling strong` splits 1024 rods over the GPUs; with --full the mode not chosen is reported
+under `extra`).  With --full, BASELINE cfg4 then runs as `extra.train_dp`: 4096 trajectories sharded over the ranks,
+28->512->25, 50 epochs, ONE all-reduce (SUM) of the flat fp32 gradient + loss buffer per epoch - RCCL over xGMI with
+the nccl backend - and the single-rank repeat of the same global batch on rank 0 as the parity check.
 """
 import argparse
 import json
@@ -278,12 +288,19 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch rods on every GPU; strong: --batch rods split over the GPUs")
-    ap.add_argument("--chunks", type=int, default=5, help="consecutive K-step chunks of the trajectory that are timed "
-                    "(value = their median)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg and the cold-start runs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs for the other BASELINE configurations / "
-                    "the data-parallel training leg")
+    ap.add_argument("--chunks", type=int, default=None, help="consecutive K-step chunks of the trajectory that are timed "
+                    "(value = their median; default 1, with --full 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as "
+                    "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also run the CPU baseline, the cold-start runs, the oracle "
+                    "check and the legs of the other BASELINE configurations / the data-parallel training leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg, the cold-start runs "
+                    "and the oracle check")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs for the other BASELINE "
+                    "configurations / the data-parallel training leg")
     args = ap.parse_args()
+    run_cpu = args.full and not args.no_cpu
+    run_extra = args.full and not args.no_extra
 
     import numpy as np
     import torch
@@ -304,7 +321,7 @@ def main():
     # presets are host-side library calls.
     cpu_leg = None
     refs = None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and run_cpu:
         probe = CosseratRod(use_fsolve=True)
         setup_robot(probe)
         pre0 = max(0, SETTLE_TOTAL - args.warmup) + args.warmup
@@ -315,7 +332,7 @@ def main():
         except Exception as e:  # the C restatement is optional test infrastructure (needs gcc or its prebuilt .so)
             cbc = {"error": str(e)}
         cpu_leg = (Tc, cb, cpu_tips, cbc)
-        if not args.no_extra:
+        if run_extra:
             try:
                 refs = oracle_refs(probe.del_t, EXTRA_REFS)
             except Exception as e:
@@ -355,7 +372,12 @@ def main():
 
     settle = max(0, SETTLE_TOTAL - W)
     pre = settle + W  # untimed steps of the trajectory
-    n_chunks = max(1, args.chunks)
+    n_chunks = max(1, args.chunks if args.chunks is not None else (5 if args.full else 1))
+    # plain run: two untimed K-step chunks in the timed form ahead of the timed one.  The first launch of that form is
+    # ~50 us slower than the ones after it and the second still ~1 % (profiles/*_bench_steps20.json, `wall_ms`): the
+    # timed chunk is the third of the trajectory, the one the median of --full's five chunks usually is.  --full times
+    # every chunk as it always did.
+    n_warm = 0 if args.full else 2
 
     def run_cold(B, T, dt=None, scheme=0):
         """T steps from the straight rod with no predictor hand-over: (seconds, unconverged rod-steps)."""
@@ -378,8 +400,8 @@ def main():
     # exactly 2 sweeps per step and 84 k ticks per step each time, takes 46 us per step in a process that has just
     # started and 36 us after ~2 s of fp64 work; an fp32 ramp warms less).  The ramp runs the persistent solver with
     # RK4 sweeps in the precision of the measurement on scratch copies of the problem: the same instruction mix, but a
-    # different kernel instantiation, so that in a rocprofv3 trace of `bench.py --no-cpu --no-extra --chunks 1` the
-    # timed kernel appears exactly once (the K timed steps); the untimed steps of the trajectory go through the
+    # different kernel instantiation, so that in a rocprofv3 trace of `bench.py --full --no-cpu --no-extra --chunks 1`
+    # the timed kernel appears exactly once (the K timed steps); the untimed steps of the trajectory go through the
     # one-launch-per-step form for the same reason.
     RAMP_A, RAMP_B = 0.5, 0.3
 
@@ -398,15 +420,17 @@ def main():
         torch.cuda.synchronize()
 
     def headline(B, b_world, b_rank, with_cold):
-        """`pre` untimed steps, then n_chunks x K timed steps of ONE trajectory per rod.  Rods [b_rank B, (b_rank + 1) B)
-        of a global draw of b_world x B rods.  Returns the measurement record of this rank (rank 0 assembles)."""
-        ctl = rank_controls(B, b_world, b_rank, pre + n_chunks * K, robot.del_t)
+        """`pre` untimed steps, n_warm untimed and n_chunks timed chunks of K steps of ONE trajectory per rod.  Rods
+        [b_rank B, (b_rank + 1) B) of a global draw of b_world x B rods.  Returns the measurement record of this rank
+        (rank 0 assembles)."""
+        n_all = n_warm + n_chunks
+        ctl = rank_controls(B, b_world, b_rank, pre + n_all * K, robot.del_t)
         ctl_pre = torch.as_tensor(ctl[:, :pre], device=dev).to(tdt).contiguous() if pre else None
         ctl_k = [torch.as_tensor(ctl[:, pre + c * K: pre + (c + 1) * K], device=dev).to(tdt).contiguous()
-                 for c in range(n_chunks)]
+                 for c in range(n_all)]
         G = torch.zeros((B, 6), dtype=tdt, device=dev)
-        status = torch.zeros((n_chunks, B, K), dtype=torch.int32, device=dev)
-        tip = torch.empty((n_chunks, B, K, 3), dtype=tdt, device=dev)
+        status = torch.zeros((n_all, B, K), dtype=torch.int32, device=dev)
+        tip = torch.empty((n_all, B, K, 3), dtype=tdt, device=dev)
         tip_pre = torch.empty((B, max(pre, 1), 3), dtype=tdt, device=dev)
         h.set_option("keep_predictor", 0)
         persistent_default = h.get_option("persistent")
@@ -442,7 +466,7 @@ def main():
             prev_init = None
         h.set_option("persistent", persistent_default)
         walls, kernels = [], []
-        for c in range(n_chunks):
+        for c in range(n_all):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if world > 1:
                 dist.barrier()
@@ -458,24 +482,28 @@ def main():
                 tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
                 dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
                 elapsed = float(tmax.item())
-            walls.append(elapsed)
-            kernels.append(ev0.elapsed_time(ev1))  # duration of the K-step region on the launch stream (HIP events)
-            if c + 1 < n_chunks:
+            if c >= n_warm:
+                walls.append(elapsed)
+                kernels.append(ev0.elapsed_time(ev1))  # duration of the K-step region on the launch stream (HIP events)
+            if c + 1 < n_all:
                 # the ring leaves the newest state in slot K % 3 and the one before it in (K - 1) % 3; the next call
                 # starts from slot 0 again (untimed device copies)
                 newest, older = states[K % 3].clone(), states[(K - 1) % 3].clone()
                 states[0].copy_(newest)
                 prev_init = older
         h.set_option("keep_predictor", 0)
-        return {"B": B, "walls": walls, "kernel_ms": kernels, "n_bad": int((status != 0).sum()), "cold": cold,
-                "tip": tip, "tip_pre": tip_pre, "path": h.get_option("last_sim_path"),
-                "kernel": bl.kernel_label(h), "waves_per_rod": h.get_option("last_waves_per_rod")}
+        return {"B": B, "walls": walls, "kernel_ms": kernels, "n_bad": int((status[n_warm:] != 0).sum()), "cold": cold,
+                "tip": tip, "tip_pre": tip_pre, "status": status, "G": G, "state": states[K % 3],
+                "path": h.get_option("last_sim_path"), "kernel": bl.kernel_label(h),
+                "waves_per_rod": h.get_option("last_waves_per_rod")}
 
     strong = args.scaling == "strong"
     if strong and args.batch % world:
         raise SystemExit("--scaling strong needs --batch divisible by the number of GPUs")
     B = args.batch // world if strong else args.batch
-    m = headline(B, world, rank, with_cold=not args.no_cpu)
+    m = headline(B, world, rank, with_cold=run_cpu)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, h)
 
     out = None
     if rank == 0:
@@ -527,9 +555,10 @@ def main():
             "dtype": args.dtype,
             "data": "synthetic",
             "timed_chunks": {
-                "n": n_chunks, "steps_each": K,
+                "n": n_chunks, "steps_each": K, "warm_chunks": n_warm,
                 "what": "consecutive K-step chunks of ONE trajectory per rod, each its own kr_simulate_batch call bracketed "
-                        "by barrier + synchronize (MAX over ranks); value / ms_per_step = the median chunk",
+                        "by barrier + synchronize (MAX over ranks), after `warm_chunks` untimed ones of the same form; "
+                        "value / ms_per_step = the median timed chunk",
                 "value_min": round(rod_steps / max(walls), 1), "value_median": round(rod_steps / elapsed, 1),
                 "value_max": round(rod_steps / min(walls), 1), "value_first": round(rod_steps / walls[0], 1),
                 "wall_ms": [round(w * 1e3, 4) for w in walls], "kernel_ms": [round(k, 4) for k in kms],
@@ -590,7 +619,7 @@ def main():
             out["cpu_baseline_c"] = cbc
 
     extra = {}
-    if not args.no_extra:
+    if run_extra:
         if world == 1:
             extra.update(run_extras(torch, dev_index, refs, log))
         else:
@@ -645,6 +674,30 @@ def cpu_baseline_c(N, del_t, B, rods=256, steps=150):
             "kind": "port", "sample": f"{rods} rods x {steps} steps of the bench workload (N={N}, fp64), scalar C, Newton shooting to 1e-12, "
                       f"one rod per thread", "single_core_value": round(steps / t_single, 1),
             "unconverged": int(sum(r[2] for r in res) + one[2])}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, m, h):
+    """What the last timed step returned to its caller, as <path>/<name>.npy (float64, or float32 for --dtype f32):
+    tip [B, 3] and status [B] of that step, the base wrench G [B, 6] the call leaves behind, and the rods' last state
+    unpacked into y [B, 19, N] and z [B, 6, N].  Where that exceeds DUMP_BYTES_MAX, every array keeps the same
+    seeded sample of rods (ascending, written as rods.npy)."""
+    import numpy as np
+    import torch
+    y, z = h.unpack(m["state"])
+    out = {"tip": m["tip"][-1, :, -1], "status": m["status"][-1, :, -1].double(), "base_wrench": m["G"], "y": y, "z": z}
+    B = m["B"]
+    per_rod = sum(t[0].numel() * t.element_size() for t in out.values())
+    if B * per_rod > DUMP_BYTES_MAX:
+        rods = np.sort(np.random.default_rng(SEED).choice(B, DUMP_BYTES_MAX // (per_rod + 8), replace=False))
+        idx = torch.as_tensor(rods, device=y.device)
+        out = {k: v.index_select(0, idx) for k, v in out.items()}
+        out["rods"] = torch.as_tensor(rods, dtype=torch.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v.cpu().numpy())
 
 
 if __name__ == "__main__":

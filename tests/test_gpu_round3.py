@@ -300,7 +300,7 @@ def test_bench_two_ranks(torch_cuda):
     port = str(29800 + os.getpid() % 90)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-           "--warmup", "5", "--no-cpu"]
+           "--warmup", "5", "--full", "--no-cpu"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -50,11 +50,10 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.kr_version() >= 100
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors of kr_params / kr_derived have the C layout (checked by compiling a probe)."""
     import krod_native as kn
-    probe = os.path.join(ROOT, "gpurun_out", "_layout_probe")
-    os.makedirs(os.path.dirname(probe), exist_ok=True)
+    probe = str(tmp_path / "_layout_probe")
     with open(probe + ".c", "w") as f:
         f.write('#include <stdio.h>\n#include <stddef.h>\n#include "knode_rod.h"\n'
                 'int main(){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(kr_params), sizeof(kr_derived),'

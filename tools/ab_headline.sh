@@ -11,7 +11,7 @@ for r in $(seq 1 "$rounds"); do
   for lib in "$@"; do
     for steps in 1000 20; do
       if [ "$steps" = 1000 ]; then extra="--warmup 60 --chunks 2"; else extra="--warmup 5"; fi
-      line=$(KR_LIB_PATH=$PWD/$lib timeout -k 10 300 python3 bench.py --steps $steps $extra --no-cpu --no-extra 2>/dev/null | tail -1)
+      line=$(KR_LIB_PATH=$PWD/$lib timeout -k 10 300 python3 bench.py --full --steps $steps $extra --no-cpu --no-extra 2>/dev/null | tail -1)
       echo "$line" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

@@ -31,7 +31,7 @@ SQ_MEM="SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VME
 OPS_F64="SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 OPS_MFMA="SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES"
 OPS_F32="SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_WAVE_CYCLES"
-BENCH="python3 bench.py --no-cpu --no-extra"
+BENCH="python3 bench.py --full --no-cpu --no-extra"
 rocprofv3 -L > $out/${tag}_counters.txt 2>&1 || true
 
 # one leg of bench.py's `extra` under the profiler: leg_passes <leg> <pass ...>   (pass: stats fetch write sq sqm ops opsm vops64 vops32)
@@ -54,13 +54,13 @@ leg_passes() {
 }
 if want bench; then
   echo "[bench] bench line (with CPU baseline)"
-  timeout -k 10 500 python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { echo "bench failed"; exit 1; }
+  timeout -k 10 500 python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { echo "bench failed"; exit 1; }
   tail -c 400 $out/${tag}_bench.json; echo
   # the driver's own command line (20-step chunks): the fixed cost of a call shows here
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extra > $out/${tag}_bench_steps20.json 2> $out/${tag}_bench_steps20.err || true
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra > $out/${tag}_bench_steps20.json 2> $out/${tag}_bench_steps20.err || true
 fi
 if want stats; then
-  echo "[stats] rocprofv3 kernel stats of the same command (--no-cpu --no-extra)"
+  echo "[stats] rocprofv3 kernel stats of the same command (--full --no-cpu --no-extra)"
   prof bench_stats 300 --stats --output-format csv -d $out/${tag}_bench_stats -- $BENCH
 fi
 if want hbm; then

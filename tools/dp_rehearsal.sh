@@ -19,8 +19,10 @@ PY
 # tensors), four ranks sharing the card (the pool's guard allows 6 processes on one GPU and counts the launcher too: six
 # ranks were killed by it); the driver's own run is --gpus 8 with nccl = RCCL, one rank per GPU.  Same code path: rank-sharded
 # rods, barrier + MAX timing, weak and strong scaling, the cfg4 data-parallel leg with one all-reduce per epoch and the
-# single-rank repeat.  JSON -> gpurun_out/<tag>_rehearsal4.json
+# single-rank repeat.  JSON -> $out/<tag>_rehearsal4.json (OUT_DIR, default bench_out)
 tag=${1:-r05}
+out=${OUT_DIR:-bench_out}
+mkdir -p "$out"
 KR_BENCH_BACKEND=gloo timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus 4 --steps 20 --warmup 5 --no-cpu > gpurun_out/${tag}_rehearsal4.json 2> gpurun_out/${tag}_rehearsal4.err
-tail -c 1500 gpurun_out/${tag}_rehearsal4.json
+  bench.py --gpus 4 --steps 20 --warmup 5 --full --no-cpu > "$out/${tag}_rehearsal4.json" 2> "$out/${tag}_rehearsal4.err"
+tail -c 1500 "$out/${tag}_rehearsal4.json"

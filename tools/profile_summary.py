@@ -149,7 +149,7 @@ def summarise(tag, G, P, log=print):
     workload = f"B={B} N={N} {dtype} Euler"
 
     def bench_pass(name):
-        """(rows, expected us per timed dispatch, steps per launch) of one pass over `bench.py --no-cpu --no-extra`."""
+        """(rows, expected us per timed dispatch, steps per launch) of one pass over `bench.py --full --no-cpu --no-extra`."""
         d = os.path.join(G, f"{tag}_{name}")
         own = last_json_line(d + ".out")
         if own is None:
@@ -179,8 +179,8 @@ def summarise(tag, G, P, log=print):
             f"{sum(g['ns'] for g in good.values()) / len(good) * 1e-3:.1f} us (events: {expect_us:.1f})")
 
     def do_hbm():
-        rec = {"source": "rocprofv3 --kernel-trace --pmc <X> --output-format csv -- python3 bench.py --no-cpu --no-extra (separate "
-                         "passes for FETCH_SIZE and WRITE_SIZE), tools/collect.sh; dispatches selected by instantiation and "
+        rec = {"source": "rocprofv3 --kernel-trace --pmc <X> --output-format csv -- python3 bench.py --full --no-cpu --no-extra "
+                         "(separate passes for FETCH_SIZE and WRITE_SIZE), tools/collect.sh; dispatches selected by instantiation and "
                          "duration (tools/profile_summary.py)",
                "kernel": bench["roofline"]["kernel"], "workload": workload}
         per = {}
