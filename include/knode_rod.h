@@ -302,6 +302,41 @@ int kr_simulate_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void
                       void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
                       const void* state_prev_init, int dtype, void* stream);
 
+/* ---- heterogeneous batches: per-rod parameter tables ------------------- */
+/* Every call above takes its rod from the handle: B rods are B copies of one parameter set.  A parameter table gives
+ * rod b of a simulate call its own kr_params - the reference's "one true rod, several mismatched models" experiment
+ * (knode.setup_robot with its mods, knode.py:6-53, walked one model at a time by physics_multitrain.py), parameter
+ * sweeps, system identification, domain randomisation - in ONE launch instead of one handle and one launch per rod.
+ *
+ * Shared with the handle (a row that differs: KR_E_ARG): N, del_t, nn_input_history.  The MLP is the handle's
+ * (kr_set_mlp), one network for all rods.
+ * Per rod: every other field of kr_params (L - hence ds -, E, r, rho, vstar, g, Bse, Bbt, C, F_tip, M_tip, tendon_dirs,
+ * p0, h0, q0, w0).
+ * Served (anything else: KR_E_UNSUPPORTED with a message that names the rule - never a silent fallback to the handle's
+ * parameters): diagonal Bse / Bbt on every row (every preset qualifies); scheme KR_EULER; 9 <= N <= 128; MLP off, or an
+ * MLP the persistent one-wavefront kernel evaluates; KR_F32 and KR_F64.  Table calls always run one wavefront per rod
+ * in one persistent launch (last_sim_path 2, last_waves_per_rod 1): the overlapped kernel with its take-over launch, or
+ * the plain persistent kernel for MLP-on and overlap = 0.  Options residual_test, overlap, predictor, keep_predictor,
+ * nn_* mean what they mean for kr_simulate_batch; waves_per_rod = 2 / 4, ms_mode = 0 and persistent = 0 are refused.
+ * NOT served with a table: several wavefronts per rod, N > 128, single shooting, RK4, full material matrices, one
+ * launch per step, kr_step_batch / kr_residual_* / kr_ode_batch, per-rod N / del_t / MLP, training. */
+typedef struct kr_param_table kr_param_table;
+
+/* Host arithmetic only (no handle, no GPU - like kr_derive): may rods_host[0..B) ride in one launch with `base`?
+ * KR_OK, or KR_E_ARG / KR_E_UNSUPPORTED with *bad_rod (nullable) = the first offending row (-1: the fault is not in a
+ * row) and kr_last_error() naming the field. */
+int kr_param_table_check(const kr_params* base, int64_t B, const kr_params* rods_host, int64_t* bad_rod);
+/* Checks the rows against the handle's parameters, derives every row exactly as kr_set_params derives the handle's own
+ * constants (fp64, then rounded to fp32) and uploads both precisions.  The table belongs to the handle's device and is
+ * immutable; destroy it after the last call that uses it has finished on its stream. */
+int kr_param_table_create(kr_handle* h, int64_t B, const kr_params* rods_host, kr_param_table** out);
+int kr_param_table_destroy(kr_param_table* t);
+/* kr_state_init_straight / kr_simulate_batch with rod b taking row b of the table (B = the table's B). */
+int kr_state_init_straight_table(kr_handle* h, const kr_param_table* t, void* state, int dtype, void* stream);
+int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, void* states,
+                            int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
+                            const void* state_prev_init, int dtype, void* stream);
+
 /* ---- KNODE one-step-ahead training path -------------------------------- */
 /* CosseratRodTorch.parallelGetNextSegmentEuler (cosserat_ode_torch.py:401-437)
  * and, with idx = 1..N-1, getNextSegmentEuler (:370-399), plus the four-term

@@ -965,6 +965,166 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
   return launch_step<double>(h, scheme, use_nn, a, s);
 }
 
+// ---- per-rod parameter tables -------------------------------------------------------------------------------------
+static const char* tab_field_mismatch(const kr_params& base, const kr_params& r) {
+  if (r.N != base.N) return "N";
+  if (r.del_t != base.del_t) return "del_t";
+  if (r.nn_input_history != base.nn_input_history) return "nn_input_history";
+  return nullptr;
+}
+
+// the rules of kr_param_table_check for one row; `d` receives the row's dependent terms
+static int tab_check_row(const kr_params& base, const kr_params& r, int64_t b, kr_derived& d) {
+  const std::string who = "parameter table, rod " + std::to_string(b) + ": ";
+  if (const char* f = tab_field_mismatch(base, r)) {
+    set_error(who + "field " + f + " differs from the base parameters (N, del_t and nn_input_history are shared by all rods of a launch)");
+    return KR_E_ARG;
+  }
+  if (int rc = derive(r, d)) {
+    set_error(who + kr_last_error());
+    return rc;
+  }
+  const char* nd = !is_diag(r.Bse) ? "Bse" : !is_diag(r.Bbt) ? "Bbt" : nullptr;
+  if (!nd && !(is_diag(d.Kse_plus_c0_Bse_inv) && is_diag(d.Kbt_plus_c0_Bbt_inv) && is_diag(d.rhoJ))) nd = "Kse/Kbt/rhoJ";
+  if (nd) {
+    set_error(who + "field " + nd + " is not diagonal (table calls serve diagonal material matrices only)");
+    return KR_E_UNSUPPORTED;
+  }
+  return KR_OK;
+}
+
+int kr_param_table_check(const kr_params* base, int64_t B, const kr_params* rods_host, int64_t* bad_rod) {
+  if (bad_rod) *bad_rod = -1;
+  KR_CHECK_PTR(base);
+  KR_CHECK_PTR(rods_host);
+  if (B <= 0) { set_error("parameter table: B must be > 0"); return KR_E_ARG; }
+  if (base->N - 1 < 8 || base->N > 128) {
+    set_error("parameter table: N = " + std::to_string(base->N) + ", table calls serve 9 <= N <= 128 (the one-wavefront persistent kernels)");
+    return KR_E_UNSUPPORTED;
+  }
+  for (int64_t b = 0; b < B; ++b) {
+    kr_derived d{};
+    if (int rc = tab_check_row(*base, rods_host[b], b, d)) {
+      if (bad_rod) *bad_rod = b;
+      return rc;
+    }
+  }
+  return KR_OK;
+}
+
+int kr_param_table_destroy(kr_param_table* t) {
+  if (!t) return KR_OK;
+  if (t->rows_f) (void)hipFree(t->rows_f);
+  if (t->rows_d) (void)hipFree(t->rows_d);
+  if (t->L) (void)hipFree(t->L);
+  delete t;
+  return KR_OK;
+}
+
+int kr_param_table_create(kr_handle* h, int64_t B, const kr_params* rods_host, kr_param_table** out) {
+  KR_CHECK_H(h);
+  KR_CHECK_PTR(out);
+  *out = nullptr;
+  if (int rc = kr_param_table_check(&h->params, B, rods_host, nullptr)) return rc;
+  int dev = -1;
+  if (hipGetDevice(&dev) == hipSuccess && dev != h->device) {
+    set_error("the current HIP device is not the one the handle was created on: call hipSetDevice first");
+    return KR_E_ARG;
+  }
+  std::vector<RodConst<float>> rf((size_t)B);
+  std::vector<RodConst<double>> rd((size_t)B);
+  std::vector<double> Ls((size_t)B);
+  for (int64_t b = 0; b < B; ++b) {
+    kr_derived d{};
+    if (int rc = derive(rods_host[b], d)) return rc;
+    fill_consts(rods_host[b], d, rf[(size_t)b]);
+    fill_consts(rods_host[b], d, rd[(size_t)b]);
+    Ls[(size_t)b] = rods_host[b].L;
+  }
+  kr_param_table* t = new kr_param_table();
+  t->device = h->device;
+  t->B = B;
+  t->N = h->params.N;
+  t->nn_input_history = h->params.nn_input_history;
+  t->del_t = h->params.del_t;
+  hipError_t e = hipMalloc((void**)&t->rows_f, sizeof(RodConst<float>) * (size_t)B);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->rows_d, sizeof(RodConst<double>) * (size_t)B);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->L, sizeof(double) * (size_t)B);
+  // (synchronous copies from pageable memory: the table is complete on the device when this returns)
+  if (e == hipSuccess) e = hipMemcpy(t->rows_f, rf.data(), sizeof(RodConst<float>) * (size_t)B, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(t->rows_d, rd.data(), sizeof(RodConst<double>) * (size_t)B, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(t->L, Ls.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    kr_param_table_destroy(t);
+    return hip_fail(e, "kr_param_table_create");
+  }
+  *out = t;
+  return KR_OK;
+}
+
+// a table may be used with any handle on its device that shares N, del_t and nn_input_history with its rows
+static int tab_matches(const kr_handle* h, const kr_param_table* t) {
+  const char* f = t->device != h->device ? "device" : t->N != h->params.N ? "N" : t->del_t != h->params.del_t ? "del_t"
+                  : t->nn_input_history != h->params.nn_input_history ? "nn_input_history" : nullptr;
+  if (!f) return KR_OK;
+  set_error(std::string("parameter table: ") + f + " of the table differs from the handle's");
+  return KR_E_ARG;
+}
+
+int kr_state_init_straight_table(kr_handle* h, const kr_param_table* t, void* state, int dtype, void* stream) {
+  KR_CHECK_PTR(t);
+  KR_BATCH_PROLOGUE(t->B);
+  KR_CHECK_PTR(state);
+  if (int rc = tab_matches(h, t)) return rc;
+  return dtype == KR_F32 ? launch_tab_init_straight<float>(h, t, (float*)state, s)
+                         : launch_tab_init_straight<double>(h, t, (double*)state, s);
+}
+
+extern "C++" {
+template <typename T>
+static int simulate_table_impl(kr_handle* h, const kr_param_table* t, int64_t T_steps, int scheme, const void* ctl, void* states,
+                               int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
+                               const void* prev_init, hipStream_t s) {
+  const int64_t B = t->B;
+  auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, G, ctl, 4, tol, maxit);
+  SimArgs<T> sa{};
+  sa.B = B; sa.T_steps = T_steps; sa.states = (T*)states; sa.slot_elems = (int64_t)((size_t)B * t->N * KR_SLOTS); sa.ring = ring;
+  sa.prev_init = (const T*)prev_init; sa.ctl = (const T*)ctl; sa.G = (T*)G; sa.tip = (T*)tip; sa.status = status;
+  sa.tol = a0.tol; sa.tolA = a0.tolA; sa.fd_eps = a0.fd_eps; sa.hc1 = a0.hc1; sa.hc2 = a0.hc2;
+  sa.maxit = a0.maxit; sa.predictor = h->predictor; sa.residual_test = h->residual_test; sa.nn_lowp = h->nn_lowp_first; sa.nn_base_only = h->nn_base_only_store;
+  sa.dbg = static_cast<unsigned long long*>(h->dbg);
+  sa.pred_io = nullptr; sa.pred_load = 0;
+  // the predictor image does not depend on the parameters: option keep_predictor works as in kr_simulate_batch
+  if (h->keep_predictor && (size_t)B * KR_PRED_IMG_DOUBLES * sizeof(double) <= ((size_t)1 << 30)) {
+    if (int rcp = ensure_pred(h, B)) return rcp;
+    sa.pred_io = static_cast<double*>(h->pred_buf);
+    sa.pred_load = h->pred_valid_B == B && h->pred_valid_W == 1 && h->pred_valid_nn == (use_nn ? 1 : 0);
+  }
+  const int rc = launch_tab_sim<T>(h, t, scheme, use_nn, sa, s);
+  if (rc == KR_OK) {
+    h->last_sim_path = 2;
+    if (sa.pred_io) { h->pred_valid_B = B; h->pred_valid_W = 1; h->pred_valid_nn = use_nn ? 1 : 0; }
+  }
+  return rc;
+}
+}  // extern "C++"
+
+int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, void* states,
+                            int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
+                            const void* state_prev_init, int dtype, void* stream) {
+  KR_CHECK_PTR(t);
+  KR_BATCH_PROLOGUE(t->B);
+  if (int rc = tab_matches(h, t)) return rc;
+  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
+  if (T == 0) return KR_OK;
+  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  return dtype == KR_F32
+             ? simulate_table_impl<float>(h, t, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                          state_prev_init, s)
+             : simulate_table_impl<double>(h, t, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                           state_prev_init, s);
+}
+
 int kr_simulate_prepare(kr_handle* h, int64_t B, int dtype) {
   KR_CHECK_H(h);
   KR_CHECK_DTYPE(dtype);

@@ -114,6 +114,20 @@ struct kr_handle {
   hipEvent_t order_event = nullptr;
 };
 
+// Per-rod parameter table (kr_param_table_create): row b = the constants of rod b, derived like the handle's own and
+// uploaded in both precisions.  Immutable after creation.
+struct kr_param_table {
+  int device = 0;
+  int64_t B = 0;
+  // what every row shares with the handle it is used with
+  int N = 0;
+  int nn_input_history = 0;
+  double del_t = 0;
+  kr::RodConst<float>* rows_f = nullptr;   // [B], device
+  kr::RodConst<double>* rows_d = nullptr;  // [B], device
+  double* L = nullptr;                     // [B], device: rod lengths (kr_state_init_straight_table)
+};
+
 namespace kr {
 
 int ensure_ws(kr_handle* h, size_t bytes);
@@ -244,6 +258,19 @@ int launch_msw_nn_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s);
 template <typename T>
 int launch_msw_gh_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s);
 int ensure_hist_ws(kr_handle* h, size_t bytes);
+// kr_tab_f32.hip / kr_tab_f64.hip: the one-wavefront persistent kernels with per-rod constants (kr_tab_impl.hpp).
+// launch_tab_sim refuses (KR_E_UNSUPPORTED, with a message) what these kernels do not serve; nothing falls back to the
+// handle's own parameters.
+template <typename T>
+inline const RodConst<T>* table_rows(const kr_param_table* t);
+template <>
+inline const RodConst<float>* table_rows<float>(const kr_param_table* t) { return t->rows_f; }
+template <>
+inline const RodConst<double>* table_rows<double>(const kr_param_table* t) { return t->rows_d; }
+template <typename T>
+int launch_tab_sim(kr_handle* h, const kr_param_table* t, int scheme, int use_nn, const SimArgs<T>& a, hipStream_t s);
+template <typename T>
+int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s);
 // kr_sim_f32.hip / kr_sim_f64.hip: the same for the one-wavefront persistent kernel that runs behind it
 template <typename T>
 int prepare_ms_sim(kr_handle* h);

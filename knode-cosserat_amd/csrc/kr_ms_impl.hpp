@@ -1610,10 +1610,12 @@ constexpr int MS_NPL = 2;  // grid points per lane held in registers by the pers
 // instantiation runs two wavefronts per SIMD - two rods - whose issue-bound sweeps and latency-bound algebra overlap:
 // +25 % (N = 100) to +37 % (N = 64) at B >= 2048 (tools/occ_probe.py), -3 % at B = 1024 where every SIMD has one
 // wavefront anyway (68 spilled registers).  In fp64 a rod needs 37.8 KB of LDS: four per CU, one per SIMD.
-template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1>
-__global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const RodConst<T> Pc, const SimArgs<T> A, const MlpDev<T> M) {
+// PSRC: the rod's constants come from the kernel argument itself (RodConst<T>) or from a per-rod table (RodTable<T>,
+// kr_tab_impl.hpp); see rod_src_row (rod_device.hpp).
+template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1, typename PSRC = RodConst<T>>
+__global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC Pa, const SimArgs<T> A, const MlpDev<T> M) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int N = Pc.N;
+  const int N = rod_src_N<T>(Pa);
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = threadIdx.x / WAVE;
   const int64_t rod = (int64_t)blockIdx.x * MS_WPB + wv;
@@ -1622,11 +1624,12 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const RodCon
   // it finished leaves at once
   const int64_t t0 = A.resume ? (int64_t)A.resume[rod] : 0;
   if (t0 >= A.T_steps) return;
+  const auto& Pc = rod_src_row<T>(Pa, rod);
   const bool resumed = t0 > 0;
   const size_t rod_elems = (size_t)N * KR_SLOTS;
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * ms_lds_elems<T, HS>(N, true, NN), N, true, NN);
   const MsRole R = ms_role(lane, N);
-  ms_cold_fill<T>(Pc, L.cold, lane);
+  ms_cold_fill<T>(rod_src_mem<T>(Pa, rod), L.cold, lane);
   if constexpr (NN) {  // p-column blocks of the Jacobian (ms_newton): none known yet
     for (int e = lane; e < MS_BP_ELEMS; e += WAVE) L.Bp[e] = T(0);
   }

@@ -96,14 +96,17 @@ struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 
 
 // OCC: workgroups per CU the register allocation leaves room for.  OCC = 2 (fp32, batches beyond one rod per SIMD)
 // runs two rods on every SIMD, whose issue-bound sweeps and latency-bound algebra overlap (as kr_ms_impl.hpp's OCC).
-template <typename T, bool DIAG, int HS, int OCC = 1>
-__global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const RodConst<T> Pc, const SimArgs<T> A) {
+// PSRC: where a rod's constants come from - the kernel argument itself (RodConst<T>, all rods alike) or a per-rod
+// table (RodTable<T>, kr_tab_impl.hpp); see rod_src_row (rod_device.hpp).
+template <typename T, bool DIAG, int HS, int OCC = 1, typename PSRC = RodConst<T>>
+__global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC Pa, const SimArgs<T> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int N = Pc.N;
+  const int N = rod_src_N<T>(Pa);
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = threadIdx.x / WAVE;
   const int64_t rod = (int64_t)blockIdx.x * MS_WPB + wv;
   if (rod >= A.B) return;  // whole wavefront; there is no workgroup barrier in this kernel
+  const auto& Pc = rod_src_row<T>(Pa, rod);
   const size_t rod_elems = (size_t)N * KR_SLOTS;
   const int64_t T_steps = A.T_steps;
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * mso_lds_elems<T, HS>(N), N, true, false);
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const RodCo
   const int ib = isB ? lane - MSO_B0 : 0;
   const int s_l = isB ? ms_interval_start(ib, R.sbase, R.srem) : R.s_i;
   const int len_l = isB ? R.sbase + (ib < R.srem ? 1 : 0) : R.len_i;
-  ms_cold_fill<T>(Pc, L.cold, lane);
+  ms_cold_fill<T>(rod_src_mem<T>(Pa, rod), L.cold, lane);
   wave_sync();
 
   auto state_ptr = [&](int64_t k) -> T* { return A.states + (A.ring ? k % 3 : k) * A.slot_elems + rod * rod_elems; };

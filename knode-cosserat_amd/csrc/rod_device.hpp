@@ -22,6 +22,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "../../include/knode_rod.h"
 
 namespace kr {
@@ -59,6 +61,54 @@ struct RodConst {
   int N;
   int diag;
 };
+
+// Per-rod constants (kr_param_table): rows[b] belongs to rod b.  The table lives in global memory, is written by the
+// host only and never changes while a kernel that reads it is running - so the kernel sees it through the CONSTANT
+// address space, and the pointer carries that in its type from the kernel argument on (a cast inside the kernel is
+// folded away with the pointer's global origin, and the reads then are vector loads the compiler repeats after every
+// store).  N is shared by all rows (it fixes the data layout and the LDS carve-up), so it travels beside the pointer.
+#define KR_CONSTANT_AS __attribute__((address_space(4)))
+template <typename T>
+struct RodTable {
+  const KR_CONSTANT_AS RodConst<T>* rows;
+  int N;
+};
+// What a persistent kernel takes as its first argument: the launch-uniform RodConst<T> by value (every rod alike), or a
+// RodTable<T>.  rod_src_row yields the constants of one rod for the kernel's arithmetic: the kernel argument itself,
+// or - table - a local copy of the rod's row, read ONCE, unconditionally, where the kernel starts: scalar loads (the
+// address is wavefront-uniform, the memory constant) whose results the compiler keeps in SGPRs like those of the
+// kernel argument.  (Reading the row in place instead leaves the loads where the values are used: unlike the
+// kernel-argument segment the row is not known to be dereferenceable, so a load under a condition inside a sweep
+// cannot be hoisted out of it, and every trip pays s_load + s_waitcnt on the dependent chain of a lone wavefront.)
+// rod_src_mem is the row in memory, for accesses with a per-lane index (ms_cold_fill), which would force the local
+// copy into scratch.  `rod` must be the same in every lane of the wavefront.
+template <typename T>
+__device__ __forceinline__ int rod_src_N(const RodConst<T>& P) { return P.N; }
+template <typename T>
+__device__ __forceinline__ int rod_src_N(const RodTable<T>& P) { return P.N; }
+template <typename T>
+__device__ __forceinline__ const RodConst<T>& rod_src_mem(const RodConst<T>& P, int64_t) { return P; }
+template <typename T>
+__device__ __forceinline__ const RodConst<T>& rod_src_mem(const RodTable<T>& Tb, int64_t rod) {
+  const int row = __builtin_amdgcn_readfirstlane((int)rod);  // (uniform anyway; this lets the compiler know)
+  return *(const RodConst<T>*)(Tb.rows + row);
+}
+template <typename T>
+__device__ __forceinline__ const RodConst<T>& rod_src_row(const RodConst<T>& P, int64_t) { return P; }
+template <typename T>
+__device__ __forceinline__ RodConst<T> rod_src_row(const RodTable<T>& Tb, int64_t rod) {
+  constexpr int NT = 5 + 5 * 9 + 5 * 3 + 12 + 3 + 4 + 3 + 3;  // the T-typed members, which lead the struct
+  static_assert(offsetof(RodConst<T>, N) == NT * sizeof(T), "RodConst: the T-typed members must be contiguous");
+  const int row = __builtin_amdgcn_readfirstlane((int)rod);
+  const KR_CONSTANT_AS T* src = (const KR_CONSTANT_AS T*)(Tb.rows + row);
+  RodConst<T> P;
+  T* dst = reinterpret_cast<T*>(&P);
+#pragma unroll
+  for (int i = 0; i < NT; ++i) dst[i] = src[i];
+  P.N = Tb.N;
+  P.diag = 1;  // (the host admits only rows with diagonal material matrices)
+  return P;
+}
 
 template <typename T>
 __device__ __forceinline__ V3<T> matvec(const T (&A)[9], V3<T> x) {

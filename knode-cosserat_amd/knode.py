@@ -94,29 +94,62 @@ def _like(robot, values, is_np):
     return torch.tensor(values, device=robot.device)
 
 
-def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False):
+def _robots_rows(robot, robots, B):
+    """KrParams rows of ``robots`` for a heterogeneous ``simulate_batch``; host-side validation only (no device call)."""
+    robots = list(robots)
+    if len(robots) != B:
+        raise kn.KrError(f"simulate_batch: robots holds {len(robots)} rods, ctl {B}")
+    base = robot._params()
+    rows = [r._params() for r in robots]
+    for b, p in enumerate(rows):
+        for f in ("N", "del_t", "nn_input_history"):
+            if getattr(p, f) != getattr(base, f):
+                raise kn.KrError(f"simulate_batch: rod {b}: field {f} = {getattr(p, f)} differs from the carrier robot's "
+                                 f"{getattr(base, f)} (N, del_t and nn_input_history are shared by all rods of a launch)")
+    rc, bad, msg = kn.param_table_check(base, rows)
+    if rc != 0:
+        err = kn.KrError(f"libknode_rod error {rc}: {msg}")
+        err.code = rc
+        raise err
+    return rows
+
+
+def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
+                   robots=None):
     """B rods, each with its own tension history.
+
+    robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
+    reference's way (attributes, ``setup_robot(r, mod)``, ``compute_intermediate_terms()``): rod b runs with the
+    parameters of ``robots[b]`` - the reference's eight model-mismatch variants (knode.py:6-53) in one launch.
+    ``robot`` stays the carrier of N, del_t, the MLP and the device handle; N, del_t and nn_input_history must agree.
 
     ctl: array-like [B, T, 4].  Returns a dict with
       ``tip``    float[B, T, 3]  tip position after each solved step,
       ``status`` int32[B, T]     0 converged / 1 iteration cap / 2 non-finite,
       ``traj``   float[B, T+1, 25, N] (reference row order, entry 0 = initial state) unless ``tip_only``.
     All T steps are solved (no off-by-one drop here)."""
+    rows = None
+    if robots is not None:  # (validated on the host before anything touches the device)
+        rows = _robots_rows(robot, robots, int(np.asarray(ctl).shape[0]))
     import torch
     h = robot._native()
+    table = h.param_table(rows) if rows is not None else None
     dev = f"cuda:{robot.device}"
     tdt = torch.float64 if dtype in ("f64", torch.float64, np.float64) else torch.float32
     ctl_t = torch.as_tensor(np.asarray(ctl, dtype=np.float64), device=dev).to(tdt).contiguous()
     B, T = ctl_t.shape[0], ctl_t.shape[1]
     n_slots = 3 if tip_only else T + 1
     states = h.new_state(B, tdt, n_slots=n_slots)
-    h.init_straight(states[0])
+    h.init_straight(states[0], table=table)
     G = torch.zeros((B, 6), dtype=tdt, device=dev)  # knode.py:67
     tip = torch.empty((B, T, 3), dtype=tdt, device=dev)
     status = torch.zeros((B, T), dtype=torch.int32, device=dev)
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
-               scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn)
-    out = {"tip": tip.cpu().numpy(), "status": status.cpu().numpy(), "G": G.cpu().numpy()}
+               scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
+               table=table)
+    out = {"tip": tip.cpu().numpy(), "status": status.cpu().numpy(), "G": G.cpu().numpy()}  # (.cpu() waits for the run)
+    if table is not None:
+        table.close()
     if not tip_only and return_states:
         N = h.N
         traj = torch.empty((B, T + 1, 25, N), dtype=tdt, device=dev)

@@ -83,6 +83,11 @@ _PROTOS = {
     "kr_residual_mid_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "kr_step_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, C.c_double, _int, _vp, _vp, _int, _vp, _int, _int, _vp]),
     "kr_simulate_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int, _vp]),
+    "kr_param_table_check": (_int, [C.POINTER(KrParams), _i64, C.POINTER(KrParams), C.POINTER(_i64)]),
+    "kr_param_table_create": (_int, [_vp, _i64, C.POINTER(KrParams), C.POINTER(_vp)]),
+    "kr_param_table_destroy": (_int, [_vp]),
+    "kr_state_init_straight_table": (_int, [_vp, _vp, _vp, _int, _vp]),
+    "kr_simulate_batch_table": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int, _vp]),
     "kr_next_segment_physics": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp]),
     "kr_mlp_ws_bytes": (C.c_size_t, [_int, C.POINTER(C.c_int32), _i64]),
     "kr_mlp_forward": (_int, [_vp, _i64, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _vp, _int, _vp, _vp, _vp]),
@@ -193,6 +198,58 @@ def params_from_dict(d: dict) -> KrParams:
     return p
 
 
+def _params_array(rows):
+    rows = list(rows)
+    arr = (KrParams * max(len(rows), 1))()
+    for i, r in enumerate(rows):
+        if not isinstance(r, KrParams):
+            raise KrError(f"parameter table: row {i} is not a KrParams")
+        C.memmove(C.byref(arr, i * C.sizeof(KrParams)), C.byref(r), C.sizeof(KrParams))
+    return arr, len(rows)
+
+
+def param_table_check(base: KrParams, rows):
+    """Host-only (no GPU): may ``rows`` (sequence of KrParams) ride in one launch with ``base``?  Returns
+    ``(rc, bad_rod, message)``: rc 0, or KR_E_ARG / KR_E_UNSUPPORTED with the first offending row and the library's
+    message, which names the field."""
+    lib = load()
+    arr, n = _params_array(rows)
+    bad = _i64(-1)
+    rc = lib.kr_param_table_check(C.byref(base), n, arr if n else None, C.byref(bad))
+    msg = lib.kr_last_error() if rc else b""
+    return rc, bad.value, msg.decode() if msg else ""
+
+
+class ParamTable:
+    """Owns one kr_param_table: row b = the parameters of rod b of ``Handle.simulate(..., table=...)``.  Immutable;
+    usable as a context manager.  Close it only after the last call that uses it has finished on its stream."""
+
+    def __init__(self, handle: "Handle", rows):
+        self.lib = handle.lib
+        arr, n = _params_array(rows)
+        self.B = n
+        self._t = _vp()
+        check(self.lib.kr_param_table_create(handle._h, n, arr if n else None, C.byref(self._t)))
+
+    def close(self):
+        if getattr(self, "_t", None) is not None and self._t:
+            self.lib.kr_param_table_destroy(self._t)
+            self._t = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Handle:
     """Owns one kr_handle (one device, one parameter set)."""
 
@@ -281,8 +338,16 @@ class Handle:
         shape = (n_slots, B, self.N, KR_SLOTS) if n_slots > 1 else (B, self.N, KR_SLOTS)
         return torch.zeros(shape, dtype=dtype, device=f"cuda:{self.device}")
 
-    def init_straight(self, state):
+    def param_table(self, rows) -> ParamTable:
+        return ParamTable(self, rows)
+
+    def init_straight(self, state, table=None):
         B = state.shape[0]
+        if table is not None:  # rod b takes its length from row b
+            if B != table.B:
+                raise KrError(f"state holds {B} rods, the parameter table {table.B}")
+            check(self.lib.kr_state_init_straight_table(self._h, table._t, _ptr(state), dtype_code(state.dtype), _stream()))
+            return state
         check(self.lib.kr_state_init_straight(self._h, B, _ptr(state), dtype_code(state.dtype), _stream()))
         return state
 
@@ -362,8 +427,15 @@ class Handle:
         check(self.lib.kr_set_option(self._h, name.encode(), int(value)))
 
     def simulate(self, ctl, states, G, ring=False, tip=None, status=None, scheme=KR_EULER, tol=0.0, maxit=0,
-                 use_nn=False, prev_init=None):
+                 use_nn=False, prev_init=None, table=None):
         B, T = ctl.shape[0], ctl.shape[1]
+        if table is not None:  # rod b takes row b of the table instead of the handle's parameters
+            if B != table.B:
+                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
+            check(self.lib.kr_simulate_batch_table(self._h, table._t, T, scheme, _ptr(ctl), _ptr(states), int(bool(ring)),
+                                                   _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
+                                                   int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+            return
         check(self.lib.kr_simulate_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), int(bool(ring)), _ptr(G),
                                          _ptr(tip), float(tol), int(maxit), _ptr(status), int(bool(use_nn)),
                                          _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
