@@ -319,7 +319,8 @@ int kr_simulate_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void
  * the plain persistent kernel for MLP-on and overlap = 0.  Options residual_test, overlap, predictor, keep_predictor,
  * nn_* mean what they mean for kr_simulate_batch; waves_per_rod = 2 / 4, ms_mode = 0 and persistent = 0 are refused.
  * NOT served with a table: several wavefronts per rod, N > 128, single shooting, RK4, full material matrices, one
- * launch per step, kr_step_batch / kr_residual_* / kr_ode_batch, per-rod N / del_t / MLP, training. */
+ * launch per step, kr_step_batch / kr_residual_* / kr_ode_batch, per-rod N / del_t, training.  A per-rod MLP is served
+ * by kr_simulate_batch_bank (below), not by kr_simulate_batch_table. */
 typedef struct kr_param_table kr_param_table;
 
 /* Host arithmetic only (no handle, no GPU - like kr_derive): may rods_host[0..B) ride in one launch with `base`?
@@ -336,6 +337,54 @@ int kr_state_init_straight_table(kr_handle* h, const kr_param_table* t, void* st
 int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, void* states,
                             int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
                             const void* state_prev_init, int dtype, void* stream);
+
+/* ---- heterogeneous batches: per-rod networks (banks) ------------------- */
+/* The reference's model-mismatch experiment does not run one network for all models: for every mod it calls
+ * setup_robot(robot, mod) and then loads THAT model's own trained network from saved_models/..._{mod}_..._{seed}.pth
+ * before it simulates, for every seed (physics_multitrain.py:181-199).  A bank holds K networks of ONE shape;
+ * kr_simulate_batch_bank runs rod b with row b of a parameter table and network net_of_rod[b] of the bank - the
+ * (mod, seed) grid, a seed sweep, a checkpoint comparison or an ensemble in ONE launch instead of one kr_set_mlp and
+ * one launch per network.
+ *
+ * Shared by all K networks: n_layers, dims, acts (what a wavefront needs of its network then is one base address).
+ * Served (anything else: KR_E_UNSUPPORTED with a message that names the rule - never served from the handle's own
+ * MLP): what kr_simulate_batch_table serves with the MLP on - scheme KR_EULER; 9 <= N <= 128; diagonal material
+ * matrices (the table's rule); nn_input_history = 0; a shape the persistent one-wavefront kernel evaluates
+ * (28 -> H -> 25, or 28 -> H1 <= 64 -> H2 <= 192 -> 25 with one activation on both hidden layers; no output
+ * activation; option mfma_mlp on); the rod fits the LDS; KR_F32 and KR_F64.  A bank call always runs one wavefront per
+ * rod in one persistent launch (last_sim_path 2, last_waves_per_rod 1, last_overlap 0).  Options residual_test,
+ * predictor, keep_predictor, nn_* mean what they mean for kr_simulate_batch_table; waves_per_rod = 2 / 4,
+ * ms_mode = 0 and persistent = 0 are refused.
+ * NOT served with a bank: RK4, several wavefronts per rod, N > 128, single shooting, kr_ode_batch / kr_step_batch,
+ * networks of differing shape in one bank, training.
+ * The handle's own MLP (kr_set_mlp) is neither read nor changed by a bank or a bank call. */
+typedef struct kr_mlp_bank kr_mlp_bank;
+
+/* Host arithmetic only (no handle, no GPU - like kr_param_table_check): is a bank of K networks of this one shape
+ * served for rods with the shared fields of `base` (N, nn_input_history)?  KR_OK, KR_E_ARG (K < 1, a malformed shape)
+ * or KR_E_UNSUPPORTED with kr_last_error() naming the rule. */
+int kr_mlp_bank_check(const kr_params* base, int K, int n_layers, const int32_t* dims, const int32_t* acts);
+/* W, b: K * n_layers pointers, network-major (W[k * n_layers + l] = layer l of network k), each laid out as for
+ * kr_set_mlp; src_on_device as there.  Every network is packed exactly as kr_set_mlp packs the handle's own (the same
+ * gather plan, the same kernel): entry k is bit-identical to what kr_set_mlp would have produced for network k.  The
+ * K packed images lie a constant stride apart in one allocation.
+ * Source lifetime: the bank has finished reading W and b - host or device - when this call returns (it synchronises
+ * `stream`); the caller may free or overwrite them at once.
+ * The bank belongs to the handle's device and is immutable; it may be used with any handle on that device.  Destroy it
+ * after the last call that uses it has finished on its stream. */
+int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, const int32_t* acts,
+                       const float* const* W, const float* const* b, int src_on_device, void* stream,
+                       kr_mlp_bank** out);
+int kr_mlp_bank_destroy(kr_mlp_bank* bank);
+/* kr_simulate_batch_table with the MLP on (there is no use_nn), rod b evaluating network net_of_rod_host[b].
+ * net_of_rod_host: HOST array of B = the table's B entries.  Every entry is range-checked on the host BEFORE anything
+ * is copied or launched (KR_E_ARG naming the first bad rod; no output buffer is touched), then the array is copied to
+ * the device: the kernel never sees an index outside [0, K).  The array has been read when the call returns.
+ * t is required: build a table of identical rows when only the networks vary. */
+int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank,
+                           const int32_t* net_of_rod_host, int64_t T, int scheme, const void* ctl, void* states,
+                           int ring, void* G, void* tip, double tol, int maxit, int32_t* status,
+                           const void* state_prev_init, int dtype, void* stream);
 
 /* ---- KNODE one-step-ahead training path -------------------------------- */
 /* CosseratRodTorch.parallelGetNextSegmentEuler (cosserat_ode_torch.py:401-437)

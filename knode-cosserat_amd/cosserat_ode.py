@@ -49,6 +49,19 @@ def mlp_from_layer_strings(model, param_ls):
     return weights, biases, acts
 
 
+def mlp_digest(model, param_ls, nn_input_history):
+    """Identity of a network: a digest of the layer strings and of every parameter byte (CosseratRod._push_mlp, and
+    the deduplication of ``knode.simulate_batch(..., per_robot_nn=True)``)."""
+    import hashlib
+    dg = hashlib.blake2b(digest_size=16)
+    dg.update(("|".join(str(m) for m in model) + f"|{bool(nn_input_history)}").encode())
+    for p_ in param_ls:
+        a = np.ascontiguousarray(np.asarray(p_, dtype=np.float32))
+        dg.update(str(a.shape).encode())
+        dg.update(a.tobytes())
+    return dg.digest()
+
+
 class CosseratRod:
     def __init__(self, nn_path=None, use_fsolve=False, nn_input_history=False, device=0):
         self.verbose = False
@@ -132,14 +145,7 @@ class CosseratRod:
         """Packs and uploads the network only when it changed: the key is a digest of every parameter byte and
         of the layer strings, so repeated ``simulate`` / ``get_nn_output`` calls with the same weights reuse the
         packed copies the handle already holds (kr_set_mlp allocates and copies synchronously)."""
-        import hashlib
-        dg = hashlib.blake2b(digest_size=16)
-        dg.update(("|".join(str(m) for m in model) + f"|{bool(self.nn_input_history)}").encode())
-        for p_ in param_ls:
-            a = np.ascontiguousarray(np.asarray(p_, dtype=np.float32))
-            dg.update(str(a.shape).encode())
-            dg.update(a.tobytes())
-        key = dg.digest()
+        key = mlp_digest(model, param_ls, self.nn_input_history)
         if key != self._mlp_key:
             self._handle.set_mlp(*mlp_from_layer_strings(model, param_ls))
             self._mlp_key = key

@@ -515,6 +515,7 @@ int kr_destroy(kr_handle* h) {
   if (h->ws) (void)hipFree(h->ws);
   if (h->pred_buf) (void)hipFree(h->pred_buf);
   if (h->resume_buf) (void)hipFree(h->resume_buf);
+  if (h->net_idx_buf) (void)hipFree(h->net_idx_buf);
   if (h->hist_ws) (void)hipFree(h->hist_ws);
   if (h->loss_scratch) (void)hipFree(h->loss_scratch);
   if (h->order_event) (void)hipEventDestroy(h->order_event);
@@ -588,6 +589,7 @@ struct kr_mlp_plan {
   kr::PackJobs jobs{};
   uint32_t* idx = nullptr;    // device: source code of every destination element
   unsigned char* arena = nullptr;  // device: every packed buffer
+  size_t arena_bytes = 0;     // ... of ONE network (a multiple of 256); a bank's arena holds `copies` of them
   float* staging = nullptr;   // device copy of host-side sources (src_on_device = 0)
   size_t src_off[2 * KR_MAX_LAYERS + 1] = {};
 };
@@ -605,7 +607,9 @@ void free_mlp_plan(kr_handle* h) {
 
 // Builds the plan of one shape.  The layouts are those of mlp_lane.hpp (Wt, b), mlp_mfma.hpp (wfrag, bfrag), mlp_jvp.hpp
 // (wq, bq, jfrag, w32, b32); every buffer is described by the source code of each of its elements.
-static int build_mlp_plan(kr_handle* h, int n_layers, const int32_t* dims, const int32_t* acts, kr_mlp_plan& P) {
+// `copies` > 1 (kr_mlp_bank_create): the arena has room for that many packed images, arena_bytes apart; the plan
+// describes the first.
+static int build_mlp_plan(kr_handle* h, int n_layers, const int32_t* dims, const int32_t* acts, kr_mlp_plan& P, size_t copies = 1) {
   MlpDev<float>& mf = P.mf;
   MlpDev<double>& md = P.md;
   mf = MlpDev<float>{};
@@ -758,7 +762,8 @@ static int build_mlp_plan(kr_handle* h, int n_layers, const int32_t* dims, const
     total += jobs[j].code.size();
   }
   if (total >= 0xFFFFFFF0ull) { set_error("kr_set_mlp: network too large"); return KR_E_ARG; }
-  KR_HIP(hipMalloc(&P.arena, arena_bytes));
+  P.arena_bytes = arena_bytes;
+  KR_HIP(hipMalloc(&P.arena, arena_bytes * copies));
   KR_HIP(hipMalloc(&P.idx, total * sizeof(uint32_t)));
   KR_HIP(hipMalloc(&P.staging, P.src_off[2 * n_layers] * sizeof(float)));
   std::vector<uint32_t> all(total);
@@ -1123,6 +1128,191 @@ int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, in
                                           state_prev_init, s)
              : simulate_table_impl<double>(h, t, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
                                            state_prev_init, s);
+}
+
+// ---- per-rod networks: banks ----------------------------------------------------------------------------------------
+// the argument rules of kr_set_mlp for a bank's shape, then the rules of what the bank kernels serve
+static int bank_check_shape(int nn_input_history, int N, int K, int n_layers, const int32_t* dims, const int32_t* acts) {
+  const std::string who = "network bank: ";
+  if (K < 1) { set_error(who + "K must be >= 1"); return KR_E_ARG; }
+  if (n_layers < 1 || n_layers > KR_MAX_LAYERS) { set_error(who + "n_layers out of range"); return KR_E_ARG; }
+  for (int k = 0; k <= n_layers; ++k)
+    if (dims[k] <= 0) { set_error(who + "bad layer width"); return KR_E_ARG; }
+  for (int k = 0; k < n_layers; ++k)
+    if (acts[k] < KR_ACT_NONE || acts[k] > KR_ACT_ELU) { set_error(who + "bad activation code"); return KR_E_ARG; }
+  if ((dims[0] != 28 && dims[0] != 53) || dims[n_layers] != 25) {
+    set_error(who + "a network must map 28 -> 25 (cosserat_ode_torch.py:60-62)");
+    return KR_E_ARG;
+  }
+  auto refuse = [&](const std::string& rule) {
+    set_error(who + rule + " (bank calls serve what the persistent one-wavefront kernel evaluates)");
+    return KR_E_UNSUPPORTED;
+  };
+  if (nn_input_history || dims[0] == 53) return refuse("nn_input_history = 0 only: the 53-input history form is not served");
+  if (N - 1 < 8 || N > 128) return refuse("N = " + std::to_string(N) + ", bank calls serve 9 <= N <= 128");
+  // (the conditions of mfma_ok && jvp_ok, build_mlp_plan)
+  if (n_layers != 2 && n_layers != 3) return refuse("n_layers = " + std::to_string(n_layers) + ", two or three layers only");
+  if (acts[n_layers - 1] != KR_ACT_NONE) return refuse("the output layer must have no activation");
+  if (n_layers == 3 && dims[1] > 64) return refuse("first hidden layer of " + std::to_string(dims[1]) + " units, at most 64 with three layers");
+  if (n_layers == 3 && acts[0] != acts[1]) return refuse("mixed activations: both hidden layers must share one");
+  if (n_layers == 3 && dims[2] > 64 * 3) return refuse("second hidden layer of " + std::to_string(dims[2]) + " units, at most 192");
+  return KR_OK;
+}
+
+int kr_mlp_bank_check(const kr_params* base, int K, int n_layers, const int32_t* dims, const int32_t* acts) {
+  KR_CHECK_PTR(base);
+  KR_CHECK_PTR(dims);
+  KR_CHECK_PTR(acts);
+  return bank_check_shape(base->nn_input_history, base->N, K, n_layers, dims, acts);
+}
+
+int kr_mlp_bank_destroy(kr_mlp_bank* bk) {
+  if (!bk) return KR_OK;
+  if (bk->arena) (void)hipFree(bk->arena);
+  delete bk;
+  return KR_OK;
+}
+
+int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* W,
+                       const float* const* b, int src_on_device, void* stream, kr_mlp_bank** out) {
+  KR_CHECK_H(h);
+  KR_CHECK_PTR(out);
+  *out = nullptr;
+  KR_CHECK_PTR(dims); KR_CHECK_PTR(acts); KR_CHECK_PTR(W); KR_CHECK_PTR(b);
+  if (int rc = bank_check_shape(h->params.nn_input_history, h->params.N, K, n_layers, dims, acts)) return rc;
+  for (int i = 0; i < K * n_layers; ++i) { KR_CHECK_PTR(W[i]); KR_CHECK_PTR(b[i]); }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc_order_ = order_stream(h, s)) return rc_order_;
+  // the gather plan of kr_set_mlp for this shape, its arena K images long
+  kr_mlp_plan P;
+  auto drop = [&P]() {
+    if (P.idx) (void)hipFree(P.idx);
+    if (P.staging) (void)hipFree(P.staging);
+    if (P.arena) (void)hipFree(P.arena);
+  };
+  if (int rc = build_mlp_plan(h, n_layers, dims, acts, P, (size_t)K)) { drop(); return rc; }
+  if (!P.mf.mfma_ok || !P.mf.jvp_ok) {  // (bank_check_shape restates these rules; the plan has the last word)
+    drop();
+    set_error("network bank: a shape the persistent one-wavefront kernel does not evaluate");
+    return KR_E_UNSUPPORTED;
+  }
+  const uint32_t total = P.jobs.start[P.jobs.n];
+  int grid = (int)((total + 255) / 256);
+  if (grid > 1024) grid = 1024;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < K && e == hipSuccess; ++k) {
+    PackJobs J = P.jobs;
+    for (int j = 0; j < J.n; ++j) J.dst[j] = static_cast<unsigned char*>(J.dst[j]) + (size_t)k * P.arena_bytes;
+    for (int l = 0; l < n_layers && e == hipSuccess; ++l) {
+      const float* Wl = W[(size_t)k * n_layers + l];
+      const float* bl = b[(size_t)k * n_layers + l];
+      if (src_on_device) {
+        J.src[2 * l] = Wl;
+        J.src[2 * l + 1] = bl;
+      } else {  // (one staging area: network k + 1 is copied in only after the pack launch of network k has finished, below)
+        e = hipMemcpyAsync(P.staging + P.src_off[2 * l], Wl, sizeof(float) * dims[l] * dims[l + 1], hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(P.staging + P.src_off[2 * l + 1], bl, sizeof(float) * dims[l + 1], hipMemcpyHostToDevice, s);
+        J.src[2 * l] = P.staging + P.src_off[2 * l];
+        J.src[2 * l + 1] = P.staging + P.src_off[2 * l + 1];
+      }
+    }
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(kr::mlp_pack_kernel, dim3(grid), dim3(256), 0, s, J, P.idx);
+    e = hipGetLastError();
+    if (e == hipSuccess && !src_on_device) e = hipStreamSynchronize(s);
+  }
+  // the bank has read its sources, host or device, when this returns; the plan's index table and staging go with it
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    drop();
+    return hip_fail(e, "kr_mlp_bank_create");
+  }
+  kr_mlp_bank* bk = new kr_mlp_bank();
+  bk->device = h->device;
+  bk->K = K;
+  bk->mf = P.mf;
+  bk->md = P.md;
+  bk->stride = P.arena_bytes;
+  bk->arena = P.arena;
+  P.arena = nullptr;
+  drop();
+  *out = bk;
+  return KR_OK;
+}
+
+static int ensure_net_idx(kr_handle* h, int64_t B) {
+  const size_t bytes = (size_t)B * sizeof(int32_t);
+  if (bytes <= h->net_idx_cap) return KR_OK;
+  if (h->net_idx_buf) {
+    KR_HIP(hipDeviceSynchronize());
+    KR_HIP(hipFree(h->net_idx_buf));
+    h->net_idx_buf = nullptr;
+    h->net_idx_cap = 0;
+  }
+  KR_HIP(hipMalloc(&h->net_idx_buf, bytes + bytes / 4));
+  h->net_idx_cap = bytes + bytes / 4;
+  return KR_OK;
+}
+
+extern "C++" {
+template <typename T>
+static int simulate_bank_impl(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, int64_t T_steps, int scheme,
+                              const void* ctl, void* states, int ring, void* G, void* tip, double tol, int maxit,
+                              int32_t* status, const void* prev_init, hipStream_t s) {
+  const int64_t B = t->B;
+  auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, G, ctl, 4, tol, maxit);
+  SimArgs<T> sa{};
+  sa.B = B; sa.T_steps = T_steps; sa.states = (T*)states; sa.slot_elems = (int64_t)((size_t)B * t->N * KR_SLOTS); sa.ring = ring;
+  sa.prev_init = (const T*)prev_init; sa.ctl = (const T*)ctl; sa.G = (T*)G; sa.tip = (T*)tip; sa.status = status;
+  sa.tol = a0.tol; sa.tolA = a0.tolA; sa.fd_eps = a0.fd_eps; sa.hc1 = a0.hc1; sa.hc2 = a0.hc2;
+  sa.maxit = a0.maxit; sa.predictor = h->predictor; sa.residual_test = h->residual_test; sa.nn_lowp = h->nn_lowp_first; sa.nn_base_only = h->nn_base_only_store;
+  sa.dbg = static_cast<unsigned long long*>(h->dbg);
+  sa.pred_io = nullptr; sa.pred_load = 0;
+  // option keep_predictor works as in kr_simulate_batch_table (the image is a starting guess, whatever network wrote it)
+  if (h->keep_predictor && (size_t)B * KR_PRED_IMG_DOUBLES * sizeof(double) <= ((size_t)1 << 30)) {
+    if (int rcp = ensure_pred(h, B)) return rcp;
+    sa.pred_io = static_cast<double*>(h->pred_buf);
+    sa.pred_load = h->pred_valid_B == B && h->pred_valid_W == 1 && h->pred_valid_nn == 1;
+  }
+  const int rc = launch_bank_sim<T>(h, t, bk, static_cast<const int32_t*>(h->net_idx_buf), scheme, sa, s);
+  if (rc == KR_OK) {
+    h->last_sim_path = 2;
+    if (sa.pred_io) { h->pred_valid_B = B; h->pred_valid_W = 1; h->pred_valid_nn = 1; }
+  }
+  return rc;
+}
+}  // extern "C++"
+
+int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank, const int32_t* net_of_rod_host,
+                           int64_t T, int scheme, const void* ctl, void* states, int ring, void* G, void* tip, double tol,
+                           int maxit, int32_t* status, const void* state_prev_init, int dtype, void* stream) {
+  KR_CHECK_PTR(t);
+  KR_CHECK_PTR(bank);
+  KR_CHECK_PTR(net_of_rod_host);
+  KR_CHECK_H(h);
+  KR_CHECK_DTYPE(dtype);
+  if (int rc = tab_matches(h, t)) return rc;
+  if (bank->device != h->device) { set_error("network bank: device of the bank differs from the handle's"); return KR_E_ARG; }
+  // every index is checked here, on the host, before anything is copied or launched
+  for (int64_t b = 0; b < t->B; ++b)
+    if (net_of_rod_host[b] < 0 || net_of_rod_host[b] >= bank->K) {
+      set_error("network bank: rod " + std::to_string(b) + " asks for network " + std::to_string(net_of_rod_host[b]) +
+                ", the bank holds " + std::to_string(bank->K));
+      return KR_E_ARG;
+    }
+  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
+  if (T == 0 || t->B == 0) return KR_OK;
+  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc_order_ = order_stream(h, s)) return rc_order_;
+  if (int rc = ensure_net_idx(h, t->B)) return rc;
+  // queued behind the previous bank call's kernel, which reads the same buffer; the caller's array has been read when
+  // this call returns
+  KR_HIP(hipMemcpyAsync(h->net_idx_buf, net_of_rod_host, sizeof(int32_t) * (size_t)t->B, hipMemcpyHostToDevice, s));
+  KR_HIP(hipStreamSynchronize(s));
+  return dtype == KR_F32
+             ? simulate_bank_impl<float>(h, t, bank, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, state_prev_init, s)
+             : simulate_bank_impl<double>(h, t, bank, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, state_prev_init, s);
 }
 
 int kr_simulate_prepare(kr_handle* h, int64_t B, int dtype) {

@@ -1,0 +1,6 @@
+// float instantiation of the persistent kernel with per-rod parameter tables and per-rod networks (kr_bank_impl.hpp)
+#define KR_MS_NO_INST
+#include "kr_bank_impl.hpp"
+namespace kr {
+template int launch_bank_sim<float>(kr_handle*, const kr_param_table*, const kr_mlp_bank*, const int32_t*, int, const SimArgs<float>&, hipStream_t);
+}

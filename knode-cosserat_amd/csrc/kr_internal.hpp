@@ -105,6 +105,8 @@ struct kr_handle {
   int nn_base_only_store = 1;  // fp64, MLP on, persistent one-wavefront kernel: storing sweeps without forward-difference columns
   void* resume_buf = nullptr;  // int32 per rod (SimArgs::resume)
   size_t resume_cap = 0;
+  void* net_idx_buf = nullptr;  // int32 per rod: the network of rod b of a kr_simulate_batch_bank call (MlpBank::net_of_rod)
+  size_t net_idx_cap = 0;
   void* hist_ws = nullptr;     // history records [B][N][12] of the several-wavefront persistent kernel with the MLP on
   size_t hist_ws_cap = 0;
   // Stream ordering of the handle's scratch (ws, pred_buf, resume_buf, hist_ws, loss_scratch are shared by its calls):
@@ -128,7 +130,28 @@ struct kr_param_table {
   double* L = nullptr;                     // [B], device: rod lengths (kr_state_init_straight_table)
 };
 
+// Bank of K networks of one shape (kr_mlp_bank_create): every network packed like the handle's own (the gather plan
+// and mlp_pack_kernel of kr_set_mlp), the K packed images `stride` bytes apart in one arena - network k's buffers are
+// those of network 0 (mf / md) moved by k * stride.  Immutable after creation.
+struct kr_mlp_bank {
+  int device = 0;
+  int K = 0;
+  kr::MlpDev<float> mf{};    // descriptor of network 0
+  kr::MlpDev<double> md{};
+  size_t stride = 0;         // bytes, a multiple of 256
+  unsigned char* arena = nullptr;  // [K][stride], device
+};
+
 namespace kr {
+
+// What a bank kernel takes in place of the by-value MlpDev<T> (ms_sim_kernel, MSRC): rod b runs network
+// net_of_rod[b].  Like the rows of a parameter table the index array is written by the host only and never changes
+// while a kernel reads it: constant address space, from the kernel argument on (mlp_src_net, kr_ms_impl.hpp).
+template <typename T>
+struct MlpBank : MlpDev<T> {  // (the base: the descriptor of network 0)
+  const KR_CONSTANT_AS int32_t* net_of_rod;  // [B], every entry in [0, K): checked on the host before the launch
+  unsigned long long stride;                 // bytes between the packed images of two networks
+};
 
 int ensure_ws(kr_handle* h, size_t bytes);
 // Makes work queued on `s` from here on run after everything the handle's previous calls queued on ANOTHER stream (an
@@ -271,6 +294,18 @@ template <typename T>
 int launch_tab_sim(kr_handle* h, const kr_param_table* t, int scheme, int use_nn, const SimArgs<T>& a, hipStream_t s);
 template <typename T>
 int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s);
+// kr_bank_f32.hip / kr_bank_f64.hip: the MLP-on persistent kernel with per-rod constants AND per-rod networks
+// (kr_bank_impl.hpp).  net_idx: device copy of the caller's index array.  Refuses what it does not serve; nothing
+// falls back to the handle's own MLP.
+template <typename T>
+inline const MlpDev<T>& bank_net0(const kr_mlp_bank* bk);
+template <>
+inline const MlpDev<float>& bank_net0<float>(const kr_mlp_bank* bk) { return bk->mf; }
+template <>
+inline const MlpDev<double>& bank_net0<double>(const kr_mlp_bank* bk) { return bk->md; }
+template <typename T>
+int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, const int32_t* net_idx, int scheme,
+                    const SimArgs<T>& a, hipStream_t s);
 // kr_sim_f32.hip / kr_sim_f64.hip: the same for the one-wavefront persistent kernel that runs behind it
 template <typename T>
 int prepare_ms_sim(kr_handle* h);

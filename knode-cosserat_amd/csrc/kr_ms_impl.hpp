@@ -1604,6 +1604,30 @@ __global__ __launch_bounds__(WAVE * MS_WPB) void ms_step_kernel(const RodConst<T
 // ---------------------------------------------------------------------------
 // persistent form: one launch runs all T steps of kr_simulate_batch; a wavefront keeps its rod
 // ---------------------------------------------------------------------------
+// The network of one rod of a bank kernel (MSRC = MlpBank<T>; otherwise the network is the kernel argument itself), as
+// rod_src_row yields a rod's constants: a descriptor formed ONCE where the kernel starts.  The rod's network index is
+// one scalar load through the constant address space (uniform address, invariant memory), read unconditionally, and
+// every buffer of network k lies k * stride bytes behind the same buffer of network 0 (pointers of layers the shape
+// does not have are moved too and, as before, never followed).  The sweeps below receive this descriptor like the
+// by-value one; neither the index nor a base address is formed again inside a loop.  `rod` must be the same in every
+// lane of the wavefront.
+template <typename T>
+__device__ __forceinline__ MlpDev<T> mlp_src_net(const MlpBank<T>& Bk, int64_t rod) {
+  const int row = __builtin_amdgcn_readfirstlane((int)rod);  // (uniform anyway; this lets the compiler know)
+  const unsigned long long off = (unsigned long long)(unsigned)Bk.net_of_rod[row] * Bk.stride;
+  MlpDev<T> M = Bk;  // (network 0)
+  auto at = [off](auto* p) { return reinterpret_cast<decltype(p)>(reinterpret_cast<const unsigned char*>(p) + off); };
+#pragma unroll
+  for (int k = 0; k < KR_MAX_LAYERS; ++k) {
+    M.Wt[k] = at(M.Wt[k]); M.b[k] = at(M.b[k]);
+    M.wfrag[k] = at(M.wfrag[k]); M.bfrag[k] = at(M.bfrag[k]);
+    M.jfrag[k] = at(M.jfrag[k]);
+    M.wq[k] = at(M.wq[k]); M.bq[k] = at(M.bq[k]);
+    M.w32[k] = at(M.w32[k]); M.b32[k] = at(M.b32[k]);
+  }
+  return M;
+}
+
 constexpr int MS_NPL = 2;  // grid points per lane held in registers by the persistent kernel (N <= 128)
 
 // OCC: workgroups the register allocation must leave room for on a CU (__launch_bounds__).  With OCC = 2 the fp32
@@ -1612,8 +1636,10 @@ constexpr int MS_NPL = 2;  // grid points per lane held in registers by the pers
 // wavefront anyway (68 spilled registers).  In fp64 a rod needs 37.8 KB of LDS: four per CU, one per SIMD.
 // PSRC: the rod's constants come from the kernel argument itself (RodConst<T>) or from a per-rod table (RodTable<T>,
 // kr_tab_impl.hpp); see rod_src_row (rod_device.hpp).
-template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1, typename PSRC = RodConst<T>>
-__global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC Pa, const SimArgs<T> A, const MlpDev<T> M) {
+// MSRC: the network is the kernel argument itself (MlpDev<T>, one network for every rod) or the rod's entry of a bank
+// (MlpBank<T>, kr_bank_impl.hpp); see mlp_src_net.
+template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1, typename PSRC = RodConst<T>, typename MSRC = MlpDev<T>>
+__global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC Pa, const SimArgs<T> A, const MSRC Ma) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int N = rod_src_N<T>(Pa);
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1625,6 +1651,12 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
   const int64_t t0 = A.resume ? (int64_t)A.resume[rod] : 0;
   if (t0 >= A.T_steps) return;
   const auto& Pc = rod_src_row<T>(Pa, rod);
+  // (a direct binding, not a call that returns the reference: through a call hipcc 7.2 generates the fp64 MLP-on
+  //  instantiations differently - tools/bank_asm_compare.py, part 1)
+  constexpr bool BANK = !std::is_same<MSRC, MlpDev<T>>::value;
+  MlpDev<T> Mrod;  // bank only: the rod's own descriptor
+  if constexpr (BANK) Mrod = mlp_src_net<T>(Ma, rod);
+  const MlpDev<T>& M = BANK ? Mrod : static_cast<const MlpDev<T>&>(Ma);
   const bool resumed = t0 > 0;
   const size_t rod_elems = (size_t)N * KR_SLOTS;
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * ms_lds_elems<T, HS>(N, true, NN), N, true, NN);

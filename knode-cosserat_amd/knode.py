@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 import krod_native as kn
-from cosserat_ode import CosseratRod
+from cosserat_ode import CosseratRod, mlp_digest, mlp_from_layer_strings
 
 _MODS = (None, "noair", "nsw", "short", "damping", "dampstiff", "lengthstiff", "youngs")
 
@@ -114,8 +114,53 @@ def _robots_rows(robot, robots, B):
     return rows
 
 
+def _robots_networks(robot, robots):
+    """Networks of ``robots`` for ``simulate_batch(..., per_robot_nn=True)``: ``(networks, net_of_rod)`` with the
+    distinct networks in order of first appearance (the digest of CosseratRod._push_mlp tells them apart).  Host-side
+    validation only (no device call)."""
+    base = robot._params()
+    keys, networks, net_of_rod = {}, [], []
+    model0 = shape0 = None
+    for b, r in enumerate(robots):
+        model, param_ls = getattr(r, "nn_model", None), getattr(r, "param_ls", None)
+        if getattr(r, "nn_path", None) is None or model is None or param_ls is None:
+            raise kn.KrError(f"simulate_batch: rod {b}: per_robot_nn needs a network on every robot (nn_path / nn_model / "
+                             "param_ls, as the reference leaves a robot after loading nn_path)")
+        if bool(r.nn_input_history) != bool(robot.nn_input_history):
+            raise kn.KrError(f"simulate_batch: rod {b}: nn_input_history = {bool(r.nn_input_history)} differs from the "
+                             f"carrier robot's {bool(robot.nn_input_history)}")
+        names = [str(m) for m in model]
+        if model0 is None:
+            model0 = names
+        elif names != model0:
+            raise kn.KrError(f"simulate_batch: rod {b}: layers {names} differ from rod 0's {model0} (the networks of one "
+                             "launch share one shape)")
+        key = mlp_digest(model, param_ls, r.nn_input_history)
+        if key not in keys:
+            net = mlp_from_layer_strings(model, param_ls)
+            try:
+                dims, acts, _ = kn._bank_shape([net])
+            except kn.KrError as e:
+                raise kn.KrError(f"simulate_batch: rod {b}: {e}") from None
+            if shape0 is None:
+                shape0 = (dims, acts)
+            elif (dims, acts) != shape0:
+                raise kn.KrError(f"simulate_batch: rod {b}: network of layer widths {dims}, rod 0's has {shape0[0]} (the "
+                                 "networks of one launch share one shape)")
+            keys[key] = len(networks)
+            networks.append(net)
+        net_of_rod.append(keys[key])
+    dims, acts = shape0
+    rc, msg = kn.mlp_bank_check(base, len(networks), dims, acts)
+    if rc != 0:
+        err = kn.KrError(f"libknode_rod error {rc}: {msg}")
+        err.code = rc
+        raise err
+    return networks, net_of_rod
+
+
 def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
-                   robots=None):
+                   robots=None, per_robot_nn=False):
     """B rods, each with its own tension history.
 
     robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
@@ -123,17 +168,29 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     parameters of ``robots[b]`` - the reference's eight model-mismatch variants (knode.py:6-53) in one launch.
     ``robot`` stays the carrier of N, del_t, the MLP and the device handle; N, del_t and nn_input_history must agree.
 
+    per_robot_nn (needs ``robots``): rod b also runs with the NETWORK ``robots[b]`` carries (``nn_model`` /
+    ``param_ls``) - the reference loads every model variant's own trained network before it simulates
+    (physics_multitrain.py:181-199).  Robots that carry the same network share one upload; the result gains
+    ``net_of_rod`` int[B] and ``n_networks``.  All networks must have one shape; the carrier's own MLP is not used.
+
     ctl: array-like [B, T, 4].  Returns a dict with
       ``tip``    float[B, T, 3]  tip position after each solved step,
       ``status`` int32[B, T]     0 converged / 1 iteration cap / 2 non-finite,
       ``traj``   float[B, T+1, 25, N] (reference row order, entry 0 = initial state) unless ``tip_only``.
     All T steps are solved (no off-by-one drop here)."""
     rows = None
+    networks = net_of_rod = None
     if robots is not None:  # (validated on the host before anything touches the device)
+        robots = list(robots)
         rows = _robots_rows(robot, robots, int(np.asarray(ctl).shape[0]))
+    if per_robot_nn:
+        if robots is None:
+            raise kn.KrError("simulate_batch: per_robot_nn needs robots=[...]")
+        networks, net_of_rod = _robots_networks(robot, robots)
     import torch
     h = robot._native()
     table = h.param_table(rows) if rows is not None else None
+    bank = h.mlp_bank(networks) if networks is not None else None
     dev = f"cuda:{robot.device}"
     tdt = torch.float64 if dtype in ("f64", torch.float64, np.float64) else torch.float32
     ctl_t = torch.as_tensor(np.asarray(ctl, dtype=np.float64), device=dev).to(tdt).contiguous()
@@ -146,10 +203,14 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     status = torch.zeros((B, T), dtype=torch.int32, device=dev)
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
                scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
-               table=table)
+               table=table, bank=bank, net_of_rod=net_of_rod)
     out = {"tip": tip.cpu().numpy(), "status": status.cpu().numpy(), "G": G.cpu().numpy()}  # (.cpu() waits for the run)
     if table is not None:
         table.close()
+    if bank is not None:
+        out["net_of_rod"] = np.asarray(net_of_rod, dtype=np.int32)
+        out["n_networks"] = bank.K
+        bank.close()
     if not tip_only and return_states:
         N = h.N
         traj = torch.empty((B, T + 1, 25, N), dtype=tdt, device=dev)

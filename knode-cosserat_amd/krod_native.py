@@ -88,6 +88,12 @@ _PROTOS = {
     "kr_param_table_destroy": (_int, [_vp]),
     "kr_state_init_straight_table": (_int, [_vp, _vp, _vp, _int, _vp]),
     "kr_simulate_batch_table": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int, _vp]),
+    "kr_mlp_bank_check": (_int, [C.POINTER(KrParams), _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "kr_mlp_bank_create": (_int, [_vp, _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _int, _vp,
+                                  C.POINTER(_vp)]),
+    "kr_mlp_bank_destroy": (_int, [_vp]),
+    "kr_simulate_batch_bank": (_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp,
+                                      _vp, _int, _vp]),
     "kr_next_segment_physics": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp]),
     "kr_mlp_ws_bytes": (C.c_size_t, [_int, C.POINTER(C.c_int32), _i64]),
     "kr_mlp_forward": (_int, [_vp, _i64, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _vp, _int, _vp, _vp, _vp]),
@@ -250,6 +256,83 @@ class ParamTable:
             pass
 
 
+def _bank_shape(networks):
+    """(dims, acts, per-network float32 arrays) of a sequence of (weights, biases, acts); every network must have the
+    shape of the first.  Host only."""
+    nets = list(networks)
+    if not nets:
+        return [], [], []
+    packed, dims0, acts0 = [], None, None
+    for k, (weights, biases, acts) in enumerate(nets):
+        Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+        bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
+        if not Ws or len(Ws) != len(bs) or len(Ws) != len(acts) or any(w.ndim != 2 for w in Ws):
+            raise KrError(f"network bank: network {k}: malformed layer lists")
+        dims = [Ws[0].shape[1]] + [w.shape[0] for w in Ws]
+        for l in range(len(Ws)):
+            if Ws[l].shape[1] != dims[l] or bs[l].shape != (dims[l + 1],):
+                raise KrError(f"network bank: network {k}, layer {l}: inconsistent shapes {Ws[l].shape} / {bs[l].shape}")
+        acts = [int(a) for a in acts]
+        if dims0 is None:
+            dims0, acts0 = dims, acts
+        elif dims != dims0 or acts != acts0:
+            raise KrError(f"network bank: network {k} has layers {dims} / activations {acts}, network 0 {dims0} / {acts0} "
+                          "(all networks of a bank share one shape)")
+        packed.append((Ws, bs))
+    return dims0, acts0, packed
+
+
+def mlp_bank_check(base: KrParams, K: int, dims, acts):
+    """Host-only (no GPU): is a bank of K networks with layer widths ``dims`` and activation codes ``acts`` served for
+    rods like ``base``?  Returns ``(rc, message)``; the message names the rule."""
+    lib = load()
+    n = len(acts)
+    dims_c = (C.c_int32 * max(len(dims), 1))(*[int(d) for d in dims])
+    acts_c = (C.c_int32 * max(n, 1))(*[int(a) for a in acts])
+    rc = lib.kr_mlp_bank_check(C.byref(base), int(K), n, dims_c, acts_c)
+    msg = lib.kr_last_error() if rc else b""
+    return rc, msg.decode() if msg else ""
+
+
+class MlpBank:
+    """Owns one kr_mlp_bank: K networks of one shape, ``networks[k] = (weights, biases, acts)`` as for
+    ``Handle.set_mlp``; rod b of ``Handle.simulate(..., table=, bank=, net_of_rod=)`` evaluates network
+    ``net_of_rod[b]``.  Immutable; usable as a context manager.  Close it only after the last call that uses it has
+    finished on its stream."""
+
+    def __init__(self, handle: "Handle", networks):
+        self.lib = handle.lib
+        dims, acts, packed = _bank_shape(networks)
+        self.K = len(packed)
+        self.dims, self.acts = tuple(dims), tuple(acts)
+        n = len(acts)
+        dims_c = (C.c_int32 * max(len(dims), 1))(*dims)
+        acts_c = (C.c_int32 * max(n, 1))(*acts)
+        Wp = (_vp * max(self.K * n, 1))(*[w.ctypes.data for Ws, _ in packed for w in Ws])
+        bp = (_vp * max(self.K * n, 1))(*[b.ctypes.data for _, bs in packed for b in bs])
+        self._b = _vp()
+        # (the library has read the host arrays when create returns: `packed` need not outlive this call)
+        check(self.lib.kr_mlp_bank_create(handle._h, self.K, n, dims_c, acts_c, Wp, bp, 0, _stream(), C.byref(self._b)))
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b:
+            self.lib.kr_mlp_bank_destroy(self._b)
+            self._b = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Handle:
     """Owns one kr_handle (one device, one parameter set)."""
 
@@ -341,6 +424,9 @@ class Handle:
     def param_table(self, rows) -> ParamTable:
         return ParamTable(self, rows)
 
+    def mlp_bank(self, networks) -> MlpBank:
+        return MlpBank(self, networks)
+
     def init_straight(self, state, table=None):
         B = state.shape[0]
         if table is not None:  # rod b takes its length from row b
@@ -427,8 +513,20 @@ class Handle:
         check(self.lib.kr_set_option(self._h, name.encode(), int(value)))
 
     def simulate(self, ctl, states, G, ring=False, tip=None, status=None, scheme=KR_EULER, tol=0.0, maxit=0,
-                 use_nn=False, prev_init=None, table=None):
+                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None):
         B, T = ctl.shape[0], ctl.shape[1]
+        if bank is not None or net_of_rod is not None:  # rod b: row b of the table, network net_of_rod[b] of the bank
+            if bank is None or net_of_rod is None or table is None:
+                raise KrError("a bank call needs table=, bank= and net_of_rod= together")
+            if B != table.B:
+                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
+            idx = np.ascontiguousarray(np.asarray(net_of_rod).reshape(-1), dtype=np.int32)
+            if idx.size != B:
+                raise KrError(f"ctl holds {B} rods, net_of_rod {idx.size}")
+            check(self.lib.kr_simulate_batch_bank(self._h, table._t, bank._b, idx.ctypes.data_as(C.POINTER(C.c_int32)), T, scheme,
+                                                  _ptr(ctl), _ptr(states), int(bool(ring)), _ptr(G), _ptr(tip), float(tol),
+                                                  int(maxit), _ptr(status), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+            return
         if table is not None:  # rod b takes row b of the table instead of the handle's parameters
             if B != table.B:
                 raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
