@@ -90,6 +90,25 @@ __device__ __forceinline__ void lds_store_vec(T* dst, const T (&v)[NV]) {
   }
 }
 
+// A wavefront-uniform value in scalar registers OF ITS OWN.  The kernel argument arrives through one wide scalar load,
+// and the compiler keeps what it needs from it as sub-registers of that 16-register tuple: when scalar registers run
+// out the WHOLE tuple goes to the lanes of a spill register and every use of one member brings all sixteen back
+// (16 v_readlane for a pointer test).  Values that went through here are allocated - and, if need be, spilled - one by one.
+template <typename U>
+__device__ __forceinline__ U own_sgpr(U v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+// ... for a pointer into global memory (a kernel argument's pointer is known to be one; behind the asm it no longer
+// would be, and its accesses would turn into flat_load / flat_store)
+template <typename U>
+__device__ __forceinline__ U* own_sgpr_global(U* p) {
+  uintptr_t v = (uintptr_t)p;
+  asm volatile("" : "+s"(v));
+  return (U*)(__attribute__((address_space(1))) U*)v;
+}
+
 #ifdef KR_MS_STAMPS
 struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 0, chord = 0, rejects = 0, retries = 0, rebuilds = 0, t_sweep = 0, t_alg = 0, t_pred = 0, t_verdict = 0, t_cond = 0, t_fin = 0, t_upd = 0, t_v1 = 0, t_v2 = 0, t_c1 = 0, t_c2 = 0, t_copy = 0; };
 #endif
@@ -108,13 +127,27 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   if (rod >= A.B) return;  // whole wavefront; there is no workgroup barrier in this kernel
   const auto& Pc = rod_src_row<T>(Pa, rod);
   const size_t rod_elems = (size_t)N * KR_SLOTS;
-  const int64_t T_steps = A.T_steps;
+  // the members of the argument every step uses (the rest is read where a cold path needs it)
+  T* const a_states = own_sgpr_global(A.states);
+  const int64_t a_slot_elems = own_sgpr(A.slot_elems);
+  const int a_ring = own_sgpr(A.ring);
+  T* const a_tip = own_sgpr_global(A.tip);
+  int32_t* const a_status = own_sgpr_global(A.status);
+  const int a_residual_test = own_sgpr(A.residual_test), a_predictor = own_sgpr(A.predictor);
+  const T hc1 = own_sgpr(A.hc1), hc2 = own_sgpr(A.hc2);
+  const int T_steps = own_sgpr((int)A.T_steps);  // (step indices are 32-bit: the host refuses a call of 2^31 steps or more)
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * mso_lds_elems<T, HS>(N), N, true, false);
-  T* const Xs = L.Xs;
   T* const Es = L.Es;
   T* const XB = L.XB;
   T* const Tm = L.Tm;
-  T* const XsB = L.c12 + (size_t)N * 12;  // [P][19] unknowns of the step the verifying lanes re-integrate
+  // The unknowns of the step the forward-difference lanes work on (Xs) and of the step the verifying lanes re-integrate
+  // (XsB), [P][19] each, are two areas that change roles when a step is handed over: nothing is copied.  Which is which
+  // is an offset from one base (not a select between two pointers, DESIGN rule 4: the accesses stay LDS accesses).
+  T* const X0 = L.Xs;
+  const ptrdiff_t X_d = (L.c12 + (size_t)N * 12) - L.Xs;
+  int xsel = 0;
+  T* Xs = X0;
+  T* XsB = X0 + X_d;
   T* const EsB = Es + MSO_B0 * MS_YP;     // their end states: the Es slots of lanes 58..61
   const MsRole R = ms_role(lane, N);
   const int iv = R.iv, col = R.col;
@@ -126,7 +159,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   ms_cold_fill<T>(rod_src_mem<T>(Pa, rod), L.cold, lane);
   wave_sync();
 
-  auto state_ptr = [&](int64_t k) -> T* { return A.states + (A.ring ? k % 3 : k) * A.slot_elems + rod * rod_elems; };
+  auto slot_ptr = [&](int slot) -> T* { return a_states + (int64_t)slot * a_slot_elems + rod * rod_elems; };
+  auto state_ptr = [&](int k) -> T* { return slot_ptr(a_ring ? k % 3 : k); };  // (cold paths; the sweep's slot is rsA)
   // The BDF2 history (knode.py:74-75) is kept RAW: two tiles of leading slots (q w v u of every grid point), tile (t & 1)
   // for the state at time level t.  A lane forms the record it needs - hc1 * newest + hc2 * older, then av / au - itself,
   // right after the read: 30 instructions that every lane of the wavefront shares, where a precombined record cost the
@@ -135,9 +169,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   T* const lead0 = L.c12;                    // [N][12] states at even time levels
   const ptrdiff_t lead_d = L.hist - L.c12;  // states at odd time levels: the first 12 N elements of the record area
   // (offset arithmetic, not a select between two pointers: the compiler turned such selects into a table in scratch)
-  auto lead_of = [&](int64_t t) -> T* { return lead0 + (ptrdiff_t)(t & 1) * lead_d; };
+  auto lead_of = [&](int t) -> T* { return lead0 + (ptrdiff_t)(t & 1) * lead_d; };
   // both tiles of step t's history from the states in HBM
-  auto rebuild = [&](int64_t t) {
+  auto rebuild = [&](int t) {
     const T* cur = state_ptr(t);
     const T* prv = t > 0 ? state_ptr(t - 1) : (A.prev_init ? A.prev_init + rod * rod_elems : cur);
     T* const lc = lead_of(t);
@@ -151,12 +185,12 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     }
     wave_sync();
   };
-  const T* ctl = A.ctl + rod * T_steps * 4;
-  auto load_fc = [&](int64_t t) -> V3<T> {  // rhoA g + tendon force of step t (cosserat_ode.py:151,195)
+  const T* ctl = A.ctl + rod * A.T_steps * 4;
+  auto load_fc = [&](int t) -> V3<T> {  // rhoA g + tendon force of step t (cosserat_ode.py:151,195)
     V3<T> tf{T(0), T(0), T(0)};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const T tt = ctl[t * 4 + k];
+      const T tt = ctl[(size_t)t * 4 + k];
       tf.x += tt * L.cold[CD_TDIRS + k * 3 + 0];
       tf.y += tt * L.cold[CD_TDIRS + k * 3 + 1];
       tf.z += tt * L.cold[CD_TDIRS + k * 3 + 2];
@@ -169,15 +203,15 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   MsPred<T> Q;
   double* img = A.pred_io ? A.pred_io + (size_t)rod * MS_PRED_ROWS * WAVE : nullptr;
   if (img && A.pred_load) ms_pred_load<T>(Q, img, lane);
-  else ms_pred_init<T>(Q, lane, R, s0, sp0, A.prev_init != nullptr, A.predictor);
+  else ms_pred_init<T>(Q, lane, R, s0, sp0, A.prev_init != nullptr, a_predictor);
   V3<T> vlast, ulast;  // z of the last grid point is never touched by a sweep (cosserat_ode.py:198-201)
   {
     const T* cl = s0 + (size_t)(N - 1) * KR_SLOTS;
     vlast = {cl[SL_V], cl[SL_V + 1], cl[SL_V + 2]};
     ulast = {cl[SL_U], cl[SL_U + 1], cl[SL_U + 2]};
   }
-  const T tol = A.tol, tolA = A.tolA, fd_eps = A.fd_eps;
-  const int maxit = A.maxit;
+  const T tol = own_sgpr(A.tol), tolA = own_sgpr(A.tolA), fd_eps = own_sgpr(A.fd_eps);
+  const int maxit = own_sgpr(A.maxit);
   T kappa = Q.kappa;
   T Gguess = lane < 6 ? A.G[rod * 6 + lane] : T(0);
   MsStamps stamps;
@@ -191,7 +225,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   rebuild(0);
 
   // ---- state of the iteration -----------------------------------------------------------------------------------
-  int64_t tA = 0;        // step the forward-difference lanes work on (unknowns: Xs)
+  int tA = 0;            // step the forward-difference lanes work on (unknowns: Xs)
+  int rsA = 0;           // slot of `states` the state at time level tA goes to (ring: tA mod 3, advanced with tA, never divided)
   bool merged = false;   // the coming sweep also re-integrates step tA - 1 from XsB and streams it out
   int it = 0;            // forward-difference sweeps spent on step tA
   int order = Q.next_order;
@@ -206,16 +241,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   int itB = 0, orderB = 0;
   bool pred_skip = false;  // the predictor has already consumed step tA (a verifying sweep of it was rejected)
   bool reverify = false;   // the coming merged sweep verifies step tA - 1 for the second time (after a chord update)
-  int64_t resume_at = T_steps;
+  int resume_at = T_steps;
   T Xreg[MS_P - 1][2];
 #pragma unroll
   for (int g = 0; g < MS_P - 1; ++g) Xreg[g][0] = Xreg[g][1] = T(0);
-  const int kp = lane & 3;
-  const int r = 3 + (lane >> 2);
-  const bool plane = lane < 3 * (MS_P - 1);
-  const int pi = plane ? lane / 3 : 0;  // term i = 0 .. P-2
-  const int prow = plane ? lane - 3 * pi : 0;
-  const bool glane = lane >= WAVE - 6;  // six lanes own the base wrench in the update step
   // (tensions are requested one step before they are needed: a load from HBM takes longer than what lies between
   // the hand-over of a step and the sweep that follows)
   V3<T> fcA = load_fc(0), fcB = fcA;
@@ -243,7 +272,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 
   while (true) {
     const bool runA = tA < T_steps;  // (false only for the sweep that verifies the last step)
-    const int64_t tB = tA - 1;
+    const int tB = tA - 1;
     // ---- start state of this lane -------------------------------------------------------------------------------
     T yr[19];
     {
@@ -252,15 +281,19 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       for (int q = 0; q < 19; ++q) yr[q] = src[q];
     }
     const T hstep = (isA && col > 0) ? fd_eps * fmax(fabs(Xs[iv * MS_YP + (R.comp > 0 ? R.comp : 3)]), T(1)) : T(1);
+    // (comp is -1 in every lane that perturbs nothing, the verifying and the idle lanes included.  Compared afresh in
+    //  every sweep: as loop invariants the sixteen masks q == comp lived in 32 scalar registers, i.e. in a spill register)
+    int comp = R.comp;
+    asm volatile("" : "+v"(comp));
 #pragma unroll
-    for (int q = 3; q < 19; ++q) yr[q] += (isA && q == R.comp) ? hstep : T(0);
+    for (int q = 3; q < 19; ++q) yr[q] += q == comp ? hstep : T(0);
     RodState<T> y = rows_to_state(yr);
     const V3<T> fc = isB ? fcB : fcA;
     // the verifying lanes run MSO_LAG grid points ahead of the forward-difference lanes that consume their records
     const int lag = (isA && merged) ? MSO_LAG : 0;
     const bool act = isB ? merged : (isA && runA);
     const int trips = R.lmax + ((merged && runA) ? MSO_LAG : 0);
-    T* const out_rod = state_ptr(tB + 1);  // (used by the verifying lanes only)
+    T* const out_rod = slot_ptr(rsA);  // state tB + 1 (used by the verifying lanes only)
     // grid point this lane evaluates in trip k (clamped to its interval: lanes outside their range keep evaluating
     // their first / last point and do not advance)
     auto point_of = [&](int k) -> int {
@@ -276,7 +309,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     auto hist_form = [&](const T (&la)[12], const T (&lb)[12]) __attribute__((always_inline)) -> RodHist<T> {
       T raw[12];
 #pragma unroll
-      for (int c = 0; c < 12; ++c) raw[c] = A.hc1 * la[c] + A.hc2 * lb[c];
+      for (int c = 0; c < 12; ++c) raw[c] = hc1 * la[c] + hc2 * lb[c];
       RodHist<T> h;
       h.qh = {raw[0], raw[1], raw[2]};
       h.wh = {raw[3], raw[4], raw[5]};
@@ -310,7 +343,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     } else {
       // one trip of the merged sweep.  FULL: every active lane is inside its interval (no predicates, no clamped
       // indices) - true for the trips MSO_LAG .. sbase - 1, i.e. all but the first and last few.
-      const bool lean = A.ring && tB + 4 <= T_steps;  // (the last three states of a call stay complete)
+      const bool lean = a_ring && tB + 4 <= T_steps;  // (the last three states of a call stay complete)
       T* const lead_w = lead_of(tB + 1);               // the tile the verifying lanes write: state tB + 1 over state tB - 1
       auto trip = [&](int k, auto full_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
@@ -381,6 +414,18 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     if (merged) st.merged += 1;
 #endif
 
+    // Lane roles of the algebra between two sweeps.  They are functions of the lane index, and as loop invariants the
+    // compiler kept each of them - a 64-bit mask per predicate - in scalar registers across the sweep, i.e. in the lanes
+    // of a spill register, two v_readlane per use.  Formed from a lane index the compiler cannot see through, they
+    // are recomputed here, once per sweep, for one or two instructions each.
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int kp = ln & 3;
+    const int r = 3 + (ln >> 2);
+    const bool plane = ln < 3 * (MS_P - 1);
+    const int pi = plane ? ln / 3 : 0;  // term i = 0 .. P-2
+    const int prow = plane ? ln - 3 * pi : 0;
+    const bool glane = ln >= WAVE - 6;  // six lanes own the base wrench in the update step
     T er[19];
     state_to_rows(y, er);
     T d[6];
@@ -434,7 +479,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         nf = update_ratio(U.updP, U.xsP);
       }
       if (glane) {
-        const int k = lane - (WAVE - 6);
+        const int k = ln - (WAVE - 6);
         U.xsG = X[0 * MS_YP + 7 + k];
         U.updG = k == 0 ? d[0] : k == 1 ? d[1] : k == 2 ? d[2] : k == 3 ? d[3] : k == 4 ? d[4] : d[5];
         nf = fmaxf(nf, update_ratio(U.updG, U.xsG));
@@ -451,7 +496,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     };
     auto apply = [&](T* X) {
       if (plane) X[(pi + 1) * MS_YP + prow] = U.xsP + U.updP;
-      if (glane) X[0 * MS_YP + 7 + (lane - (WAVE - 6))] = U.xsG + U.updG;
+      if (glane) X[0 * MS_YP + 7 + (ln - (WAVE - 6))] = U.xsG + U.updG;
 #pragma unroll
       for (int g = 1; g < MS_P; ++g)
         if (((g - 1) & 3) == kp) X[g * MS_YP + r] = U.xsY[g - 1] + updY[g - 1];
@@ -472,8 +517,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #pragma unroll
           for (int c = 0; c < 12; ++c) lead[c] = rec[c];
           lds_store_vec<T, 12>(lead_of(tB + 1) + (size_t)(N - 1) * 12, lead);
-          if (A.tip) {
-            T* tp = A.tip + (rod * T_steps + tB) * 3;
+          if (a_tip) {
+            T* tp = a_tip + (rod * T_steps + tB) * 3;
             tp[0] = y.p.x; tp[1] = y.p.y; tp[2] = y.p.z;
           }
         }
@@ -485,12 +530,12 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
       // residual of the sweep: interface jumps E_g - Y_{g+1} and the tip condition, one component per lane
       float rn = 0.f;
-      if (lane < 3 * MS_YP) {
-        const int g = lane / MS_YP, q = lane - MS_YP * g;
+      if (ln < 3 * MS_YP) {
+        const int g = ln / MS_YP, q = ln - MS_YP * g;
         const T x = XsB[(g + 1) * MS_YP + q];
         rn = update_ratio(EsB[g * MS_YP + q] - x, x);
-      } else if (lane < 3 * MS_YP + 6) {
-        const int k = lane - 3 * MS_YP;
+      } else if (ln < 3 * MS_YP + 6) {
+        const int k = ln - 3 * MS_YP;
         const T e = EsB[(MS_P - 1) * MS_YP + 7 + k];
         rn = update_ratio(L.cold[CD_FTIP + k] - e, e);
       }
@@ -500,7 +545,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
       const float est = ampB * rn;
       // residual test (kr_ms_impl.hpp: audited factor 256 on the measured update / residual ratio)
-      bool accepted = A.residual_test != 0 && ampB > 0.f && T(256) * (T)est <= tol;
+      bool accepted = a_residual_test != 0 && ampB > 0.f && T(256) * (T)est <= tol;
       float dnv = est;
 #ifdef KR_MS_STAMPS
       if (accepted) st.quick += 1;
@@ -569,7 +614,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       if (accepted) {
         {  // leading slots of the accepted state: tile -> HBM, every grid point in one pass of the wavefront
           const T* const lt = lead_of(tB + 1);
-          for (int j = lane; j < N; j += WAVE) {
+          for (int j = ln; j < N; j += WAVE) {
             T lv[12];
             lds_load_vec<T, 12>(lt + (size_t)j * 12, lv);
             store_vec<T, 12>(out_rod + (size_t)j * KR_SLOTS, lv);
@@ -580,8 +625,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           const T kq = fmax((T)dnv, floor_dn) * fast_rcp(dnB * dnB);
           kappa = fmin(fmax(kq, T(1e-4)), T(1));
         }
-        if (lane == 0 && A.status) A.status[rod * T_steps + tB] = KR_ST_CONVERGED;
-        if (lane < 6) Gguess = XsB[0 * MS_YP + 7 + lane];
+        if (ln == 0 && a_status) a_status[rod * T_steps + tB] = KR_ST_CONVERGED;
+        if (ln < 6) Gguess = XsB[0 * MS_YP + 7 + ln];
         pred_skip = false;
         reverify = false;
         merged = false;
@@ -616,8 +661,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           continue;
         }
         reverify = false;
-        for (int e = lane; e < MS_NE; e += WAVE) Xs[e] = XsB[e];
+        for (int e = ln; e < MS_NE; e += WAVE) Xs[e] = XsB[e];
         tA = tB;
+        rsA = a_ring ? (rsA == 0 ? 2 : rsA - 1) : rsA - 1;
         fcN = fcA;
         fcA = fcB;
         order = orderB;
@@ -653,10 +699,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       const int l0own = iv == 0 ? 0 : 7 + 17 * (iv - 1);
       if (isA && col == 0) {
 #pragma unroll
-        for (int q = 0; q < 19; ++q) Es[lane * MS_YP + q] = er[q];
+        for (int q = 0; q < 19; ++q) Es[ln * MS_YP + q] = er[q];
       }
       wave_sync_lds();
-      res_full = ms_residual_norm<T>(Es, Xs, L.cold, lane);
+      res_full = ms_residual_norm<T>(Es, Xs, L.cold, ln);
       if (isA && col > 0) {
         const T ih = fast_rcp(hstep);
         T e0[19];  // all loads first: the compiler cannot tell that they never alias the stores below
@@ -664,7 +710,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         for (int q = 0; q < 19; ++q) e0[q] = Es[l0own * MS_YP + q];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int q = 0; q < 19; ++q) Es[lane * MS_YP + q] = (er[q] - e0[q]) * ih;
+        for (int q = 0; q < 19; ++q) Es[ln * MS_YP + q] = (er[q] - e0[q]) * ih;
       }
       wave_sync_lds();
     }
@@ -727,19 +773,23 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
     {
       T a6[6][7];
+      // rows [rhs | T] from Tm (which nothing overwrites before finish()): once for the solve, once more if a row moves
+      auto fill6 = [&](T (&m)[6][7]) {
 #pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        T row[8];
-        load_hist_vec<T, 8>(Tm + i * 8, row);
+        for (int i = 0; i < 6; ++i) {
+          T row[8];
+          load_hist_vec<T, 8>(Tm + i * 8, row);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) a6[i][k] = row[1 + k];
-        a6[i][6] = lane < 6 ? (lane == i ? T(1) : T(0)) : row[0];  // lanes 0..5: unit vectors -> columns of T^-1
-      }
+          for (int k = 0; k < 6; ++k) m[i][k] = row[1 + k];
+          m[i][6] = ln < 6 ? (ln == i ? T(1) : T(0)) : row[0];  // lanes 0..5: unit vectors -> columns of T^-1
+        }
+      };
+      fill6(a6);
       T x6[6];
-      solve6(a6, x6);
-      if (lane < 6) {
+      solve6_uniform(a6, x6, fill6);
+      if (ln < 6) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) L.Ti[i * 6 + lane] = x6[i];
+        for (int i = 0; i < 6; ++i) L.Ti[i * 6 + ln] = x6[i];
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) d[i] = lane_bcast<6>(x6[i]);
@@ -791,9 +841,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       if (order > 0 && !retried) {
         retried = true;
         order = 0;
-        ms_pred_guess<T>(Q, 0, lane, L.cold, Xs);
+        ms_pred_guess<T>(Q, 0, ln, L.cold, Xs);
         wave_sync_lds();
-        if (lane < 6) Xs[0 * MS_YP + 7 + lane] = Gguess;
+        if (ln < 6) Xs[0 * MS_YP + 7 + ln] = Gguess;
         wave_sync_lds();
         it = 0; dn_prev = T(-1); have_fac = false; amp = -1.f; below = false;
 #ifdef KR_MS_STAMPS
@@ -806,17 +856,19 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     }
     if (next_final && dn <= T(1e-2)) {
       // hand step tA to the verifying lanes and move the forward-difference lanes on to step tA + 1
-      for (int e = lane; e < MS_NE; e += WAVE) XsB[e] = Xs[e];
-      wave_sync_lds();
+      xsel ^= 1;
+      Xs = X0 + xsel * X_d;
+      XsB = X0 + (1 - xsel) * X_d;
 #ifdef KR_MS_STAMPS
       { unsigned long long t_; KR_STAMP(t_); st.t_copy += t_ - tq; }
 #endif
       dnB = dn; ampB = amp; belowB = below; itB = it; orderB = order;
-      if (!pred_skip) ms_pred_update<T>(Q, order, KR_ST_CONVERGED, A.predictor, lane, XsB, stamps);
+      if (!pred_skip) ms_pred_update<T>(Q, order, KR_ST_CONVERGED, a_predictor, lane, XsB, stamps);
 #ifdef KR_MS_STAMPS
       { unsigned long long t_; KR_STAMP(t_); st.t_upd += t_ - tq; }
 #endif
       tA += 1;
+      rsA = a_ring ? (rsA == 2 ? 0 : rsA + 1) : rsA + 1;
       fcB = fcA;
       if (tA < T_steps) {
         fcA = fcN;
@@ -858,6 +910,16 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
 }
 
+// The kernel counts steps in 32 bits (SimArgs::resume always did); offsets into `states`, `ctl`, `tip` and `status` are
+// formed in 64 bits.
+inline int mso_check_steps(int64_t T_steps) {
+  if (T_steps > (int64_t)0x7fffffff) {
+    set_error("T_steps = " + std::to_string(T_steps) + ": the overlapped persistent kernel counts steps in 32 bits (T_steps < 2^31)");
+    return KR_E_ARG;
+  }
+  return KR_OK;
+}
+
 // Host-side one-time work of the first launch, done ahead of time (kr_simulate_prepare): resolves the kernel in the
 // code object and sets its dynamic LDS limit.  Returns 1 when the kernel does not serve the handle's problem.
 template <typename T>
@@ -887,6 +949,7 @@ int launch_mso_sim(kr_handle* h, const SimArgs<T>& a, hipStream_t s) {
   if (!P.diag || P.N - 1 < 2 * MS_P) return 1;
   const size_t smem = sizeof(T) * mso_lds_elems<T, HS>(P.N) * MS_WPB;
   if (smem > (size_t)h->lds_limit) return 1;
+  if (int rc_steps_ = mso_check_steps(a.T_steps)) return rc_steps_;
   const dim3 grid((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), block(WAVE * MS_WPB);
   if constexpr (sizeof(T) == 4) {
     // fp32, more rods than SIMDs, and two workgroups fit the LDS of a CU: two wavefronts per SIMD

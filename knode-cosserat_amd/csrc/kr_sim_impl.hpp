@@ -230,6 +230,44 @@ __device__ __forceinline__ void solve6(T (&a)[6][7], T (&x)[6]) {
   }
 }
 
+// solve6 for callers whose MATRIX part a[.][0..5] is the same in every lane (the right-hand side a[.][6] may differ) and
+// who can fill `a` again (`reload(a)`): the same arithmetic without a row exchange on the straight path.  solve6's
+// fifteen pivot tests are fifteen divergent branches, each a block of its own (compare, exec mask, branch) that ends
+// in copies merging its values with those of an exchange that hardly ever runs.  Here the elimination runs as if no
+// row had to move and ORs the fifteen tests over rows, columns and lanes into one scalar condition.  Up to the first
+// test that fires both routines compute the same values (a column's sequential tests compare with an a[k][k] that
+// changes only after one of them has fired), so the condition is false exactly when solve6 would not have exchanged
+// anything, and then x is solve6's x.  Otherwise the system is filled again and goes through solve6 itself, out of
+// line.  (Taken over all lanes the condition is right even for a caller whose lanes differ.)
+template <typename T, typename F>
+__device__ __forceinline__ void solve6_uniform(T (&a)[6][7], T (&x)[6], F&& reload) {
+  T inv[6];
+  bool moves = false;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int i = k + 1; i < 6; ++i) moves = moves | (fabs(a[i][k]) > fabs(a[k][k]));  // (|: no short circuit)
+    inv[k] = fast_rcp(a[k][k]);
+#pragma unroll
+    for (int i = k + 1; i < 6; ++i) {
+      const T f = a[i][k] * inv[k];
+#pragma unroll
+      for (int c = k + 1; c < 7; ++c) a[i][c] = fma(-f, a[k][c], a[i][c]);
+    }
+  }
+#pragma unroll
+  for (int k = 5; k >= 0; --k) {
+    T s = a[k][6];
+#pragma unroll
+    for (int c = k + 1; c < 6; ++c) s = fma(-a[k][c], x[c], s);
+    x[k] = s * inv[k];
+  }
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(moves) != 0, 0)) {
+    reload(a);
+    solve6(a, x);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // MLP correction inside a sweep (cosserat_ode.py:169-184)
 // ---------------------------------------------------------------------------

@@ -87,6 +87,7 @@ int launch_tab_sim(kr_handle* h, const kr_param_table* t, int scheme, int use_nn
     // two launches, as launch_sim_persistent: the overlapped kernel, then the take-over launch for what it left behind
     if (int rc = ensure_resume(h, a.B)) return rc;
     a2.resume = static_cast<int32_t*>(h->resume_buf);
+    if (int rc = mso_check_steps(a.T_steps)) return rc;
     auto ko = mso_sim_kernel<T, true, HS, 1, RodTable<T>>;
     if (int rc = dyn_lds(reinterpret_cast<const void*>(ko), smem_o)) return rc;
     hipLaunchKernelGGL(ko, grid, block, smem_o, s, tab, a2);
