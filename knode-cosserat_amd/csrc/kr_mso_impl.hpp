@@ -42,6 +42,10 @@ constexpr int MSO_B0 = 7 + 17 * (MS_P - 1);  // 58: first of the four lanes that
 // lets the next trip's tile reads go out under this trip's arithmetic - measured 40.8 M against 42.1 M rod-steps/s (one more
 // trip per sweep, and the pinned hand-over keeps the compiler from pairing trips)
 constexpr int MSO_LAG = KR_MSO_LAG;
+// -DKR_MSO_PROBE_EARLY_READS (a compile-time probe, TIMING ONLY - the results are wrong): a full trip reads BOTH tiles of
+// the next grid point in front of the verifying lanes' store block, so no read waits for a store of its own trip.  The
+// merged-sweep ticks of the stamped build of it (make dbg DBGFLAGS="-DKR_MS_STAMPS -DKR_MSO_PROBE_EARLY_READS") are the
+// most that hiding the tile round trip can give (LABBOOK, "merged trip").
 static_assert(MSO_B0 + MS_P <= WAVE, "the verifying lanes must fit beside the forward-difference lanes");
 
 template <typename T, int HS>
@@ -306,10 +310,16 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     // producing).  The tile addresses differ per lane; the arithmetic is the same for all.
     const T* const lead_n = lead_of(isB ? tB : tA);      // this lane's newest state
     const T* const lead_o = lead_of(isB ? tB + 1 : tB);  // ... and the one before it (same parity as two levels on)
-    auto hist_form = [&](const T (&la)[12], const T (&lb)[12]) __attribute__((always_inline)) -> RodHist<T> {
+    // (the rounding of a record is written out - one product, one fused multiply-add - so that it does not depend on
+    //  where the compiler's contraction finds the two halves: the merged trip forms them a store block apart)
+    auto hist_older = [&](const T (&lb)[12], T (&pb)[12]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int c = 0; c < 12; ++c) pb[c] = hc2 * lb[c];
+    };
+    auto hist_newest = [&](const T (&la)[12], const T (&pb)[12]) __attribute__((always_inline)) -> RodHist<T> {
       T raw[12];
 #pragma unroll
-      for (int c = 0; c < 12; ++c) raw[c] = hc1 * la[c] + hc2 * lb[c];
+      for (int c = 0; c < 12; ++c) raw[c] = fma(hc1, la[c], pb[c]);
       RodHist<T> h;
       h.qh = {raw[0], raw[1], raw[2]};
       h.wh = {raw[3], raw[4], raw[5]};
@@ -318,6 +328,11 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       h.av = {hk_b[0] * raw[6] + hk_a[0], hk_b[1] * raw[7] + hk_a[1], hk_b[2] * raw[8] + hk_a[2]};  // (Kse + c0 Bse)^-1 (Kse v* - Bse v_h)
       h.au = {hk_c[0] * raw[9], hk_c[1] * raw[10], hk_c[2] * raw[11]};                                       // -(Kbt + c0 Bbt)^-1 Bbt u_h
       return h;
+    };
+    auto hist_form = [&](const T (&la)[12], const T (&lb)[12]) __attribute__((always_inline)) -> RodHist<T> {
+      T pb[12];
+      hist_older(lb, pb);
+      return hist_newest(la, pb);
     };
     auto hist_at = [&](int j) __attribute__((always_inline)) -> RodHist<T> {
       T la[12], lb[12];
@@ -343,19 +358,39 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     } else {
       // one trip of the merged sweep.  FULL: every active lane is inside its interval (no predicates, no clamped
       // indices) - true for the trips MSO_LAG .. sbase - 1, i.e. all but the first and last few.
+      //
+      // What a lone wavefront must not do is wait for the tile round trip (the verifying lanes' six stores, then the reads
+      // of the next grid point's leading slots) with nothing else to issue.  The LDS returns in order, so the first use of
+      // ANY read issued behind the stores waits for the stores too.  Hence, per trip:
+      //   * the OLDER tile of the next grid point is read at the head of the trip and its half of the record (hc2 * older)
+      //     is formed IN FRONT of the store block: no lane's older tile changes at that grid point before the next trip
+      //     (static during the sweep for the forward-difference lanes; a verifying lane replaces slot j + 1 in trip k + 1)
+      //   * the NEWEST tile is read right behind the stores and consumed behind the rest of this trip's arithmetic (the
+      //     bulk of ode_eval and the Euler update need only the current record)
+      // In a predicated trip past a lane's interval the clamped older read is that of the slot the lane has just written,
+      // taken before the store: such a lane's record feeds an evaluation that is multiplied by dsl = 0.
       const bool lean = a_ring && tB + 4 <= T_steps;  // (the last three states of a call stay complete)
       T* const lead_w = lead_of(tB + 1);               // the tile the verifying lanes write: state tB + 1 over state tB - 1
-      auto trip = [&](int k, auto full_tag) __attribute__((always_inline)) {
+      auto trip = [&](int k, auto full_tag, auto lean_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
+        constexpr bool LEAN = decltype(lean_tag)::value;  // (FULL trips: the loop exists once per value; others test `lean`)
         const int kk = k - lag;
         const bool live = FULL ? act : (act && kk >= 0 && kk < len_l);
         const int j = FULL ? s_l + kk : point_of(k);
-        // MSO_LAG >= 2: what the next trip reads was written a trip ago - requested now, under the arithmetic of this one
-        T la[12], lb[12];
+        const int eo = j * 12;                                       // elements in front of grid point j in a tile
+        const int en = FULL ? eo + 12 : point_of(k + 1) * 12;  // ... of the grid point of the next trip
+        T la[12], lb[12], pb[12];
         if constexpr (MSO_LAG >= 2) {
-          const int jn = FULL ? j + 1 : point_of(k + 1);
-          lds_load_vec<T, 12>(lead_n + (size_t)jn * 12, la);
-          lds_load_vec<T, 12>(lead_o + (size_t)jn * 12, lb);
+          // what the next trip reads was written a trip ago - requested now, under the arithmetic of this one
+          lds_load_vec<T, 12>(lead_n + en, la);
+          lds_load_vec<T, 12>(lead_o + en, lb);
+        } else {
+          lds_load_vec<T, 12>(lead_o + en, lb);
+#ifdef KR_MSO_PROBE_EARLY_READS
+          // TIMING PROBE, results are wrong: the newest tile too is read in front of the store block, so the
+          // forward-difference lanes see leading slots that are two time levels old
+          if constexpr (FULL) lds_load_vec<T, 12>(lead_n + en, la);
+#endif
         }
         RodState<T> k1;
         V3<T> v, u;
@@ -367,6 +402,11 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           asm volatile("" : "+v"(hst.qh.x), "+v"(hst.qh.y), "+v"(hst.qh.z), "+v"(hst.wh.x), "+v"(hst.wh.y), "+v"(hst.wh.z));
           asm volatile("" : "+v"(hst.vh.x), "+v"(hst.vh.y), "+v"(hst.vh.z), "+v"(hst.uh.x), "+v"(hst.uh.y), "+v"(hst.uh.z));
           asm volatile("" : "+v"(hst.av.x), "+v"(hst.av.y), "+v"(hst.av.z), "+v"(hst.au.x), "+v"(hst.au.y), "+v"(hst.au.z));
+        } else {
+          // (pinned: the products - and the wait for the older tile - stay in front of the block)
+          hist_older(lb, pb);
+          asm volatile("" : "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]), "+v"(pb[4]), "+v"(pb[5]), "+v"(pb[6]), "+v"(pb[7]),
+                            "+v"(pb[8]), "+v"(pb[9]), "+v"(pb[10]), "+v"(pb[11]));
         }
         if (isB && live) {
           // the accepted-to-be state of step tB at grid point j: to HBM; its leading slots replace those of the state
@@ -381,32 +421,63 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           // slots of every record plus the full records at the interval starts and at the last grid point (predictor,
           // z of the last point).  The leading slots are what this sweep leaves in its tile: once the step is accepted
           // the whole tile goes out in one pass of the wavefront (below, 2 x 6 stores from all lanes instead of 6 stores
-          // from four lanes in every trip); interior records of interior steps store nothing here, all others only
-          // their remaining sixteen slots.
+          // from four lanes in every trip); interior records of interior steps store nothing here (an interval start is
+          // the grid point of trip 0, the last grid point is the verdict's: the trailing predicated trips are interior
+          // too), all others only their remaining sixteen slots or, in a predicated trip, the whole record.
           if constexpr (FULL) {
-            if (!lean) {  // the rest of the record (p h n m); its leading slots follow with the tile
+            if constexpr (!LEAN) {  // the rest of the record (p h n m); its leading slots follow with the tile
               T rest[KR_SLOTS - 12];
 #pragma unroll
               for (int c = 0; c < KR_SLOTS - 12; ++c) rest[c] = rec[12 + c];
               store_vec<T, KR_SLOTS - 12>(out_rod + (size_t)j * KR_SLOTS + 12, rest);
             }
           } else {
-            store_record(out_rod + (size_t)j * KR_SLOTS, rec);
+            if (!(lean && k >= R.sbase)) store_record(out_rod + (size_t)j * KR_SLOTS, rec);  // (verifying lanes: kk = k)
           }
-          lds_store_vec<T, 12>(lead_w + (size_t)j * 12, lead);
+          lds_store_vec<T, 12>(lead_w + eo, lead);
         }
         // history record of the next trip.  A forward-difference lane reads the leading slots a verifying lane wrote
         // MSO_LAG - 1 trips ago (for MSO_LAG = 1: above, in this trip); a verifying lane reads slots it has not
         // replaced yet.  (FULL: j + 1 <= N - 1 is a valid grid point even where it lies past the lane's interval.)
-        if constexpr (MSO_LAG < 2) hst = hist_at(FULL ? j + 1 : point_of(k + 1));
+        if constexpr (MSO_LAG < 2) {
+#ifdef KR_MSO_PROBE_EARLY_READS
+          if constexpr (!FULL)
+#endif
+          lds_load_vec<T, 12>(lead_n + en, la);
+          // (the reads stay right behind the block: left alone, the scheduler sinks them to ~20 instructions in front of
+          //  their first use.  Two wavefronts per SIMD hide that themselves, and the barrier costs them scratch.)
+          if constexpr (OCC == 1) __builtin_amdgcn_sched_barrier(0);
+        }
         const T dsl = live ? Pc.ds : T(0);  // (a lane outside its range evaluates finite data and adds nothing)
         y = state_axpy(y, dsl, k1);
+        if constexpr (MSO_LAG < 2) {
+          // (pinned behind the Euler update: the first use of the newest tile, i.e. the wait for the stores in front of
+          //  its reads, comes when everything that needs only the current record has been issued)
+          //  (through the products, which are single registers: a value pinned inside a 16-byte read costs a copy)
+          asm volatile("" : "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]), "+v"(pb[4]), "+v"(pb[5]), "+v"(pb[6]), "+v"(pb[7]),
+                            "+v"(pb[8]), "+v"(pb[9]), "+v"(pb[10]), "+v"(pb[11]), "+v"(y.p.z), "+v"(y.h3), "+v"(y.n.z), "+v"(y.m.z),
+                            "+v"(y.q.z), "+v"(y.w.z));
+          hst = hist_newest(la, pb);
+        }
       };
       int k = 0;
-      for (; k < MSO_LAG && k < trips; ++k) trip(k, std::false_type{});
-#pragma unroll 2
-      for (; k < R.sbase; ++k) trip(k, std::true_type{});
-      for (; k < trips; ++k) trip(k, std::false_type{});
+      for (; k < MSO_LAG && k < trips; ++k) trip(k, std::false_type{}, std::false_type{});
+      // (the loop of full trips once for ring-lean steps and once for complete records: no test of `lean` inside a trip)
+      // (two trips per pass written out: the pins are convergent operations, and a loop that holds one is not unrolled
+      //  with a remainder by the compiler)
+      auto full_trips = [&](auto lean_tag) __attribute__((always_inline)) {
+        for (; k + 1 < R.sbase; k += 2) {
+          trip(k, std::true_type{}, lean_tag);
+          trip(k + 1, std::true_type{}, lean_tag);
+        }
+        if (k < R.sbase) {
+          trip(k, std::true_type{}, lean_tag);
+          ++k;
+        }
+      };
+      if (lean) full_trips(std::true_type{});
+      else full_trips(std::false_type{});
+      for (; k < trips; ++k) trip(k, std::false_type{}, std::false_type{});
     }
 #ifdef KR_MS_STAMPS
     KR_STAMP_ADD(st.t_sweep, tq);
@@ -505,10 +576,18 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     // =============================================================================================================
     // verdict on the step under verification
     // =============================================================================================================
+    // End states through Es.  EsB is the Es area of lanes 58..61, so the verifying lanes' end states and the base end
+    // states of the forward-difference sweep are ONE round of 19 stores under the union of both masks: in a merged sweep
+    // it is issued here, and the Newton block below stores (and fences) only behind a plain sweep.  (The chord update
+    // reads the forward-difference COLUMNS of the last condensation from Es and the verifying lanes' slots, not the base
+    // slots 0, 7, 24, 41; after a rejection the next sweep writes them again before anything reads them.)
+    const bool es_stored = merged;
     if (merged) {
-      if (isB) {
+      if (isB || (isA && col == 0)) {
 #pragma unroll
-        for (int q = 0; q < 19; ++q) EsB[ib * MS_YP + q] = er[q];
+        for (int q = 0; q < 19; ++q) Es[ln * MS_YP + q] = er[q];
+      }
+      if (isB) {
         if (ib == MS_P - 1) {  // the last grid point: y from the sweep, z untouched
           T rec[KR_SLOTS];
           record_from(y, vlast, ulast, rec);
@@ -697,11 +776,13 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     float res_full;
     {
       const int l0own = iv == 0 ? 0 : 7 + 17 * (iv - 1);
-      if (isA && col == 0) {
+      if (!es_stored) {  // (a merged sweep's end states are in Es since the verdict)
+        if (isA && col == 0) {
 #pragma unroll
-        for (int q = 0; q < 19; ++q) Es[ln * MS_YP + q] = er[q];
+          for (int q = 0; q < 19; ++q) Es[ln * MS_YP + q] = er[q];
+        }
+        wave_sync_lds();
       }
-      wave_sync_lds();
       res_full = ms_residual_norm<T>(Es, Xs, L.cold, ln);
       if (isA && col > 0) {
         const T ih = fast_rcp(hstep);
