@@ -511,6 +511,49 @@ size_t kr_estimate_ws_bytes(int64_t T, int N);
 int kr_estimate_state(kr_handle* h, int64_t T, const double* data, const double* tensions, double* est, void* ws,
                       void* stream);
 
+/* ---- evaluation metrics of a batch ------------------------------------- */
+/* What the reference's drivers compute on the host from every simulated trajectory, one rod at a time
+ * (physics_multitrain.py:213-222, physics_train.py:136-167), as device kernels that read the packed states where a
+ * simulate call left them: two doubles per rod come back instead of a trajectory.
+ * All metric arithmetic is fp64 whatever `dtype`, which is only the element type of the inputs; outputs are double.
+ * Both calls use none of the handle's scratch; kr_pose_mse_batch takes N from the handle, kr_dtw_batch reads no
+ * parameter at all.
+ * FastDTW (what the reference calls) is NOT built on the device: it needs the warp path traced back on every level of
+ * its pyramid, its parity with the third-party package is unpinned in this project anyway (krod_eval.py), and the
+ * exact distance below is the quantity it approximates (and a lower bound of it). */
+#define KR_DTW_MAX_LEN 4096
+
+/* Exact dynamic-time-warping distance, L1 point distance, between 3-vectors - what
+ * krod_eval.dtw_distance(a, b) computes (the metric of physics_multitrain.py:213 / physics_train.py:159
+ * without FastDTW's coarse-path restriction).  Sample i of rod b of sequence a is the 3 consecutive elements at
+ * a + b*a_rod_stride + i*a_step_stride (strides in ELEMENTS, >= 0; rod stride 0 = one sequence shared by all rods).
+ * This reads simulate's tip[B][T][3] (rod T*3, step 3) and equally one grid point of a full state history
+ * states[T+1][B][N][KR_SLOTS] (pointer to slot 12 of that point in states[0]; rod N*KR_SLOTS, step B*N*KR_SLOTS).
+ * dist[B].
+ * The recurrence is cost = (|dx| + |dy|) + |dz|, D = cost + min(min(up, left), diag) in exactly this order: the
+ * result is bit-identical to krod_eval.dtw_distance on the same (upcast) samples.  A NaN sample is not propagated the
+ * way NumPy's minimum does.  Nothing but the Ta, Tb samples of each rod is read.
+ * 1 <= Ta, Tb <= KR_DTW_MAX_LEN; longer: KR_E_UNSUPPORTED, nothing is launched and dist is left untouched.
+ * One wavefront per rod; no scratch in global memory. */
+int kr_dtw_batch(kr_handle* h, int64_t B,
+                 const void* a, int64_t Ta, int64_t a_rod_stride, int64_t a_step_stride,
+                 const void* b, int64_t Tb, int64_t b_rod_stride, int64_t b_step_stride,
+                 double* dist, int dtype, void* stream);
+
+/* physics_multitrain.py:215-222 per rod: mse[b] = 1000 * mean over the first T states and the handle's N grid points
+ * of the 3 squared position errors and the 3 squared zyx-Euler-angle errors (6*T*N terms).
+ * states[T][B][N][KR_SLOTS] (the first T slots of a full history), ref_states[T][ref_B][N][KR_SLOTS], ref_B = 1 or B;
+ * both 16-byte aligned.  parts[B][2] (nullable): the two sums (position, Euler) before the division.
+ * The angles are SciPy's Rotation.from_quat(q, scalar_first=True).as_euler('zyx') (extrinsic) in closed form: with
+ * (w, x, y, z) = q / |q|
+ *     a = atan2(2(wz - xy), 1 - 2(y^2 + z^2)),  b = asin(clamp(2(xz + wy), -1, 1)),  c = atan2(2(wx - yz), 1 - 2(x^2 + y^2))
+ * (2.7e-15 from SciPy 1.15.3 on 20 000 random non-unit quaternions with |b| < 1.4) - not
+ * Utils.transformations.quaternion_to_euler and not the fp32 short forms of the training loss.  There is no
+ * gimbal-lock branch: within ~1e-6 of b = +-pi/2 SciPy zeroes one angle and warns, the closed form does not.
+ * The sums are formed in a fixed order without atomics: a call is reproducible bit for bit. */
+int kr_pose_mse_batch(kr_handle* h, int64_t B, int64_t T, const void* states, const void* ref_states,
+                      int64_t ref_B, double* mse, double* parts, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

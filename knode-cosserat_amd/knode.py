@@ -159,8 +159,38 @@ def _robots_networks(robot, robots):
     return networks, net_of_rod
 
 
+def _score_reference(robot, score, B, T, tip_only):
+    """``(reference[R, Tr, >=7, N], point)`` of ``simulate_batch(..., score=...)``, R = 1 or B; host-side validation only
+    (no device call)."""
+    if tip_only:
+        raise kn.KrError("simulate_batch: score needs the state history (tip_only=True keeps three states)")
+    if not isinstance(score, dict) or "reference" not in score:
+        raise kn.KrError('simulate_batch: score must be {"reference": array[, "point": grid point]}')
+    ref = np.asarray(score["reference"], dtype=np.float64)
+    N = int(robot.N)
+    shared = ref.ndim == 3
+    if ref.ndim not in (3, 4):
+        raise kn.KrError(f"simulate_batch: score reference must be [Tr, >=7, N] or [B, Tr, >=7, N]; got shape {ref.shape}")
+    if shared:
+        ref = ref[None]
+    R, Tr, rows, n = ref.shape
+    if n != N:
+        raise kn.KrError(f"simulate_batch: score reference has {n} grid points, the robot {N}")
+    if rows < 7:
+        raise kn.KrError(f"simulate_batch: score reference has {rows} rows, positions and quaternions need 7")
+    if not shared and R != B:
+        raise kn.KrError(f"simulate_batch: score reference holds {R} rods, ctl {B}")
+    if Tr < 1 or Tr > T + 1:
+        raise kn.KrError(f"simulate_batch: score reference has {Tr} states, the run 1 .. {T + 1}")
+    point = score.get("point", None)
+    point = N - 1 if point is None else int(point)
+    if not -N <= point < N:
+        raise kn.KrError(f"simulate_batch: score point {point} outside the rod's {N} grid points")
+    return ref, point % N
+
+
 def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
-                   robots=None, per_robot_nn=False):
+                   robots=None, per_robot_nn=False, score=None):
     """B rods, each with its own tension history.
 
     robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
@@ -177,7 +207,19 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
       ``tip``    float[B, T, 3]  tip position after each solved step,
       ``status`` int32[B, T]     0 converged / 1 iteration cap / 2 non-finite,
       ``traj``   float[B, T+1, 25, N] (reference row order, entry 0 = initial state) unless ``tip_only``.
-    All T steps are solved (no off-by-one drop here)."""
+    All T steps are solved (no off-by-one drop here).
+
+    score: ``{"reference": ref, "point": p}`` scores the run on the device before anything is copied (what
+    physics_multitrain.py:213-222 does on the host, one rod at a time): ref is [Tr, >=7, N] (one reference for all rods)
+    or [B, Tr, >=7, N], Tr <= T + 1; states 0 .. Tr-1 are compared.  The result gains ``dtw`` float64[B], the exact DTW
+    distance (L1) of the path of grid point p (default N - 1, the tip - the reference's literal 9 at its N = 10) to the
+    reference's, and ``mse`` float64[B], the position + zyx-Euler MSE x 1000 (``krod_eval.dtw_distance`` /
+    ``pos_euler_mse``).  With ``return_states=False`` no trajectory leaves the device."""
+    if score is not None:  # (validated on the host before anything touches the device)
+        ctl_shape = np.asarray(ctl).shape
+        if len(ctl_shape) != 3:
+            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+        score_ref, score_point = _score_reference(robot, score, int(ctl_shape[0]), int(ctl_shape[1]), tip_only)
     rows = None
     networks = net_of_rod = None
     if robots is not None:  # (validated on the host before anything touches the device)
@@ -204,6 +246,12 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
                scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
                table=table, bank=bank, net_of_rod=net_of_rod)
+    if score is not None:  # queued behind the run; the copies below wait for both
+        Tr = score_ref.shape[1]
+        ref_states = h.pack_poses(score_ref, tdt)  # [Tr, 1 or B, N, KR_SLOTS], packed once
+        ref_path = ref_states[:, :, score_point, 12:15].permute(1, 0, 2)
+        score_dtw = h.dtw(states[:Tr, :, score_point, 12:15].permute(1, 0, 2), ref_path[0] if ref_path.shape[0] == 1 else ref_path)
+        score_mse, _ = h.pose_mse(states[:Tr], ref_states)
     out = {"tip": tip.cpu().numpy(), "status": status.cpu().numpy(), "G": G.cpu().numpy()}  # (.cpu() waits for the run)
     if table is not None:
         table.close()
@@ -211,6 +259,9 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         out["net_of_rod"] = np.asarray(net_of_rod, dtype=np.int32)
         out["n_networks"] = bank.K
         bank.close()
+    if score is not None:
+        out["dtw"] = score_dtw.cpu().numpy()
+        out["mse"] = score_mse.cpu().numpy()
     if not tip_only and return_states:
         N = h.N
         traj = torch.empty((B, T + 1, 25, N), dtype=tdt, device=dev)

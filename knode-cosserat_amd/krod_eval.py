@@ -14,6 +14,10 @@
   level.  **Parity with the package is unpinned** (nothing to run it against); ``dtw_distance`` is the exact DTW
   with the same point distance, a lower bound of it (equal whenever the coarse path contains the optimal one).
 * ``pos_euler_mse``: ``physics_multitrain.py:213-222`` (position + zyx Euler angles, x 1000).
+* ``euler_zyx``, ``dtw_distance_batch``, ``pos_euler_mse_batch``, ``evaluate_batch``: the same two metrics for B rods at
+  once on the MI355X (``kr_dtw_batch``, ``kr_pose_mse_batch``) - the exact DTW, not FastDTW: that needs the warp path
+  traced back on every level, and the exact distance is what it approximates.  ``evaluate_batch`` is the inner loop of
+  ``physics_multitrain.py:196-222``; nothing but two doubles per rod leaves the device.
 * ``evaluate``: the closed-loop rollout with live weights of ``physics_train.py:136-167``; the rollout is
   ``knode.simulate`` on the MI355X with the MLP inside the shooting sweeps.
 """
@@ -147,6 +151,59 @@ def pos_euler_mse(trajectory, reference):
     ee = Rotation.from_quat(eq, scalar_first=True).as_euler("zyx")
     re = Rotation.from_quat(rq, scalar_first=True).as_euler("zyx")
     return float(np.mean(np.concatenate([(ee - re) ** 2, se_pos])) * 1000)
+
+
+def euler_zyx(q):
+    """SciPy's ``Rotation.from_quat(q, scalar_first=True).as_euler("zyx")`` (extrinsic) in closed form, q[..., 4] =
+    (w, x, y, z), not necessarily unit: the host twin of the device kernel behind ``pos_euler_mse_batch``.  No
+    gimbal-lock branch: within ~1e-6 of +-pi/2 in the middle angle SciPy zeroes one angle and warns, this does not."""
+    q = np.asarray(q, dtype=np.float64)
+    n = np.sqrt(q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1] + q[..., 2] * q[..., 2] + q[..., 3] * q[..., 3])
+    w, x, y, z = q[..., 0] / n, q[..., 1] / n, q[..., 2] / n, q[..., 3] / n
+    a = np.arctan2(2.0 * (w * z - x * y), 1.0 - 2.0 * (y * y + z * z))
+    b = np.arcsin(np.clip(2.0 * (x * z + w * y), -1.0, 1.0))
+    c = np.arctan2(2.0 * (w * x - y * z), 1.0 - 2.0 * (x * x + y * y))
+    return np.stack([a, b, c], axis=-1)
+
+
+def _torch_dtype(dtype):
+    import torch
+    return torch.float64 if dtype in ("f64", torch.float64, np.float64) else torch.float32
+
+
+def dtw_distance_batch(robot, a, b, dtype="f64"):
+    """``dtw_distance(a[r], b[r])`` for every rod r in one launch on the robot's device: a[B, Ta, 3], b[B, Tb, 3] or
+    b[Tb, 3] (one path for all rods), host arrays, uploaded as ``dtype`` (the arithmetic is fp64).  Returns float64[B],
+    bit-identical to the host function on the same samples."""
+    import torch
+    dev, tdt = f"cuda:{robot.device}", _torch_dtype(dtype)
+    h = robot._native()
+    up = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64), device=dev).to(tdt).contiguous()
+    return h.dtw(up(a), up(b)).cpu().numpy()
+
+
+def pos_euler_mse_batch(robot, trajectories, reference, dtype="f64"):
+    """``pos_euler_mse(trajectories[r], reference)`` for every rod r in one launch: trajectories[B, T, >=7, N],
+    reference[T, >=7, N] (shared) or [B, T, >=7, N], N = the robot's.  Returns float64[B]."""
+    tdt = _torch_dtype(dtype)
+    h = robot._native()
+    trajectories = np.asarray(trajectories, dtype=np.float64)
+    reference = np.asarray(reference, dtype=np.float64)
+    if reference.ndim == 3:
+        reference = reference[None]
+    mse, _ = h.pose_mse(h.pack_poses(trajectories, tdt), h.pack_poses(reference, tdt))
+    return mse.cpu().numpy()
+
+
+def evaluate_batch(robot, robots, controls, reference, per_robot_nn=False, point=-1, dtype="f64"):
+    """The inner loop of physics_multitrain.py:196-222 for B rods at once: roll every ``robots[b]`` (None: B copies of
+    ``robot``) out over ``controls[b]`` in one ``knode.simulate_batch`` call and score states 0 .. Tr-1 against
+    ``reference`` ([Tr, >=7, N] or [B, Tr, >=7, N]) on the device.  Returns ``(dtw[B], mse[B])``: the exact DTW of the
+    path of grid point ``point`` (-1: the tip) and the position + Euler MSE x 1000; no trajectory leaves the device."""
+    from knode import simulate_batch
+    out = simulate_batch(robot, controls, dtype=dtype, return_states=False, robots=robots, per_robot_nn=per_robot_nn,
+                         score={"reference": reference, "point": point})
+    return out["dtw"], out["mse"]
 
 
 def evaluate(robot_eval, torch_robot, controls, reference, eval_len=None, tip_index=-1, exact=False):

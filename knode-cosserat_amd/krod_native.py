@@ -24,6 +24,7 @@ KR_EULER, KR_RK4 = 0, 1
 ACT_NONE, ACT_TANH, ACT_SOFTPLUS, ACT_RELU, ACT_ELU = range(5)
 ST_CONVERGED, ST_MAXIT, ST_NONFINITE = 0, 1, 2
 KR_MAX_LAYERS = 8
+KR_DTW_MAX_LEN = 4096
 KR_E_ARG, KR_E_UNSUPPORTED = -1, -4
 
 # reference row (0..24 of [y; z]) -> packed slot, see knode_rod.h
@@ -115,6 +116,8 @@ _PROTOS = {
     "kr_loss_rows_fwd_bwd": (_int, [_vp, _i64, _int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "kr_estimate_ws_bytes": (C.c_size_t, [_i64, _int]),
     "kr_estimate_state": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "kr_dtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp]),
+    "kr_pose_mse_batch": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -178,6 +181,21 @@ def _ptr(t):
 def _stream():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _dtw_view(t, B, name):
+    """(rod stride, step stride, samples) in elements of a device tensor read by ``Handle.dtw``: ``[B, T, 3]`` or, shared
+    by all rods, ``[T, 3]`` - any view (a slice of a state history, an expanded tensor) whose 3 components are adjacent."""
+    if not t.is_cuda:
+        raise KrError("libknode_rod works on device memory only: tensor is on " + str(t.device))
+    if t.dim() == 2:
+        t = t.unsqueeze(0).expand(B, -1, -1)
+    if t.dim() != 3 or t.shape[0] != B or t.shape[2] != 3 or t.shape[1] < 1:
+        raise KrError(f"dtw: sequence {name} must be [B, T, 3] or [T, 3] with B = {B}, T >= 1; got {tuple(t.shape)}")
+    rod, step, comp = t.stride()
+    if comp != 1 or rod < 0 or step < 0:
+        raise KrError(f"dtw: sequence {name}: the 3 components must be adjacent and the strides >= 0 (strides {t.stride()})")
+    return (0 if B == 1 else rod), (0 if t.shape[1] == 1 else step), t.shape[1]
 
 
 def derive(params: KrParams) -> KrDerived:
@@ -537,3 +555,54 @@ class Handle:
         check(self.lib.kr_simulate_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), int(bool(ring)), _ptr(G),
                                          _ptr(tip), float(tol), int(maxit), _ptr(status), int(bool(use_nn)),
                                          _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+
+    # -- evaluation metrics ------------------------------------------------------
+    def dtw(self, a, b, out=None):
+        """Exact DTW distance (L1 point distance) of every rod's path ``a[b]`` to ``b[b]``: device tensors ``[B, Ta, 3]`` and
+        ``[B, Tb, 3]`` or ``[Tb, 3]`` (one path for all rods) of one dtype; views are read in place through their strides -
+        ``states[:T, :, j, 12:15].permute(1, 0, 2)`` is grid point j of a state history, ``tip`` the tip path of
+        ``simulate``.  Returns float64 ``[B]`` on the device; bit-identical to ``krod_eval.dtw_distance`` per rod."""
+        import torch
+        if a.dim() != 3:
+            raise KrError(f"dtw: sequence a must be [B, Ta, 3]; got {tuple(a.shape)}")
+        if a.dtype != b.dtype:
+            raise KrError(f"dtw: a is {a.dtype}, b {b.dtype}")
+        B = a.shape[0]
+        ars, ass, Ta = _dtw_view(a, B, "a")
+        brs, bss, Tb = _dtw_view(b, B, "b")
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float64, device=a.device)
+        check(self.lib.kr_dtw_batch(self._h, B, C.c_void_p(a.data_ptr()), Ta, ars, ass, C.c_void_p(b.data_ptr()), Tb, brs, bss,
+                                    _ptr(out), dtype_code(a.dtype), _stream()))
+        return out
+
+    def pose_mse(self, states, ref_states):
+        """Position + zyx-Euler MSE x 1000 of every rod over packed states ``[T, B, N, KR_SLOTS]`` (the first T slots of a
+        state history) against ``ref_states`` ``[T, B, N, KR_SLOTS]`` or ``[T, 1, N, KR_SLOTS]`` (one reference for all rods).
+        Returns ``(mse[B], parts[B, 2])``, float64 on the device; parts = the position and the Euler sum of squares."""
+        import torch
+        if states.dim() != 4 or ref_states.dim() != 4 or states.shape[2:] != (self.N, KR_SLOTS) or \
+                ref_states.shape[2:] != (self.N, KR_SLOTS) or ref_states.shape[0] != states.shape[0]:
+            raise KrError(f"pose_mse: states {tuple(states.shape)} / ref_states {tuple(ref_states.shape)}: expected "
+                          f"[T, B, {self.N}, {KR_SLOTS}] and [T, B or 1, {self.N}, {KR_SLOTS}]")
+        if states.dtype != ref_states.dtype:
+            raise KrError(f"pose_mse: states are {states.dtype}, ref_states {ref_states.dtype}")
+        T, B = states.shape[0], states.shape[1]
+        mse = torch.empty((B,), dtype=torch.float64, device=states.device)
+        parts = torch.empty((B, 2), dtype=torch.float64, device=states.device)
+        check(self.lib.kr_pose_mse_batch(self._h, B, T, _ptr(states), _ptr(ref_states), ref_states.shape[1], _ptr(mse),
+                                         _ptr(parts), dtype_code(states.dtype), _stream()))
+        return mse, parts
+
+    def pack_poses(self, traj, dtype):
+        """Host trajectories ``[R, T, >=7, N]`` (reference row order: p, h, ...) as packed states ``[T, R, N, KR_SLOTS]`` of
+        ``dtype`` on the device, by one ``kr_state_pack``; rows a trajectory does not have are zero."""
+        import torch
+        traj = np.asarray(traj, dtype=np.float64)
+        R, T, rows, N = traj.shape
+        full = np.zeros((T, R, 25, N))
+        full[:, :, :min(rows, 25)] = traj.transpose(1, 0, 2, 3)[:, :, :25]
+        dev = f"cuda:{self.device}"
+        y = torch.as_tensor(np.ascontiguousarray(full[:, :, :19].reshape(T * R, 19, N)), device=dev).to(dtype).contiguous()
+        z = torch.as_tensor(np.ascontiguousarray(full[:, :, 19:].reshape(T * R, 6, N)), device=dev).to(dtype).contiguous()
+        return self.pack(y, z).reshape(T, R, N, KR_SLOTS)
