@@ -224,17 +224,41 @@ static int ensure_pred(kr_handle* h, int64_t B) {
   return KR_OK;
 }
 
+static int refuse_plan(const SimPlan& p) {
+  set_error(p.why);
+  return p.rc;
+}
 template <typename T>
-static int simulate_impl(kr_handle* h, int64_t B, int64_t T_steps, int scheme, const void* ctl, void* states, int ring,
-                         void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
+static int step_impl(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a, hipStream_t s) {
+  const SimPlan p = plan_step<T>(h, a.B, scheme, use_nn, a.mode);
+  if (p.rc) return refuse_plan(p);
+  if (int rc = launch_step<T>(h, p, a, s)) return rc;
+  note_step_plan(h, p);
+  return KR_OK;
+}
+
+// kr_simulate_batch, _table (src.table) and _bank (src.bank too): one path
+template <typename T>
+static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, int64_t T_steps, int scheme, const void* ctl, void* states,
+                         int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
                          const void* prev_init, hipStream_t s) {
   const size_t slot = (size_t)B * h->params.N * KR_SLOTS;
   T* base = (T*)states;
-  // (one predictor image per wavefront of a rod)
-  const int wpr = use_nn ? nn_sim_waves_per_rod<T>(h, scheme, B) : step_waves_per_rod<T>(h, scheme, use_nn, B, 0);
-  const int img_w = wpr ? wpr : 1;
-  {
-    // one launch for all steps when a multiple-shooting kernel with a persistent form applies
+  PlanQuery q{B, T_steps, scheme, use_nn};
+  q.source = src.bank ? KR_SRC_BANK : src.table ? KR_SRC_TABLE : KR_SRC_HANDLE;
+  if (src.table) q.N = src.table->N;
+  q.bank = src.bank;
+  q.prev_init = prev_init; q.states = states; q.slot_elems = (int64_t)slot;
+  const SimPlan plan = plan_simulate<T>(h, q);
+  if (plan.rc) return refuse_plan(plan);
+  const PredImage im = plan_pred_image(h, plan, B);
+  double* pred = nullptr;
+  if (im.use) {
+    if (int rc = ensure_pred(h, im.rows)) return rc;
+    pred = static_cast<double*>(h->pred_buf);
+  }
+  if (plan.path == 2) {
+    // one launch for all steps
     auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, G, ctl, 4, tol, maxit);
     SimArgs<T> sa{};
     sa.B = B; sa.T_steps = T_steps; sa.states = base; sa.slot_elems = (int64_t)slot; sa.ring = ring;
@@ -242,34 +266,12 @@ static int simulate_impl(kr_handle* h, int64_t B, int64_t T_steps, int scheme, c
     sa.tol = a0.tol; sa.tolA = a0.tolA; sa.fd_eps = a0.fd_eps; sa.hc1 = a0.hc1; sa.hc2 = a0.hc2;
     sa.maxit = a0.maxit; sa.predictor = h->predictor; sa.residual_test = h->residual_test; sa.nn_lowp = h->nn_lowp_first; sa.nn_base_only = h->nn_base_only_store;
     sa.dbg = static_cast<unsigned long long*>(h->dbg);
-    sa.pred_io = nullptr; sa.pred_load = 0;
-    if (h->keep_predictor && (size_t)B * img_w * KR_PRED_IMG_DOUBLES * sizeof(double) <= ((size_t)1 << 30)) {
-      int rcp = ensure_pred(h, B * img_w);
-      if (rcp) return rcp;
-      sa.pred_io = static_cast<double*>(h->pred_buf);
-      sa.pred_load = h->pred_valid_B == B && h->pred_valid_W == img_w && h->pred_valid_nn == (use_nn ? 1 : 0);
-    }
-    const int rc = launch_sim_persistent<T>(h, scheme, use_nn, sa, s);
-    if (rc != 1) {
-      h->last_sim_path = 2;
-      if (rc == KR_OK && sa.pred_io) { h->pred_valid_B = B; h->pred_valid_W = img_w; h->pred_valid_nn = use_nn ? 1 : 0; }
-      return rc;
-    }
+    sa.pred_io = pred; sa.pred_load = im.load;
+    if (int rc = launch_sim<T>(h, plan, src, sa, LaunchAt{s, false})) return rc;
+    note_sim_plan(h, plan, im, B);
+    return KR_OK;
   }
-  h->last_sim_path = 0;
-  // one launch per step: the multiple-shooting kernel carries its start-value predictor from launch to launch
-  // through an image in HBM (12 KB per rod; skipped for batches that would need more than 1 GB of it)
-  double* pred = nullptr;
-  if (h->predictor > 2 && h->ms_mode != 0 && (h->ms_mode == 1 || B <= (int64_t)h->ms_batch_limit)) {
-    const size_t need = (size_t)B * img_w * KR_PRED_IMG_DOUBLES * sizeof(double);
-    if (need <= ((size_t)1 << 30)) {
-      int rcp = ensure_pred(h, B * img_w);
-      if (rcp) return rcp;
-      pred = static_cast<double*>(h->pred_buf);
-    }
-  }
-  const bool resume = pred && h->keep_predictor && h->pred_valid_B == B && h->pred_valid_W == img_w &&
-                      h->pred_valid_nn == (use_nn ? 1 : 0);
+  // one launch per step
   for (int64_t t = 0; t < T_steps; ++t) {
     // knode.py:65-66,76-77: before the first step y_prev = y (unless the caller hands over the state before)
     const int64_t ic = ring ? t % 3 : t;
@@ -283,16 +285,13 @@ static int simulate_impl(kr_handle* h, int64_t B, int64_t T_steps, int scheme, c
     if (order > h->predictor) order = h->predictor;  // (orders 3..5: persistent kernel only)
     if (order == 2) a.prev2 = t == 1 ? (const T*)prev_init : base + (ring ? (t + 1) % 3 : t - 2) * slot;
     a.pred_order = order;
-    a.pred = pred; a.pred_reset = t == 0 && !resume; a.pred_has_prev = prev_init != nullptr; a.pred_limit = h->predictor;
+    a.pred = pred; a.pred_reset = t == 0 && !im.load; a.pred_has_prev = prev_init != nullptr; a.pred_limit = h->predictor;
     if (tip) { a.tip = (T*)tip + t * 3; a.tip_stride = T_steps * 3; }
     if (status) { a.status = status + t; a.st_stride = T_steps; }
     if (h->dbg) { a.iters = static_cast<int32_t*>(h->dbg) + t; a.st_stride = T_steps; }  // diagnostics: sweeps per rod and step, [B][T] int32
-    int rc = launch_step<T>(h, scheme, use_nn, a, s);
-    if (rc) return rc;
+    if (int rc = launch_step<T>(h, plan, a, s)) return rc;
   }
-  // the image is current only if the multiple-shooting kernel took the steps (launch_step decides)
-  if (pred) h->pred_valid_B = (T_steps > 0 && h->last_sim_path == 1) ? B : (T_steps > 0 ? 0 : h->pred_valid_B);
-  if (pred && T_steps > 0) { h->pred_valid_W = img_w; h->pred_valid_nn = use_nn ? 1 : 0; }
+  note_sim_plan(h, plan, im, B);  // (T_steps > 0 here)
   return KR_OK;
 }
 
@@ -921,12 +920,12 @@ int kr_residual_batch(kr_handle* h, int64_t B, int scheme, const void* G, const 
     auto a = make_args<float>(h, B, state_prev, state_cur, state_next, const_cast<void*>(G), tensions, 4, 0, 0);
     a.mode = 1; a.r_out = (float*)r;
     if (hist_is_explicit) { a.hc1 = 1.f; a.hc2 = 0.f; }
-    return launch_step<float>(h, scheme, use_nn, a, s);
+    return step_impl<float>(h, scheme, use_nn, a, s);
   }
   auto a = make_args<double>(h, B, state_prev, state_cur, state_next, const_cast<void*>(G), tensions, 4, 0, 0);
   a.mode = 1; a.r_out = (double*)r;
   if (hist_is_explicit) { a.hc1 = 1.0; a.hc2 = 0.0; }
-  return launch_step<double>(h, scheme, use_nn, a, s);
+  return step_impl<double>(h, scheme, use_nn, a, s);
 }
 
 int kr_residual_mid_batch(kr_handle* h, int64_t B, int scheme, const void* G, const void* hist, const void* hist_mid,
@@ -938,11 +937,11 @@ int kr_residual_mid_batch(kr_handle* h, int64_t B, int scheme, const void* G, co
   if (dtype == KR_F32) {
     auto a = make_args<float>(h, B, hist, hist, state_next, const_cast<void*>(G), tensions, 4, 0, 0);
     a.mode = 1; a.r_out = (float*)r; a.hc1 = 1.f; a.hc2 = 0.f; a.mid = (const float*)hist_mid;
-    return launch_step<float>(h, scheme, use_nn, a, s);
+    return step_impl<float>(h, scheme, use_nn, a, s);
   }
   auto a = make_args<double>(h, B, hist, hist, state_next, const_cast<void*>(G), tensions, 4, 0, 0);
   a.mode = 1; a.r_out = (double*)r; a.hc1 = 1.0; a.hc2 = 0.0; a.mid = (const double*)hist_mid;
-  return launch_step<double>(h, scheme, use_nn, a, s);
+  return step_impl<double>(h, scheme, use_nn, a, s);
 }
 
 int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, const void* state_cur,
@@ -962,12 +961,12 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
     auto a = make_args<float>(h, B, state_prev, state_cur, state_next, G, tensions, 4, tol, maxit);
     a.status = status; a.iters = iters;
     a.prev2 = (const float*)state_prev2; a.pred_order = avail;
-    return launch_step<float>(h, scheme, use_nn, a, s);
+    return step_impl<float>(h, scheme, use_nn, a, s);
   }
   auto a = make_args<double>(h, B, state_prev, state_cur, state_next, G, tensions, 4, tol, maxit);
   a.status = status; a.iters = iters;
   a.prev2 = (const double*)state_prev2; a.pred_order = avail;
-  return launch_step<double>(h, scheme, use_nn, a, s);
+  return step_impl<double>(h, scheme, use_nn, a, s);
 }
 
 // ---- per-rod parameter tables -------------------------------------------------------------------------------------
@@ -1085,35 +1084,6 @@ int kr_state_init_straight_table(kr_handle* h, const kr_param_table* t, void* st
                          : launch_tab_init_straight<double>(h, t, (double*)state, s);
 }
 
-extern "C++" {
-template <typename T>
-static int simulate_table_impl(kr_handle* h, const kr_param_table* t, int64_t T_steps, int scheme, const void* ctl, void* states,
-                               int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
-                               const void* prev_init, hipStream_t s) {
-  const int64_t B = t->B;
-  auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, G, ctl, 4, tol, maxit);
-  SimArgs<T> sa{};
-  sa.B = B; sa.T_steps = T_steps; sa.states = (T*)states; sa.slot_elems = (int64_t)((size_t)B * t->N * KR_SLOTS); sa.ring = ring;
-  sa.prev_init = (const T*)prev_init; sa.ctl = (const T*)ctl; sa.G = (T*)G; sa.tip = (T*)tip; sa.status = status;
-  sa.tol = a0.tol; sa.tolA = a0.tolA; sa.fd_eps = a0.fd_eps; sa.hc1 = a0.hc1; sa.hc2 = a0.hc2;
-  sa.maxit = a0.maxit; sa.predictor = h->predictor; sa.residual_test = h->residual_test; sa.nn_lowp = h->nn_lowp_first; sa.nn_base_only = h->nn_base_only_store;
-  sa.dbg = static_cast<unsigned long long*>(h->dbg);
-  sa.pred_io = nullptr; sa.pred_load = 0;
-  // the predictor image does not depend on the parameters: option keep_predictor works as in kr_simulate_batch
-  if (h->keep_predictor && (size_t)B * KR_PRED_IMG_DOUBLES * sizeof(double) <= ((size_t)1 << 30)) {
-    if (int rcp = ensure_pred(h, B)) return rcp;
-    sa.pred_io = static_cast<double*>(h->pred_buf);
-    sa.pred_load = h->pred_valid_B == B && h->pred_valid_W == 1 && h->pred_valid_nn == (use_nn ? 1 : 0);
-  }
-  const int rc = launch_tab_sim<T>(h, t, scheme, use_nn, sa, s);
-  if (rc == KR_OK) {
-    h->last_sim_path = 2;
-    if (sa.pred_io) { h->pred_valid_B = B; h->pred_valid_W = 1; h->pred_valid_nn = use_nn ? 1 : 0; }
-  }
-  return rc;
-}
-}  // extern "C++"
-
 int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, void* states,
                             int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
                             const void* state_prev_init, int dtype, void* stream) {
@@ -1123,11 +1093,13 @@ int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, in
   if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
   if (T == 0) return KR_OK;
   KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  SimSrc src;
+  src.table = t;
   return dtype == KR_F32
-             ? simulate_table_impl<float>(h, t, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                          state_prev_init, s)
-             : simulate_table_impl<double>(h, t, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                           state_prev_init, s);
+             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                    state_prev_init, s)
+             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                     state_prev_init, s);
 }
 
 // ---- per-rod networks: banks ----------------------------------------------------------------------------------------
@@ -1254,35 +1226,6 @@ static int ensure_net_idx(kr_handle* h, int64_t B) {
   return KR_OK;
 }
 
-extern "C++" {
-template <typename T>
-static int simulate_bank_impl(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, int64_t T_steps, int scheme,
-                              const void* ctl, void* states, int ring, void* G, void* tip, double tol, int maxit,
-                              int32_t* status, const void* prev_init, hipStream_t s) {
-  const int64_t B = t->B;
-  auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, G, ctl, 4, tol, maxit);
-  SimArgs<T> sa{};
-  sa.B = B; sa.T_steps = T_steps; sa.states = (T*)states; sa.slot_elems = (int64_t)((size_t)B * t->N * KR_SLOTS); sa.ring = ring;
-  sa.prev_init = (const T*)prev_init; sa.ctl = (const T*)ctl; sa.G = (T*)G; sa.tip = (T*)tip; sa.status = status;
-  sa.tol = a0.tol; sa.tolA = a0.tolA; sa.fd_eps = a0.fd_eps; sa.hc1 = a0.hc1; sa.hc2 = a0.hc2;
-  sa.maxit = a0.maxit; sa.predictor = h->predictor; sa.residual_test = h->residual_test; sa.nn_lowp = h->nn_lowp_first; sa.nn_base_only = h->nn_base_only_store;
-  sa.dbg = static_cast<unsigned long long*>(h->dbg);
-  sa.pred_io = nullptr; sa.pred_load = 0;
-  // option keep_predictor works as in kr_simulate_batch_table (the image is a starting guess, whatever network wrote it)
-  if (h->keep_predictor && (size_t)B * KR_PRED_IMG_DOUBLES * sizeof(double) <= ((size_t)1 << 30)) {
-    if (int rcp = ensure_pred(h, B)) return rcp;
-    sa.pred_io = static_cast<double*>(h->pred_buf);
-    sa.pred_load = h->pred_valid_B == B && h->pred_valid_W == 1 && h->pred_valid_nn == 1;
-  }
-  const int rc = launch_bank_sim<T>(h, t, bk, static_cast<const int32_t*>(h->net_idx_buf), scheme, sa, s);
-  if (rc == KR_OK) {
-    h->last_sim_path = 2;
-    if (sa.pred_io) { h->pred_valid_B = B; h->pred_valid_W = 1; h->pred_valid_nn = 1; }
-  }
-  return rc;
-}
-}  // extern "C++"
-
 int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank, const int32_t* net_of_rod_host,
                            int64_t T, int scheme, const void* ctl, void* states, int ring, void* G, void* tip, double tol,
                            int maxit, int32_t* status, const void* state_prev_init, int dtype, void* stream) {
@@ -1310,20 +1253,32 @@ int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_b
   // this call returns
   KR_HIP(hipMemcpyAsync(h->net_idx_buf, net_of_rod_host, sizeof(int32_t) * (size_t)t->B, hipMemcpyHostToDevice, s));
   KR_HIP(hipStreamSynchronize(s));
+  SimSrc src;
+  src.table = t; src.bank = bank; src.net_idx = static_cast<const int32_t*>(h->net_idx_buf);
   return dtype == KR_F32
-             ? simulate_bank_impl<float>(h, t, bank, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, state_prev_init, s)
-             : simulate_bank_impl<double>(h, t, bank, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, state_prev_init, s);
+             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, 1, state_prev_init, s)
+             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, 1, state_prev_init, s);
 }
+
+// the one-time host work of the first kr_simulate_batch (Euler, MLP off) of this batch size, ahead of time: the kernels
+// its plan names are resolved in the code object and get their dynamic LDS limit, and the buffer such a launch needs
+// from the handle (the overlapped kernel's resume steps) is grown.  A call that takes one launch per step has no such work.
+extern "C++" {
+template <typename T>
+static int prepare_impl(kr_handle* h, int64_t B) {
+  const SimPlan plan = plan_simulate<T>(h, PlanQuery{B, 1, KR_EULER, 0});
+  if (plan.rc || plan.path != 2) return KR_OK;
+  SimArgs<T> sa{};
+  sa.B = B; sa.T_steps = 1;
+  return launch_sim<T>(h, plan, SimSrc{}, sa, LaunchAt{nullptr, true});
+}
+}  // extern "C++"
 
 int kr_simulate_prepare(kr_handle* h, int64_t B, int dtype) {
   KR_CHECK_H(h);
   KR_CHECK_DTYPE(dtype);
   if (B <= 0) return KR_OK;
-  int rc = ensure_resume(h, B);
-  if (rc) return rc;
-  if (dtype == KR_F32) { rc = prepare_mso_sim<float>(h, B); if (rc != 1 && rc) return rc; rc = prepare_ms_sim<float>(h); }
-  else { rc = prepare_mso_sim<double>(h, B); if (rc != 1 && rc) return rc; rc = prepare_ms_sim<double>(h); }
-  return rc == 1 ? KR_OK : rc;
+  return dtype == KR_F32 ? prepare_impl<float>(h, B) : prepare_impl<double>(h, B);
 }
 
 int kr_simulate_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, void* states, int ring, void* G,
@@ -1334,9 +1289,9 @@ int kr_simulate_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void
   if (T == 0) return KR_OK;
   KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
   return dtype == KR_F32
-             ? simulate_impl<float>(h, B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+             ? simulate_impl<float>(h, SimSrc{}, B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
                                     state_prev_init, s)
-             : simulate_impl<double>(h, B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+             : simulate_impl<double>(h, SimSrc{}, B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
                                      state_prev_init, s);
 }
 

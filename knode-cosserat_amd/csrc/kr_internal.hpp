@@ -163,17 +163,17 @@ int order_stream(kr_handle* h, hipStream_t s);
 int dyn_lds(const void* kern, size_t smem);
 
 template <typename T>
-inline const RodConst<T>& consts(kr_handle* h);
+inline const RodConst<T>& consts(const kr_handle* h);
 template <>
-inline const RodConst<float>& consts<float>(kr_handle* h) { return h->cf; }
+inline const RodConst<float>& consts<float>(const kr_handle* h) { return h->cf; }
 template <>
-inline const RodConst<double>& consts<double>(kr_handle* h) { return h->cd; }
+inline const RodConst<double>& consts<double>(const kr_handle* h) { return h->cd; }
 template <typename T>
-inline const MlpDev<T>& mlpdev(kr_handle* h);
+inline const MlpDev<T>& mlpdev(const kr_handle* h);
 template <>
-inline const MlpDev<float>& mlpdev<float>(kr_handle* h) { return h->mlp_f; }
+inline const MlpDev<float>& mlpdev<float>(const kr_handle* h) { return h->mlp_f; }
 template <>
-inline const MlpDev<double>& mlpdev<double>(kr_handle* h) { return h->mlp_d; }
+inline const MlpDev<double>& mlpdev<double>(const kr_handle* h) { return h->mlp_d; }
 
 // kr_sim.hip
 template <typename T>
@@ -224,12 +224,6 @@ struct StepArgs {
   // nullptr = the linear interpolation knode.simulate forms (knode.py:80-81)
   const T* mid = nullptr;
 };
-template <typename T>
-int launch_step(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a, hipStream_t s);
-// wavefronts per rod the several-wavefront step kernel (kr_msw_impl.hpp) would use for this call; 0: not that kernel
-template <typename T>
-int step_waves_per_rod(kr_handle* h, int scheme, int use_nn, int64_t B, int mode);
-
 // persistent multi-step form (kr_ms_impl.hpp)
 template <typename T>
 struct SimArgs {
@@ -257,33 +251,6 @@ struct SimArgs {
   int nn_base_only = 1;   // option "nn_base_only_store" (MsSolveArgs::bo_allowed)
 };
 
-// returns 1 when the persistent form does not apply
-template <typename T>
-int launch_sim_persistent(kr_handle* h, int scheme, int use_nn, const SimArgs<T>& a, hipStream_t s);
-// kr_mso_f32.hip / kr_mso_f64.hip: the overlapped persistent kernel (diagonal material matrices, Euler, MLP off);
-// returns 1 when it does not serve the problem
-template <typename T>
-int launch_mso_sim(kr_handle* h, const SimArgs<T>& a, hipStream_t s);
-int ensure_resume(kr_handle* h, int64_t B);
-// kr_mswo_f32.hip / kr_mswo_f64.hip: the same overlap on W = 2 / 4 wavefronts per rod; 1: does not apply
-template <typename T>
-int launch_mswo_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s);
-template <typename T>
-int prepare_mso_sim(kr_handle* h, int64_t B);
-// kr_mswn_f32.hip / kr_mswn_f64.hip: several wavefronts per rod with the MLP on (persistent form; kr_msw_impl.hpp).
-// nn_sim_waves_per_rod: wavefronts per rod kr_simulate_batch will use for this batch (0: the one-wavefront kernel);
-// launch_msw_nn_sim returns 1 when it does not serve the problem
-template <typename T>
-int nn_sim_waves_per_rod(kr_handle* h, int scheme, int64_t B);
-template <typename T>
-int launch_msw_nn_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s);
-// ... and with the MLP off, for rods too long for the LDS form (N = 400); returns 1 when it does not apply either
-template <typename T>
-int launch_msw_gh_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s);
-int ensure_hist_ws(kr_handle* h, size_t bytes);
-// kr_tab_f32.hip / kr_tab_f64.hip: the one-wavefront persistent kernels with per-rod constants (kr_tab_impl.hpp).
-// launch_tab_sim refuses (KR_E_UNSUPPORTED, with a message) what these kernels do not serve; nothing falls back to the
-// handle's own parameters.
 template <typename T>
 inline const RodConst<T>* table_rows(const kr_param_table* t);
 template <>
@@ -291,24 +258,147 @@ inline const RodConst<float>* table_rows<float>(const kr_param_table* t) { retur
 template <>
 inline const RodConst<double>* table_rows<double>(const kr_param_table* t) { return t->rows_d; }
 template <typename T>
-int launch_tab_sim(kr_handle* h, const kr_param_table* t, int scheme, int use_nn, const SimArgs<T>& a, hipStream_t s);
-template <typename T>
-int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s);
-// kr_bank_f32.hip / kr_bank_f64.hip: the MLP-on persistent kernel with per-rod constants AND per-rod networks
-// (kr_bank_impl.hpp).  net_idx: device copy of the caller's index array.  Refuses what it does not serve; nothing
-// falls back to the handle's own MLP.
-template <typename T>
 inline const MlpDev<T>& bank_net0(const kr_mlp_bank* bk);
 template <>
 inline const MlpDev<float>& bank_net0<float>(const kr_mlp_bank* bk) { return bk->mf; }
 template <>
 inline const MlpDev<double>& bank_net0<double>(const kr_mlp_bank* bk) { return bk->md; }
+
+// ---- which kernel a call runs (kr_plan.hip: the rules of DESIGN.md section 5, each stated once) -----------------------
+enum SimFamily {
+  KR_FAM_SS,          // one launch per step, single shooting, 8 rods per wavefront (kr_sim_impl.hpp)
+  KR_FAM_MS_STEP,     // one launch per step, multiple shooting, MLP off (kr_ms_impl.hpp)
+  KR_FAM_MS_STEP_NN,  // ... with the MLP inside the sweeps (kr_msn_*.hip)
+  KR_FAM_MSW_STEP,    // ... on W = 2 / 4 wavefronts per rod (kr_msw_impl.hpp)
+  KR_FAM_MS_SIM,      // all steps in one launch, one wavefront per rod (kr_ms_impl.hpp)
+  KR_FAM_MSO,         // the overlapped kernel (kr_mso_impl.hpp), then KR_FAM_MS_SIM (OCC = 1) for the steps it left behind
+  KR_FAM_MSW_SIM,     // all steps in one launch on W wavefronts per rod, MLP off (history mode `hm` 0 / 1)
+  KR_FAM_MSW_NN_SIM,  // ... with the MLP on (kr_mswn_*.hip)
+  KR_FAM_MSWO         // ... with overlapped steps (kr_mswo_impl.hpp)
+};
+enum SimSource { KR_SRC_HANDLE, KR_SRC_TABLE, KR_SRC_BANK };  // where a rod's constants / network come from
+struct SimPlan {
+  int rc = KR_OK;     // KR_OK, or what a refused call returns (`why` says why)
+  int path = 0;       // what last_sim_path reports: 0 / 1 one launch per step (single / multiple shooting), 2 persistent
+  int family = KR_FAM_SS;
+  int W = 1;          // wavefronts per rod
+  int occ = 1;        // workgroups per CU the instantiation is built for (2: fp32, B > 1024)
+  int hm = 0;         // KR_FAM_MSW_SIM: where the time history lives (msw_sim_kernel)
+  int rods_per_wg = 0;  // KR_FAM_MS_STEP*: rods (= wavefronts) per workgroup
+  bool diag = true, nn = false, nn_hist = false, gt = false, overlap = false;
+  int scheme = KR_EULER;
+  size_t smem[2] = {0, 0};  // dynamic LDS of the launch (KR_FAM_MSO: of the overlapped kernel, of the take-over launch)
+  size_t hist_ws_bytes = 0; // KR_FAM_MSW_NN_SIM: the history workspace [B][N][12] (SimArgs::hist_ws)
+  char why[256] = "";
+};
+struct PlanQuery {
+  int64_t B, T_steps;
+  int scheme, use_nn;
+  int source = KR_SRC_HANDLE;
+  int N = 0;                           // table calls: the table's
+  const kr_mlp_bank* bank = nullptr;   // bank calls
+  // the aliasing rule of KR_FAM_MSWO with its tiles in HBM
+  const void* prev_init = nullptr;
+  const void* states = nullptr;
+  int64_t slot_elems = 0;
+};
 template <typename T>
-int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, const int32_t* net_idx, int scheme,
-                    const SimArgs<T>& a, hipStream_t s);
-// kr_sim_f32.hip / kr_sim_f64.hip: the same for the one-wavefront persistent kernel that runs behind it
+SimPlan plan_simulate(const kr_handle* h, const PlanQuery& q);
+// kr_step_batch, kr_residual_* (mode 1) and the steps of a kr_simulate_batch that takes one launch per step
 template <typename T>
-int prepare_ms_sim(kr_handle* h);
+SimPlan plan_step(const kr_handle* h, int64_t B, int scheme, int use_nn, int mode);
+// The start-value predictor image of a simulate call: one per wavefront of a rod, KR_PRED_IMG_DOUBLES each
+// (SimArgs::pred_io / pred_load, StepArgs::pred / pred_reset)
+struct PredImage {
+  bool use = false, load = false;  // the kernels get the buffer; ... and start from the image the call before left in it
+  int64_t rows = 0;                // images in the buffer
+};
+PredImage plan_pred_image(const kr_handle* h, const SimPlan& p, int64_t B);
+// What the last calls ran (options last_sim_path / last_overlap / last_waves_per_rod) and what they left in the image
+// buffer: written by these two only, after the launches succeeded
+void note_sim_plan(kr_handle* h, const SimPlan& p, const PredImage& im, int64_t B);
+void note_step_plan(kr_handle* h, const SimPlan& p);  // a step or residual call
+
+// Where a launch goes: stream `s`, or - kr_simulate_prepare - nowhere: the kernel is resolved in the code object and its
+// dynamic LDS limit set, which is the one-time host work of its first launch.
+struct LaunchAt {
+  hipStream_t s;
+  bool prepare_only;
+};
+template <typename... P, typename... A>
+inline int launch(const LaunchAt& at, void (*kern)(P...), dim3 grid, dim3 block, size_t smem, const A&... args) {
+  if (at.prepare_only) {
+    hipFuncAttributes fa;
+    KR_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)));
+  }
+  if (int rc = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
+  if (at.prepare_only) return KR_OK;
+  hipLaunchKernelGGL(kern, grid, block, smem, at.s, args...);
+  KR_HIP(hipGetLastError());
+  return KR_OK;
+}
+template <typename... P, typename... A>
+inline int launch(hipStream_t s, void (*kern)(P...), dim3 grid, dim3 block, size_t smem, const A&... args) {
+  return launch(LaunchAt{s, false}, kern, grid, block, smem, args...);
+}
+
+// The launchers: each maps a plan to the template instantiation it names and launches it, in the unit that holds the
+// kernel.
+struct SimSrc {
+  const kr_param_table* table = nullptr;
+  const kr_mlp_bank* bank = nullptr;
+  const int32_t* net_idx = nullptr;  // device copy of the caller's index array
+};
+template <typename T>
+int launch_step(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);            // kr_sim_*.hip
+template <typename T>
+int launch_ms_step_nn(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);      // kr_msn_*.hip
+template <typename T>
+int launch_ms_sim(kr_handle* h, const SimPlan& p, bool take_over, const SimArgs<T>& a, const LaunchAt& at);  // kr_sim_*.hip
+template <typename T>
+int launch_msw_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);     // kr_sim_*.hip (hm = 0)
+template <typename T>
+int launch_msw_gh_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_mswn_*.hip (hm = 1)
+template <typename T>
+int launch_msw_nn_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_mswn_*.hip
+template <typename T>
+int launch_mso_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);     // kr_mso_*.hip
+template <typename T>
+int launch_mswo_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);    // kr_mswo_*.hip
+template <typename T>
+int launch_tab_sim(kr_handle* h, const kr_param_table* t, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_tab_*.hip
+template <typename T>
+int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s);
+template <typename T>
+int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, const int32_t* net_idx, const SimPlan& p,
+                    const SimArgs<T>& a, const LaunchAt& at);                                    // kr_bank_*.hip
+int ensure_resume(kr_handle* h, int64_t B);
+int ensure_hist_ws(kr_handle* h, size_t bytes);
+
+// A persistent plan (path 2) carried out: the handle's buffers the plan asks for, then the launcher(s) of its family
+template <typename T>
+inline int launch_sim(kr_handle* h, const SimPlan& p, const SimSrc& src, SimArgs<T> a, const LaunchAt& at) {
+  if (p.family == KR_FAM_MSO) {  // (the overlapped kernel leaves, per rod, the first step it did not finish)
+    if (int rc = ensure_resume(h, a.B)) return rc;
+    a.resume = static_cast<int32_t*>(h->resume_buf);
+  }
+  if (p.hist_ws_bytes) {
+    if (int rc = ensure_hist_ws(h, p.hist_ws_bytes)) return rc;
+    a.hist_ws = static_cast<T*>(h->hist_ws);
+  }
+  if (src.bank) return launch_bank_sim<T>(h, src.table, src.bank, src.net_idx, p, a, at);
+  if (src.table) return launch_tab_sim<T>(h, src.table, p, a, at);
+  switch (p.family) {
+    case KR_FAM_MSO:
+      if (int rc = launch_mso_sim<T>(h, p, a, at)) return rc;
+      return launch_ms_sim<T>(h, p, true, a, at);
+    case KR_FAM_MS_SIM: return launch_ms_sim<T>(h, p, false, a, at);
+    case KR_FAM_MSWO: return launch_mswo_sim<T>(h, p, a, at);
+    case KR_FAM_MSW_NN_SIM: return launch_msw_nn_sim<T>(h, p, a, at);
+    case KR_FAM_MSW_SIM: return p.hm ? launch_msw_gh_sim<T>(h, p, a, at) : launch_msw_sim<T>(h, p, a, at);
+    default: set_error("launch_sim: not a persistent plan"); return KR_E_STATE;
+  }
+}
 
 // kr_mlp_fused.hip: fused fp32 MLP forward / backward for training
 bool fused_mlp_supported(int n_layers, const int32_t* dims, const int32_t* acts, int in_pad);

@@ -1826,46 +1826,17 @@ static int ms_wpb(int N, bool nn, size_t lds_limit) {
 }
 
 template <typename T, bool DIAG, int SCHEME, bool NN>
-static int launch_ms_inst(const RodConst<T>& P, const MlpDev<T>& M, const StepArgs<T>& a, size_t lds_limit,
-                          hipStream_t s) {
-  auto kern = ms_step_kernel<T, DIAG, SCHEME, hs_phys<T>(), NN>;
-  const int wpb = ms_wpb<T, hs_phys<T>()>(P.N, NN, lds_limit);
-  if (wpb <= 0) { set_error("multiple-shooting kernel: history of N grid points does not fit in LDS"); return KR_E_ARG; }
-  const size_t smem = ms_lds_bytes<T, hs_phys<T>()>(P.N, false, NN, wpb);
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.B + wpb - 1) / wpb)), dim3(WAVE * wpb), smem, s, P, a, M);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
-}
-
-// true if the multiple-shooting kernel can and should take this call
-template <typename T>
-static bool ms_eligible(kr_handle* h, int use_nn, const StepArgs<T>& a) {
-  const RodConst<T>& P = consts<T>(h);
-  if (a.mode != 0) return false;
-  if (use_nn) {  // the MLP must be one the matrix-core evaluator serves (no per-lane activation buffers here)
-    const MlpDev<T>& M = mlpdev<T>(h);
-    if (M.n_layers <= 0 || !M.mfma_ok || h->params.nn_input_history) return false;
-  }
-  if (h->ms_mode == 0) return false;
-  if (P.N - 1 < 2 * MS_P) return false;                 // too few segments to cut
-  if (ms_wpb<T, hs_phys<T>()>(P.N, use_nn != 0, (size_t)h->lds_limit) <= 0) return false;
-  if (h->ms_mode == 1) return true;                     // forced
-  return a.B <= (int64_t)h->ms_batch_limit;             // auto (no limit by default: faster at every batch size)
+static int launch_ms_inst(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  const int wpb = p.rods_per_wg;
+  return launch(s, ms_step_kernel<T, DIAG, SCHEME, hs_phys<T>(), NN>, dim3((unsigned)((a.B + wpb - 1) / wpb)), dim3(WAVE * wpb),
+                p.smem[0], consts<T>(h), a, mlpdev<T>(h));
 }
 
 template <typename T, bool NN>
-static int launch_ms_nn(kr_handle* h, int scheme, const StepArgs<T>& a, hipStream_t s) {
-  const RodConst<T>& P = consts<T>(h);
-  const MlpDev<T>& M = mlpdev<T>(h);
-  if (scheme == KR_EULER)
-    return P.diag ? launch_ms_inst<T, true, KR_EULER, NN>(P, M, a, (size_t)h->lds_limit, s)
-                  : launch_ms_inst<T, false, KR_EULER, NN>(P, M, a, (size_t)h->lds_limit, s);
-  if (scheme == KR_RK4)
-    return P.diag ? launch_ms_inst<T, true, KR_RK4, NN>(P, M, a, (size_t)h->lds_limit, s)
-                  : launch_ms_inst<T, false, KR_RK4, NN>(P, M, a, (size_t)h->lds_limit, s);
-  set_error("unknown scheme");
-  return KR_E_ARG;
+static int launch_ms_nn(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  if (p.scheme == KR_EULER)
+    return p.diag ? launch_ms_inst<T, true, KR_EULER, NN>(h, p, a, s) : launch_ms_inst<T, false, KR_EULER, NN>(h, p, a, s);
+  return p.diag ? launch_ms_inst<T, true, KR_RK4, NN>(h, p, a, s) : launch_ms_inst<T, false, KR_RK4, NN>(h, p, a, s);
 }
 // The one-launch-per-step kernels WITH the MLP live in their own translation units (kr_msn_f32.hip / kr_msn_f64.hip,
 // kr_msn_impl.hpp): they are the most register-starved kernels of the library, and hipcc 7.2 places ordinary VGPR
@@ -1873,110 +1844,37 @@ static int launch_ms_nn(kr_handle* h, int scheme, const StepArgs<T>& a, hipStrea
 // tools/wwm_spill_scan.py).  Those units are compiled with SGPR spills going to memory instead of VGPR lanes, which
 // removes the brackets altogether.
 template <typename T>
-int launch_ms_step_nn(kr_handle* h, int scheme, const StepArgs<T>& a, hipStream_t s);
-template <typename T>
-static int launch_ms(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a, hipStream_t s) {
-  h->last_sim_path = 1;
-  return use_nn ? launch_ms_step_nn<T>(h, scheme, a, s) : launch_ms_nn<T, false>(h, scheme, a, s);
+static int launch_ms(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  return launch_ms_nn<T, false>(h, p, a, s);
 }
+
 template <typename T, bool DIAG, int SCHEME, bool NN, int OCC = 1>
-static int launch_ms_sim_inst(const RodConst<T>& P, const MlpDev<T>& M, const SimArgs<T>& a, hipStream_t s) {
-  auto kern = ms_sim_kernel<T, DIAG, SCHEME, hs_phys<T>(), NN, OCC>;
-  const size_t smem = ms_lds_bytes<T, hs_phys<T>()>(P.N, true, NN);
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), dim3(WAVE * MS_WPB), smem, s, P, a, M);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+static int launch_ms_sim_inst(kr_handle* h, size_t smem, const SimArgs<T>& a, const LaunchAt& at) {
+  return launch(at, ms_sim_kernel<T, DIAG, SCHEME, hs_phys<T>(), NN, OCC>, dim3((unsigned)((a.B + MS_WPB - 1) / MS_WPB)),
+                dim3(WAVE * MS_WPB), smem, consts<T>(h), a, mlpdev<T>(h));
 }
-
+// KR_FAM_MS_SIM, or (take_over) the launch behind the overlapped kernel of KR_FAM_MSO: always the OCC = 1 instantiation
 template <typename T>
-static int launch_msw_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s);  // kr_msw_impl.hpp
-
-// returns 1 when the persistent form does not apply (caller falls back to one launch per step)
-template <typename T>
-int launch_sim_persistent(kr_handle* h, int scheme, int use_nn, const SimArgs<T>& a, hipStream_t s) {
-  const RodConst<T>& P = consts<T>(h);
-  if (h->ms_mode == 0 || h->persistent == 0) return 1;
-  h->last_overlap = 0;
-  if (const int W = step_waves_per_rod<T>(h, scheme, use_nn, a.B, 0)) {  // several wavefronts per rod
-    if (h->msw_overlap && P.diag) {
-      const int rc = launch_mswo_sim<T>(h, W, a, s);
-      if (rc == KR_OK) h->last_overlap = 1;
-      if (rc != 1) return rc;
-    }
-    return launch_msw_sim<T>(h, W, a, s);
+int launch_ms_sim(kr_handle* h, const SimPlan& p, bool take_over, const SimArgs<T>& a, const LaunchAt& at) {
+  const size_t smem = p.smem[take_over ? 1 : 0];
+  // MLP inside the sweeps: the matrix-core evaluator, Euler sweeps and diagonal material matrices only (one
+  // more instantiation of the largest kernel per arithmetic type)
+  if (p.nn) return launch_ms_sim_inst<T, true, KR_EULER, true>(h, smem, a, at);
+  if (p.scheme == KR_RK4)
+    return p.diag ? launch_ms_sim_inst<T, true, KR_RK4, false>(h, smem, a, at) : launch_ms_sim_inst<T, false, KR_RK4, false>(h, smem, a, at);
+  if constexpr (sizeof(T) == 4) {  // (two wavefronts per SIMD: fp32 only)
+    if (p.occ == 2 && !take_over) return launch_ms_sim_inst<T, true, KR_EULER, false, 2>(h, smem, a, at);
   }
-  h->last_waves_per_rod = 1;
-  const MlpDev<T>& M = mlpdev<T>(h);
-  if (use_nn) {
-    if (const int W = nn_sim_waves_per_rod<T>(h, scheme, a.B)) {  // several wavefronts per rod, MLP on (kr_mswn_*.hip)
-      const int rc = launch_msw_nn_sim<T>(h, W, a, s);
-      if (rc != 1) return rc;
-    }
-    // MLP inside the sweeps: the matrix-core evaluator, Euler sweeps and diagonal material matrices only (one
-    // more instantiation of the largest kernel per arithmetic type; everything else takes one launch per step)
-    // (the persistent kernel carries the base + JVP evaluator only: a network it does not serve takes one launch per step)
-    if (M.n_layers <= 0 || !M.mfma_ok || !M.jvp_ok || h->params.nn_input_history || scheme != KR_EULER || !P.diag) return 1;
-    if (P.N - 1 < 2 * MS_P || P.N > MS_NPL * WAVE) return 1;
-    if (ms_lds_bytes<T, hs_phys<T>()>(P.N, true, true) > (size_t)h->lds_limit) return 1;
-    if (h->ms_mode != 1 && a.B > (int64_t)h->ms_batch_limit) return 1;
-    return launch_ms_sim_inst<T, true, KR_EULER, true>(P, M, a, s);
-  }
-  if (P.N - 1 < 2 * MS_P || P.N > MS_NPL * WAVE) return 1;
-  if (ms_lds_bytes<T, hs_phys<T>()>(P.N, true) > (size_t)h->lds_limit) return 1;
-  if (h->ms_mode != 1 && a.B > (int64_t)h->ms_batch_limit) return 1;
-  h->last_overlap = 0;
-  if (scheme == KR_EULER && P.diag && h->overlap) {
-    // two launches: the overlapped kernel (one sweep per step in the steady state), then this file's persistent
-    // kernel for the rods that left steps behind (a rod that finished exits at once)
-    SimArgs<T> a2 = a;
-    int rc = ensure_resume(h, a.B);
-    if (rc) return rc;
-    a2.resume = static_cast<int32_t*>(h->resume_buf);
-    rc = launch_mso_sim<T>(h, a2, s);
-    if (rc == KR_OK) {
-      h->last_overlap = 1;
-      return launch_ms_sim_inst<T, true, KR_EULER, false>(P, M, a2, s);
-    }
-    if (rc != 1) return rc;
-  }
-  if (scheme == KR_EULER) {
-    if constexpr (sizeof(T) == 4) {
-      // fp32, more rods than SIMDs, and two workgroups fit the LDS of a CU: the two-wavefronts-per-SIMD instantiation
-      if (P.diag && a.B > 1024 && 2 * ms_lds_bytes<T, hs_phys<T>()>(P.N, true) <= (size_t)h->lds_limit)
-        return launch_ms_sim_inst<T, true, KR_EULER, false, 2>(P, M, a, s);
-    }
-    return P.diag ? launch_ms_sim_inst<T, true, KR_EULER, false>(P, M, a, s) : launch_ms_sim_inst<T, false, KR_EULER, false>(P, M, a, s);
-  }
-  if (scheme == KR_RK4)
-    return P.diag ? launch_ms_sim_inst<T, true, KR_RK4, false>(P, M, a, s) : launch_ms_sim_inst<T, false, KR_RK4, false>(P, M, a, s);
-  set_error("unknown scheme");
-  return KR_E_ARG;
+  return p.diag ? launch_ms_sim_inst<T, true, KR_EULER, false>(h, smem, a, at) : launch_ms_sim_inst<T, false, KR_EULER, false>(h, smem, a, at);
 }
 }  // namespace kr
 
 #include "kr_msw_impl.hpp"  // several wavefronts per rod (uses everything above)
 
-namespace kr {
-// one-time host work of the first launch of the persistent Euler / MLP-off kernel, ahead of time (kr_simulate_prepare)
-template <typename T>
-int prepare_ms_sim(kr_handle* h) {
-  const RodConst<T>& P = consts<T>(h);
-  if (!P.diag) return 1;
-  auto kern = ms_sim_kernel<T, true, KR_EULER, hs_phys<T>(), false, 1>;
-  hipFuncAttributes fa;
-  KR_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)));
-  const size_t smem = ms_lds_bytes<T, hs_phys<T>()>(P.N, true);
-  if (smem <= (size_t)h->lds_limit) if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  return KR_OK;
-}
-}  // namespace kr
-
 #ifndef KR_MS_NO_INST  // (kr_mso_*.hip include this file for its device functions only)
 namespace kr {
-template int prepare_ms_sim<KR_SIM_T>(kr_handle*);
-template int launch_sim_persistent<KR_SIM_T>(kr_handle*, int, int, const SimArgs<KR_SIM_T>&, hipStream_t);
-template int step_waves_per_rod<KR_SIM_T>(kr_handle*, int, int, int64_t, int);
+template int launch_ms_sim<KR_SIM_T>(kr_handle*, const SimPlan&, bool, const SimArgs<KR_SIM_T>&, const LaunchAt&);
+template int launch_msw_sim<KR_SIM_T>(kr_handle*, const SimPlan&, const SimArgs<KR_SIM_T>&, const LaunchAt&);
 
 KR_INST(KR_SIM_T)
 

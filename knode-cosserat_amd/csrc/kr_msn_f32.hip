@@ -3,5 +3,5 @@
 #define KR_MS_NO_INST
 #include "kr_msn_impl.hpp"
 namespace kr {
-template int launch_ms_step_nn<float>(kr_handle*, int, const StepArgs<float>&, hipStream_t);
+template int launch_ms_step_nn<float>(kr_handle*, const SimPlan&, const StepArgs<float>&, hipStream_t);
 }

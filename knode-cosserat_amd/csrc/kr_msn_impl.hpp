@@ -12,7 +12,7 @@
 
 namespace kr {
 template <typename T>
-int launch_ms_step_nn(kr_handle* h, int scheme, const StepArgs<T>& a, hipStream_t s) {
-  return launch_ms_nn<T, true>(h, scheme, a, s);
+int launch_ms_step_nn(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  return launch_ms_nn<T, true>(h, p, a, s);
 }
 }  // namespace kr

@@ -2,6 +2,5 @@
 #define KR_MS_NO_INST
 #include "kr_mso_impl.hpp"
 namespace kr {
-template int launch_mso_sim<float>(kr_handle*, const SimArgs<float>&, hipStream_t);
-template int prepare_mso_sim<float>(kr_handle*, int64_t);
+template int launch_mso_sim<float>(kr_handle*, const SimPlan&, const SimArgs<float>&, const LaunchAt&);
 }

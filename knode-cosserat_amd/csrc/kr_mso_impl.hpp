@@ -991,62 +991,19 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
 }
 
-// The kernel counts steps in 32 bits (SimArgs::resume always did); offsets into `states`, `ctl`, `tip` and `status` are
-// formed in 64 bits.
-inline int mso_check_steps(int64_t T_steps) {
-  if (T_steps > (int64_t)0x7fffffff) {
-    set_error("T_steps = " + std::to_string(T_steps) + ": the overlapped persistent kernel counts steps in 32 bits (T_steps < 2^31)");
-    return KR_E_ARG;
-  }
-  return KR_OK;
+// The kernel counts steps in 32 bits (SimArgs::resume always did; the planner refuses T_steps >= 2^31); offsets into
+// `states`, `ctl`, `tip` and `status` are formed in 64 bits.
+template <typename T, int OCC, typename PSRC>
+static int launch_mso_inst(const PSRC& P, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  return launch(at, mso_sim_kernel<T, true, hs_phys<T>(), OCC, PSRC>, dim3((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), dim3(WAVE * MS_WPB),
+                p.smem[0], P, a);
 }
-
-// Host-side one-time work of the first launch, done ahead of time (kr_simulate_prepare): resolves the kernel in the
-// code object and sets its dynamic LDS limit.  Returns 1 when the kernel does not serve the handle's problem.
 template <typename T>
-int prepare_mso_sim(kr_handle* h, int64_t B) {
-  const RodConst<T>& P = consts<T>(h);
-  constexpr int HS = hs_phys<T>();
-  if (!P.diag || P.N - 1 < 2 * MS_P) return 1;
-  const size_t smem = sizeof(T) * mso_lds_elems<T, HS>(P.N) * MS_WPB;
-  if (smem > (size_t)h->lds_limit) return 1;
-  hipFuncAttributes fa;
-  if (sizeof(T) == 4 && B > 1024 && 2 * smem <= (size_t)h->lds_limit) {
-    auto k2 = mso_sim_kernel<T, true, HS, 2>;
-    KR_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k2)));
-    if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(k2), smem)) return rc_lds_;
-  } else {
-    auto k1 = mso_sim_kernel<T, true, HS, 1>;
-    KR_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k1)));
-    if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(k1), smem)) return rc_lds_;
+int launch_mso_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  if constexpr (sizeof(T) == 4) {  // (two wavefronts per SIMD: fp32 only)
+    if (p.occ == 2) return launch_mso_inst<T, 2>(consts<T>(h), p, a, at);
   }
-  return KR_OK;
-}
-
-template <typename T>
-int launch_mso_sim(kr_handle* h, const SimArgs<T>& a, hipStream_t s) {
-  const RodConst<T>& P = consts<T>(h);
-  constexpr int HS = hs_phys<T>();
-  if (!P.diag || P.N - 1 < 2 * MS_P) return 1;
-  const size_t smem = sizeof(T) * mso_lds_elems<T, HS>(P.N) * MS_WPB;
-  if (smem > (size_t)h->lds_limit) return 1;
-  if (int rc_steps_ = mso_check_steps(a.T_steps)) return rc_steps_;
-  const dim3 grid((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), block(WAVE * MS_WPB);
-  if constexpr (sizeof(T) == 4) {
-    // fp32, more rods than SIMDs, and two workgroups fit the LDS of a CU: two wavefronts per SIMD
-    if (a.B > 1024 && 2 * smem <= (size_t)h->lds_limit) {
-      auto kern2 = mso_sim_kernel<T, true, HS, 2>;
-      if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern2), smem)) return rc_lds_;
-      hipLaunchKernelGGL(kern2, grid, block, smem, s, P, a);
-      KR_HIP(hipGetLastError());
-      return KR_OK;
-    }
-  }
-  auto kern = mso_sim_kernel<T, true, HS, 1>;
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  hipLaunchKernelGGL(kern, grid, block, smem, s, P, a);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch_mso_inst<T, 1>(consts<T>(h), p, a, at);
 }
 
 }  // namespace kr

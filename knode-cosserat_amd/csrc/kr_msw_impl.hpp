@@ -1623,86 +1623,24 @@ __global__ __launch_bounds__(WAVE * W, OCC) void msw_sim_kernel(const RodConst<T
 }
 
 template <typename T, bool DIAG, int W, bool NN = false, int OCC = 1, int HM = NN ? 2 : 0>
-static int launch_msw_sim_inst(const RodConst<T>& P, const MlpDev<T>& M, const SimArgs<T>& a, hipStream_t s) {
-  auto kern = msw_sim_kernel<T, DIAG, W, NN, OCC, HM>;
-  const size_t smem = sizeof(T) * msw_sim_lds_elems<T, W>(P.N, NN, HM);
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.B), dim3(WAVE * W), smem, s, P, a, M);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+static int launch_msw_sim_inst(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  return launch(at, msw_sim_kernel<T, DIAG, W, NN, OCC, HM>, dim3((unsigned)a.B), dim3(WAVE * W), p.smem[0], consts<T>(h), a, mlpdev<T>(h));
 }
-// kr_simulate_batch with several wavefronts per rod: 0 launched (all steps in one launch), 1 does not apply
+// kr_simulate_batch with several wavefronts per rod, MLP off, everything in LDS (hm = 0)
 template <typename T>
-static int launch_msw_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s) {
-  const RodConst<T>& P = consts<T>(h);
-  const size_t bytes = sizeof(T) * (W == 2 ? msw_sim_lds_elems<T, 2>(P.N) : msw_sim_lds_elems<T, 4>(P.N));
-  // (every rod resident at once: a second round of workgroups would wait for the first to finish all steps)
-  if (bytes > (size_t)h->lds_limit || a.B > 256 * (int64_t)((size_t)h->lds_limit / bytes))
-    return launch_msw_gh_sim<T>(h, W, a, s);  // long rods: the form that reads the two newest states from A.states
-  h->last_waves_per_rod = W;
-  const MlpDev<T>& M = mlpdev<T>(h);
-  if (W == 2) return P.diag ? launch_msw_sim_inst<T, true, 2>(P, M, a, s) : launch_msw_sim_inst<T, false, 2>(P, M, a, s);
-  return P.diag ? launch_msw_sim_inst<T, true, 4>(P, M, a, s) : launch_msw_sim_inst<T, false, 4>(P, M, a, s);
+int launch_msw_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  if (p.W == 2) return p.diag ? launch_msw_sim_inst<T, true, 2>(h, p, a, at) : launch_msw_sim_inst<T, false, 2>(h, p, a, at);
+  return p.diag ? launch_msw_sim_inst<T, true, 4>(h, p, a, at) : launch_msw_sim_inst<T, false, 4>(h, p, a, at);
 }
 
-template <typename T, int W>
-static size_t msw_lds_bytes(int N) { return sizeof(T) * msw_lds_elems<T, W>(N); }
-
-// wavefronts per rod this call should use (0: not this kernel).  Auto: batches that leave SIMDs idle (one wavefront per
-// SIMD at most, B W <= 1024); the option "waves_per_rod" forces 1 / 2 / 4.  Measured, fp64, us per step
-// (tools/msw_timing.py; persistent = all steps of kr_simulate_batch in one launch):
-//     N    B    persistent W=1   per step W=4   persistent W=2   persistent W=4
-//    40  256        20.5            25.5            18.2             18.6
-//    64  256        26.9             -              21.4             20.3
-//   100  256        35.9            30.3            26.9             23.6
-//   100  512        36.5             -              29.5              -
-//   128  256     (47.7 per step)    32.6            31.1             25.6
-//   400  256    (115 per step)      59.5             -              52.6     (persistent: the long-rod form, HM = 1)
-template <typename T>
-int step_waves_per_rod(kr_handle* h, int scheme, int use_nn, int64_t B, int mode) {
-  const RodConst<T>& P = consts<T>(h);
-  if (use_nn || scheme != KR_EULER || mode != 0 || h->ms_mode == 0) return 0;
-  auto fits_bytes = [&](size_t bytes) {
-    if (bytes > (size_t)h->lds_limit) return false;
-    return B <= 256 * (int64_t)((size_t)h->lds_limit / bytes);
-  };
-  auto fits = [&](int W) {  // the one-launch-per-step kernel
-    if (P.N - 1 < 2 * (4 + 3 * (W - 1)) || B * W > 1024) return false;
-    return fits_bytes(W == 2 ? msw_lds_bytes<T, 2>(P.N) : msw_lds_bytes<T, 4>(P.N));
-  };
-  auto fits_sim = [&](int W) {  // ... and its persistent form
-    return fits_bytes(sizeof(T) * (W == 2 ? msw_sim_lds_elems<T, 2>(P.N) : msw_sim_lds_elems<T, 4>(P.N)));
-  };
-  if (h->waves_per_rod == 1) return 0;
-  if (h->waves_per_rod == 2) return fits(2) ? 2 : 0;
-  if (h->waves_per_rod == 4) return fits(4) ? 4 : 0;
-  if (P.N <= MS_NPL * WAVE) {
-    // the persistent one-wavefront kernel serves these: several wavefronts only where their own persistent form fits
-    // and the rod is long enough for the shorter chains to pay for the distributed condensation
-    if (P.N >= 56 && fits(4) && fits_sim(4)) return 4;
-    if (P.N >= 32 && fits(2) && fits_sim(2)) return 2;
-    return 0;
-  }
-  if (fits(4)) return 4;
-  if (fits(2)) return 2;
-  return 0;
-}
 template <typename T, bool DIAG, int W>
-static int launch_msw_inst(const RodConst<T>& P, const StepArgs<T>& a, hipStream_t s) {
-  auto kern = msw_step_kernel<T, DIAG, W>;
-  const size_t smem = msw_lds_bytes<T, W>(P.N);
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.B), dim3(WAVE * W), smem, s, P, a);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+static int launch_msw_inst(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  return launch(s, msw_step_kernel<T, DIAG, W>, dim3((unsigned)a.B), dim3(WAVE * W), p.smem[0], consts<T>(h), a);
 }
 template <typename T>
-static int launch_msw(kr_handle* h, int W, const StepArgs<T>& a, hipStream_t s) {
-  const RodConst<T>& P = consts<T>(h);
-  h->last_sim_path = 1;
-  h->last_waves_per_rod = W;
-  if (W == 2) return P.diag ? launch_msw_inst<T, true, 2>(P, a, s) : launch_msw_inst<T, false, 2>(P, a, s);
-  return P.diag ? launch_msw_inst<T, true, 4>(P, a, s) : launch_msw_inst<T, false, 4>(P, a, s);
+static int launch_msw(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  if (p.W == 2) return p.diag ? launch_msw_inst<T, true, 2>(h, p, a, s) : launch_msw_inst<T, false, 2>(h, p, a, s);
+  return p.diag ? launch_msw_inst<T, true, 4>(h, p, a, s) : launch_msw_inst<T, false, 4>(h, p, a, s);
 }
 
 }  // namespace kr

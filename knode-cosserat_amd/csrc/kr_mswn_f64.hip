@@ -2,7 +2,6 @@
 #define KR_MS_NO_INST
 #include "kr_mswn_impl.hpp"
 namespace kr {
-template int nn_sim_waves_per_rod<double>(kr_handle*, int, int64_t);
-template int launch_msw_nn_sim<double>(kr_handle*, int, const SimArgs<double>&, hipStream_t);
-template int launch_msw_gh_sim<double>(kr_handle*, int, const SimArgs<double>&, hipStream_t);
+template int launch_msw_nn_sim<double>(kr_handle*, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
+template int launch_msw_gh_sim<double>(kr_handle*, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
 }

@@ -2,5 +2,5 @@
 #define KR_MS_NO_INST
 #include "kr_mswo_impl.hpp"
 namespace kr {
-template int launch_mswo_sim<float>(kr_handle*, int, const SimArgs<float>&, hipStream_t);
+template int launch_mswo_sim<float>(kr_handle*, const SimPlan&, const SimArgs<float>&, const LaunchAt&);
 }

@@ -632,37 +632,15 @@ __global__ __launch_bounds__(WAVE * W) void mswo_sim_kernel(const RodConst<T> Pc
   }
 }
 
-// kr_simulate_batch with several wavefronts per rod and overlapped steps: 0 launched, 1 does not apply
+// kr_simulate_batch with several wavefronts per rod and overlapped steps
 template <typename T, int W, bool GT>
-static int launch_mswo_inst(const RodConst<T>& P, const SimArgs<T>& a, size_t bytes, hipStream_t s) {
-  auto kern = mswo_sim_kernel<T, W, GT>;
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), bytes)) return rc_lds_;
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.B), dim3(WAVE * W), bytes, s, P, a);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+static int launch_mswo_inst(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  return launch(at, mswo_sim_kernel<T, W, GT>, dim3((unsigned)a.B), dim3(WAVE * W), p.smem[0], consts<T>(h), a);
 }
 template <typename T>
-int launch_mswo_sim(kr_handle* h, int W, const SimArgs<T>& a, hipStream_t s) {
-  const RodConst<T>& P = consts<T>(h);
-  if (!P.diag || (W != 2 && W != 4)) return 1;
-  if (P.N - 1 < 2 * (4 + 3 * (W - 1))) return 1;
-  // (every rod resident at once: a second round of workgroups would wait for the first to finish all steps)
-  auto fits = [&](size_t bytes) { return bytes <= (size_t)h->lds_limit && a.B <= 256 * (int64_t)((size_t)h->lds_limit / bytes); };
-  const size_t b_lds = sizeof(T) * (W == 2 ? mswo_lds_elems<T, 2, false>(P.N) : mswo_lds_elems<T, 4, false>(P.N));
-  const size_t b_gt = sizeof(T) * (W == 2 ? mswo_lds_elems<T, 2, true>(P.N) : mswo_lds_elems<T, 4, true>(P.N));
-  static const int force_gt = std::getenv("KR_MSWO_GT") ? std::atoi(std::getenv("KR_MSWO_GT")) : -1;  // (tests: 1 = tiles in HBM, 0 = never)
-  const bool use_gt = force_gt == 1 || (force_gt != 0 && !fits(b_lds));
-  if (use_gt ? !fits(b_gt) : !fits(b_lds)) return 1;
-  if (use_gt && a.prev_init) {
-    // The GT form reads the state before states[0] while step 0 is being verified, i.e. while the slot of state 1 is written:
-    // a caller's prev_init inside that slot (knode_rod.h allows it to point into the ring) takes the plain form, which
-    // consumes it before its first store.
-    const T* s1 = a.states + a.slot_elems;
-    if (a.prev_init >= s1 && a.prev_init < s1 + a.slot_elems) return 1;
-  }
-  h->last_waves_per_rod = W;
-  if (use_gt) return W == 2 ? launch_mswo_inst<T, 2, true>(P, a, b_gt, s) : launch_mswo_inst<T, 4, true>(P, a, b_gt, s);
-  return W == 2 ? launch_mswo_inst<T, 2, false>(P, a, b_lds, s) : launch_mswo_inst<T, 4, false>(P, a, b_lds, s);
+int launch_mswo_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  if (p.gt) return p.W == 2 ? launch_mswo_inst<T, 2, true>(h, p, a, at) : launch_mswo_inst<T, 4, true>(h, p, a, at);
+  return p.W == 2 ? launch_mswo_inst<T, 2, false>(h, p, a, at) : launch_mswo_inst<T, 4, false>(h, p, a, at);
 }
 
 }  // namespace kr

@@ -679,12 +679,7 @@ __global__ void hist_kernel(const RodConst<T> P, T hc1, T hc2, int64_t B, const 
 template <typename T, bool DIAG, int SCHEME, bool HIST_LDS, bool NN, int HS>
 static int launch_step_inst(const RodConst<T>& P, const MlpDev<T>& M, const StepArgs<T>& a, size_t smem,
                             hipStream_t s) {
-  auto kern = step_kernel<T, DIAG, SCHEME, HIST_LDS, NN, HS>;
-  if (int rc_lds_ = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc_lds_;
-  const int grid = (int)((a.B + RPW - 1) / RPW);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE), smem, s, P, a, M);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, step_kernel<T, DIAG, SCHEME, HIST_LDS, NN, HS>, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(WAVE), smem, P, a, M);
 }
 
 template <typename T, int SCHEME, bool NN, int HS>
@@ -718,8 +713,7 @@ static int launch_step_mem(kr_handle* h, StepArgs<T> a, hipStream_t s) {
     if (!hist_in_lds) {
       a.hist_ws = reinterpret_cast<T*>(w);
       w += hist_bytes;
-      hipLaunchKernelGGL((hist_kernel<T, HS>), dim3(1024), dim3(256), 0, s, P, a.hc1, a.hc2, a.B, a.cur, a.prev, a.hist_ws);
-      KR_HIP(hipGetLastError());
+      if (int rc = launch(s, hist_kernel<T, HS>, dim3(1024), dim3(256), 0, P, a.hc1, a.hc2, a.B, a.cur, a.prev, a.hist_ws)) return rc;
     }
     if (NN && !act_in_lds) a.act_ws = reinterpret_cast<T*>(w);
   }
@@ -733,33 +727,26 @@ static int launch_step_mem(kr_handle* h, StepArgs<T> a, hipStream_t s) {
 }
 
 template <typename T, int SCHEME>
-static int launch_step_nn(kr_handle* h, int use_nn, const StepArgs<T>& a, hipStream_t s) {
-  if (!use_nn) return launch_step_mem<T, SCHEME, false, hs_phys<T>()>(h, a, s);
-  if (mlpdev<T>(h).n_layers <= 0) {
-    set_error("use_nn requested but no MLP was set (kr_set_mlp)");
-    return KR_E_STATE;
-  }
-  if (h->params.nn_input_history) return launch_step_mem<T, SCHEME, true, HS_NNH>(h, a, s);
+static int launch_step_nn(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  if (!p.nn) return launch_step_mem<T, SCHEME, false, hs_phys<T>()>(h, a, s);
+  if (p.nn_hist) return launch_step_mem<T, SCHEME, true, HS_NNH>(h, a, s);
   return launch_step_mem<T, SCHEME, true, hs_phys<T>()>(h, a, s);
 }
 
 template <typename T>
-static bool ms_eligible(kr_handle* h, int use_nn, const StepArgs<T>& a);
+static int launch_ms(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);   // kr_ms_impl.hpp
 template <typename T>
-static int launch_ms(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a, hipStream_t s);
+static int launch_msw(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);  // kr_msw_impl.hpp
 
 template <typename T>
-static int launch_msw(kr_handle* h, int W, const StepArgs<T>& a, hipStream_t s);
-
-template <typename T>
-int launch_step(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a, hipStream_t s) {
-  h->last_waves_per_rod = 1;
-  if (const int W = step_waves_per_rod<T>(h, scheme, use_nn, a.B, a.mode)) return launch_msw<T>(h, W, a, s);
-  if (ms_eligible<T>(h, use_nn, a)) return launch_ms<T>(h, scheme, use_nn, a, s);
-  if (scheme == KR_EULER) return launch_step_nn<T, KR_EULER>(h, use_nn, a, s);
-  if (scheme == KR_RK4) return launch_step_nn<T, KR_RK4>(h, use_nn, a, s);
-  set_error("unknown scheme");
-  return KR_E_ARG;
+int launch_step(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s) {
+  switch (p.family) {
+    case KR_FAM_MSW_STEP: return launch_msw<T>(h, p, a, s);
+    case KR_FAM_MS_STEP: return launch_ms<T>(h, p, a, s);
+    case KR_FAM_MS_STEP_NN: return launch_ms_step_nn<T>(h, p, a, s);
+    default: break;
+  }
+  return p.scheme == KR_EULER ? launch_step_nn<T, KR_EULER>(h, p, a, s) : launch_step_nn<T, KR_RK4>(h, p, a, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -863,41 +850,31 @@ static inline int grid_for(int64_t n, int block = 256) {
 template <typename T>
 int launch_init_straight(kr_handle* h, int64_t B, T* state, hipStream_t s) {
   const RodConst<T>& P = consts<T>(h);
-  hipLaunchKernelGGL((init_straight_kernel<T>), dim3(grid_for(B * P.N)), dim3(256), 0, s, P, h->params.L, B, state);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, init_straight_kernel<T>, dim3(grid_for(B * P.N)), dim3(256), 0, P, h->params.L, B, state);
 }
 template <typename T>
 int launch_pack(kr_handle* h, int64_t B, const T* y_fm, const T* z_fm, T* state, hipStream_t s) {
   const int N = h->params.N;
-  hipLaunchKernelGGL((pack_kernel<T>), dim3(grid_for(B * 25 * N)), dim3(256), 0, s, N, B, y_fm, z_fm, state);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, pack_kernel<T>, dim3(grid_for(B * 25 * N)), dim3(256), 0, N, B, y_fm, z_fm, state);
 }
 template <typename T>
 int launch_unpack(kr_handle* h, int64_t B, const T* state, T* y_fm, T* z_fm, hipStream_t s) {
   const int N = h->params.N;
-  hipLaunchKernelGGL((unpack_kernel<T>), dim3(grid_for(B * 25 * N)), dim3(256), 0, s, N, B, state, y_fm, z_fm);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, unpack_kernel<T>, dim3(grid_for(B * 25 * N)), dim3(256), 0, N, B, state, y_fm, z_fm);
 }
 template <typename T>
 int launch_unpack50(kr_handle* h, int64_t B, const T* st, const T* m1, const T* m2, T* out, hipStream_t s) {
   const RodConst<T>& P = consts<T>(h);
-  hipLaunchKernelGGL((unpack50_kernel<T>), dim3(grid_for(B * 50 * P.N)), dim3(256), 0, s, P, B, st, m1, m2, out);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, unpack50_kernel<T>, dim3(grid_for(B * 50 * P.N)), dim3(256), 0, P, B, st, m1, m2, out);
 }
 template <typename T>
 int launch_tip(kr_handle* h, int64_t B, const T* state, T* tip, hipStream_t s) {
   const int N = h->params.N;
-  hipLaunchKernelGGL((tip_kernel<T>), dim3(grid_for(B * 3)), dim3(256), 0, s, N, B, state, tip);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, tip_kernel<T>, dim3(grid_for(B * 3)), dim3(256), 0, N, B, state, tip);
 }
 
 #define KR_INST(T)                                                                              \
-  template int launch_step<T>(kr_handle*, int, int, const StepArgs<T>&, hipStream_t);            \
+  template int launch_step<T>(kr_handle*, const SimPlan&, const StepArgs<T>&, hipStream_t);      \
   template int launch_init_straight<T>(kr_handle*, int64_t, T*, hipStream_t);                   \
   template int launch_pack<T>(kr_handle*, int64_t, const T*, const T*, T*, hipStream_t);        \
   template int launch_unpack<T>(kr_handle*, int64_t, const T*, T*, T*, hipStream_t);            \

@@ -13,9 +13,8 @@
 // kernel next to its plain twin: the same fp64 instruction counts, no scalar memory instruction inside a loop, no
 // scratch where the plain kernel has none.
 //
-// Served: Euler sweeps, diagonal material matrices on every row, 8 <= N - 1, N <= 128, one wavefront per rod;
-// MLP off (overlapped kernel + take-over launch, or the plain persistent kernel for overlap = 0) or an MLP the
-// persistent one-wavefront kernel serves (one network, the handle's, for all rods).  Everything else is refused.
+// Served: one wavefront per rod, MLP off (overlapped kernel + take-over launch, or the plain persistent kernel) or the
+// handle's network for all rods; plan_simulate (kr_plan.hip) holds the rules and refuses everything else.
 #pragma once
 #include "kr_mso_impl.hpp"
 
@@ -41,64 +40,21 @@ __global__ void init_straight_tab_kernel(int N, const double* __restrict__ Ls, i
 
 template <typename T>
 int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s) {
-  hipLaunchKernelGGL((init_straight_tab_kernel<T>), dim3(grid_for(t->B * t->N)), dim3(256), 0, s, t->N, t->L, t->B, state);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  return launch(s, init_straight_tab_kernel<T>, dim3(grid_for(t->B * t->N)), dim3(256), 0, t->N, t->L, t->B, state);
 }
 
-static inline int tab_refuse(const std::string& why) {
-  set_error("kr_simulate_batch_table: " + why + " (not served with a parameter table; nothing falls back to the handle's parameters)");
-  return KR_E_UNSUPPORTED;
-}
-
+// KR_FAM_MSO: two launches, as with the handle's constants - the overlapped kernel, then the take-over launch for what
+// it left behind (a.resume); KR_FAM_MS_SIM: the one-wavefront persistent kernel alone
 template <typename T>
-int launch_tab_sim(kr_handle* h, const kr_param_table* t, int scheme, int use_nn, const SimArgs<T>& a, hipStream_t s) {
+int launch_tab_sim(kr_handle* h, const kr_param_table* t, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
   constexpr int HS = hs_phys<T>();
-  const int N = t->N;
-  if (scheme != KR_EULER) return tab_refuse("only Euler sweeps (scheme = KR_EULER)");
-  if (N - 1 < 2 * MS_P || N > MS_NPL * WAVE) return tab_refuse("N = " + std::to_string(N) + ", the one-wavefront persistent kernels serve 9 <= N <= 128");
-  if (h->ms_mode == 0 || h->persistent == 0) return tab_refuse("options ms_mode = 0 / persistent = 0 select kernels without a table form");
-  if (h->ms_mode != 1 && a.B > (int64_t)h->ms_batch_limit) return tab_refuse("B exceeds option ms_batch_limit");
-  if (h->waves_per_rod > 1) return tab_refuse("option waves_per_rod = " + std::to_string(h->waves_per_rod) + ", table calls run one wavefront per rod");
-  if (a.B > (int64_t)0x7fffffff) return tab_refuse("B >= 2^31");
-  const MlpDev<T>& M = mlpdev<T>(h);
-  if (use_nn) {
-    if (M.n_layers <= 0) { set_error("use_nn requested but no MLP was set (kr_set_mlp)"); return KR_E_STATE; }
-    if (!M.mfma_ok || !M.jvp_ok || h->params.nn_input_history) return tab_refuse("an MLP the persistent one-wavefront kernel does not evaluate");
-  }
-  const RodTable<T> tab{(const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t), N};
+  const RodTable<T> tab{(const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t), t->N};
   const dim3 grid((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), block(WAVE * MS_WPB);
-  h->last_waves_per_rod = 1;
-  h->last_overlap = 0;
-  if (use_nn) {
-    const size_t smem = ms_lds_bytes<T, HS>(N, true, true);
-    if (smem > (size_t)h->lds_limit) return tab_refuse("the rod's history does not fit the LDS with the MLP on");
-    auto kern = ms_sim_kernel<T, true, KR_EULER, HS, true, 1, RodTable<T>>;
-    if (int rc = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
-    hipLaunchKernelGGL(kern, grid, block, smem, s, tab, a, M);
-    KR_HIP(hipGetLastError());
-    return KR_OK;
-  }
-  const size_t smem = ms_lds_bytes<T, HS>(N, true);
-  if (smem > (size_t)h->lds_limit) return tab_refuse("the rod's history does not fit the LDS");
-  SimArgs<T> a2 = a;
-  const size_t smem_o = sizeof(T) * mso_lds_elems<T, HS>(N) * MS_WPB;
-  if (h->overlap && smem_o <= (size_t)h->lds_limit) {
-    // two launches, as launch_sim_persistent: the overlapped kernel, then the take-over launch for what it left behind
-    if (int rc = ensure_resume(h, a.B)) return rc;
-    a2.resume = static_cast<int32_t*>(h->resume_buf);
-    if (int rc = mso_check_steps(a.T_steps)) return rc;
-    auto ko = mso_sim_kernel<T, true, HS, 1, RodTable<T>>;
-    if (int rc = dyn_lds(reinterpret_cast<const void*>(ko), smem_o)) return rc;
-    hipLaunchKernelGGL(ko, grid, block, smem_o, s, tab, a2);
-    KR_HIP(hipGetLastError());
-    h->last_overlap = 1;
-  }
-  auto kern = ms_sim_kernel<T, true, KR_EULER, HS, false, 1, RodTable<T>>;
-  if (int rc = dyn_lds(reinterpret_cast<const void*>(kern), smem)) return rc;
-  hipLaunchKernelGGL(kern, grid, block, smem, s, tab, a2, M);
-  KR_HIP(hipGetLastError());
-  return KR_OK;
+  if (p.nn) return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, true, 1, RodTable<T>>, grid, block, p.smem[0], tab, a, mlpdev<T>(h));
+  if (p.family == KR_FAM_MSO)
+    if (int rc = launch_mso_inst<T, 1>(tab, p, a, at)) return rc;
+  return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, false, 1, RodTable<T>>, grid, block, p.smem[p.family == KR_FAM_MSO ? 1 : 0], tab, a,
+                mlpdev<T>(h));
 }
 
 }  // namespace kr
