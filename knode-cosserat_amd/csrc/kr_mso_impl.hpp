@@ -113,6 +113,89 @@ __device__ __forceinline__ U* own_sgpr_global(U* p) {
   return (U*)(__attribute__((address_space(1))) U*)v;
 }
 
+// ms_pred_update for this kernel (every step it hands over has converged).  While the fitted recurrence is in use and
+// predicted the step to better than 1e-3 (ms_pred_update's poly_eval == false) no polynomial order is measured: every
+// em[p] is 3.0e38f there, the order-choice loop ends at nxt = pmax and eb = 3.0e38f.  That case is written out straight -
+// the error of the fit, keep or refit, the two decisions, the level shift, in ms_pred_update's order and with its
+// expressions; every other case is ms_pred_update itself.
+template <typename T, int NC>
+__device__ __forceinline__ void mso_pred_update(MsPred<T, NC>& Q, int order, int predictor, int lane, const T* Xs,
+                                                MsStamps& stamps) {
+  // (wavefront-uniform by construction; said so, so that the two forms are two branches and not two masked passes)
+  if (!__builtin_amdgcn_readfirstlane((int)(order == MS_ORDER_LP && Q.lp_good))) {
+    ms_pred_update<T>(Q, order, KR_ST_CONVERGED, predictor, lane, Xs, stamps);
+    return;
+  }
+#ifdef KR_MS_STAMPS
+  unsigned long long tpu;
+  KR_STAMP(tpu);
+#endif
+  float err_lp = 0.f;
+  if (Q.lp_have) {
+#pragma unroll
+    for (int q = 0; q < MS_EPL; ++q) {
+      const int e = lane + q * WAVE;
+      if (e < MS_NE) {
+        const double x = (double)Xs[e];
+        double b[NC];
+        lp_basis<T, NC>(Q.Hx[q], b);
+        err_lp = fmaxf(err_lp, update_ratio(x - lp_eval<NC>(Q.lpa, b), x));
+      }
+    }
+  }
+  const float em_lp = wave_max_nonneg(err_lp);
+#ifdef KR_MS_STAMPS
+  KR_STAMP_ADD(stamps.a1, tpu);  // error of the fit in use
+#endif
+  const bool lp_tested = Q.lp_have;
+  const bool keep_fit = lp_tested && em_lp < 1.0e-3f && Q.lp_age < 3;
+  Q.lp_age = keep_fit ? Q.lp_age + 1 : 0;
+  Q.lp_have = keep_fit;
+  if (!keep_fit && predictor >= MS_ORDER_LP && Q.avail >= NC - 1) {
+    double Sn[lp_nsum<NC>()];
+#pragma unroll
+    for (int k = 0; k < lp_nsum<NC>(); ++k) Sn[k] = 0.0;
+#pragma unroll
+    for (int q = 0; q < MS_EPL; ++q) {
+      const int e = lane + q * WAVE;
+      if (e < MS_NE) {
+        const double x = (double)Xs[e];
+        double b[NC];
+        lp_basis<T, NC>(Q.Hx[q], b);
+        const double w = (double)__builtin_amdgcn_rcpf(fmaxf(fabsf((float)x), 1.0f));
+        lp_accumulate<NC>(Sn, b, x, w);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < lp_nsum<NC>(); ++k) Sn[k] = wave_sum_f64(Sn[k]);
+    double a[NC];
+    if (lp_solve<NC>(Sn, a)) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k) Q.lpa[k] = a[k];
+      Q.lp_have = true;
+    }
+  }
+#ifdef KR_MS_STAMPS
+  KR_STAMP_ADD(stamps.a2, tpu);  // refit (every fourth step)
+#endif
+  Q.next_order = Q.avail < predictor ? Q.avail : (predictor < MS_HLEV ? predictor : MS_HLEV - 1);  // pmax
+  Q.lp_good = lp_tested && Q.lp_have && em_lp < 1.0e-3f;
+  if (lp_tested && Q.lp_have && (em_lp < 3.0e38f || Q.lp_good)) Q.next_order = MS_ORDER_LP;
+#ifdef KR_MS_STAMPS
+  stamps.osum += (unsigned long long)order; stamps.olast = order;
+  for (int p = 0; p < MS_HLEV; ++p) stamps.em[p] = 3.0e38f;
+  KR_STAMP_ADD(stamps.a3, tpu);  // choice of the next order
+#endif
+#pragma unroll
+  for (int q = 0; q < MS_EPL; ++q) {
+    const int e = lane + q * WAVE;
+#pragma unroll
+    for (int k = MS_HLEV - 1; k > 0; --k) Q.Hx[q][k] = Q.Hx[q][k - 1];
+    if (e < MS_NE) Q.Hx[q][0] = Xs[e];  // MS_YP == 19: Xs is the same flat vector
+  }
+  if (Q.avail < MS_HLEV - 1) ++Q.avail;
+}
+
 #ifdef KR_MS_STAMPS
 struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 0, chord = 0, rejects = 0, retries = 0, rebuilds = 0, t_sweep = 0, t_alg = 0, t_pred = 0, t_verdict = 0, t_cond = 0, t_fin = 0, t_upd = 0, t_v1 = 0, t_v2 = 0, t_c1 = 0, t_c2 = 0, t_copy = 0; };
 #endif
@@ -341,6 +424,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       return hist_form(la, lb);
     };
     RodHist<T> hst = hist_at(point_of(0));
+    // a step of a ring call whose state nobody reads as a complete record (the last three states of a call stay complete)
+    const bool lean = a_ring && tB + 4 <= T_steps;
     if (!merged) {
       // plain forward-difference sweep (start-up, rough inputs, after a rejection): the branch-free body of
       // kr_ms_impl.hpp, two grid points per trip so that the scheduler overlaps neighbours; every interval has
@@ -369,7 +454,6 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       //     bulk of ode_eval and the Euler update need only the current record)
       // In a predicated trip past a lane's interval the clamped older read is that of the slot the lane has just written,
       // taken before the store: such a lane's record feeds an evaluation that is multiplied by dsl = 0.
-      const bool lean = a_ring && tB + 4 <= T_steps;  // (the last three states of a call stay complete)
       T* const lead_w = lead_of(tB + 1);               // the tile the verifying lanes write: state tB + 1 over state tB - 1
       auto trip = [&](int k, auto full_tag, auto lean_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
@@ -418,12 +502,12 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           for (int c = 0; c < 12; ++c) lead[c] = rec[c];
           // On a 3-slot ring nobody reads the states of the call's interior steps - except this kernel when it rolls a
           // step back and the kernel launched behind it when it takes a rod over, and both need only the twelve leading
-          // slots of every record plus the full records at the interval starts and at the last grid point (predictor,
-          // z of the last point).  The leading slots are what this sweep leaves in its tile: once the step is accepted
+          // slots of every record (v and u of the last grid point, which no sweep touches, are among them) plus the full
+          // records at the interval starts (predictor).  The leading slots are what this sweep leaves in its tile: once the step is accepted
           // the whole tile goes out in one pass of the wavefront (below, 2 x 6 stores from all lanes instead of 6 stores
           // from four lanes in every trip); interior records of interior steps store nothing here (an interval start is
-          // the grid point of trip 0, the last grid point is the verdict's: the trailing predicated trips are interior
-          // too), all others only their remaining sixteen slots or, in a predicated trip, the whole record.
+          // the grid point of trip 0, the last grid point's record is the verdict's and as lean as these: the trailing
+          // predicated trips are interior too), all others only their remaining sixteen slots or, in a predicated trip, the whole record.
           if constexpr (FULL) {
             if constexpr (!LEAN) {  // the rest of the record (p h n m); its leading slots follow with the tile
               T rest[KR_SLOTS - 12];
@@ -591,7 +675,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         if (ib == MS_P - 1) {  // the last grid point: y from the sweep, z untouched
           T rec[KR_SLOTS];
           record_from(y, vlast, ulast, rec);
-          store_record(out_rod + (size_t)(N - 1) * KR_SLOTS, rec);
+          // (a lean ring step: the leading slots go out with the tile once the step is accepted, and slots 12.. of this
+          //  record have no reader - rebuild and the take-over kernel read q w v u here, full records at interval starts)
+          if (!lean) store_record(out_rod + (size_t)(N - 1) * KR_SLOTS, rec);
           T lead[12];
 #pragma unroll
           for (int c = 0; c < 12; ++c) lead[c] = rec[c];
@@ -944,7 +1030,11 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       { unsigned long long t_; KR_STAMP(t_); st.t_copy += t_ - tq; }
 #endif
       dnB = dn; ampB = amp; belowB = below; itB = it; orderB = order;
-      if (!pred_skip) ms_pred_update<T>(Q, order, KR_ST_CONVERGED, a_predictor, lane, XsB, stamps);
+      if (!pred_skip) {
+        // (two wavefronts per SIMD: the second copy of the refit cost the fp32 instantiation 12 B more scratch)
+        if constexpr (OCC == 1) mso_pred_update<T>(Q, order, a_predictor, lane, XsB, stamps);
+        else ms_pred_update<T>(Q, order, KR_ST_CONVERGED, a_predictor, lane, XsB, stamps);
+      }
 #ifdef KR_MS_STAMPS
       { unsigned long long t_; KR_STAMP(t_); st.t_upd += t_ - tq; }
 #endif
