@@ -319,7 +319,8 @@ int kr_simulate_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void
  * the plain persistent kernel for MLP-on and overlap = 0.  Options residual_test, overlap, predictor, keep_predictor,
  * nn_* mean what they mean for kr_simulate_batch; waves_per_rod = 2 / 4, ms_mode = 0 and persistent = 0 are refused.
  * NOT served with a table: several wavefronts per rod, N > 128, single shooting, RK4, full material matrices, one
- * launch per step, kr_step_batch / kr_residual_* / kr_ode_batch, per-rod N / del_t, training.  A per-rod MLP is served
+ * launch per step, kr_step_batch / kr_residual_* / kr_ode_batch, per-rod N / del_t, training (independent trainings of
+ * several rod models share an epoch's launches through kr_train_bank_*, below).  A per-rod MLP is served
  * by kr_simulate_batch_bank (below), not by kr_simulate_batch_table. */
 typedef struct kr_param_table kr_param_table;
 
@@ -356,7 +357,7 @@ int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, in
  * predictor, keep_predictor, nn_* mean what they mean for kr_simulate_batch_table; waves_per_rod = 2 / 4,
  * ms_mode = 0 and persistent = 0 are refused.
  * NOT served with a bank: RK4, several wavefronts per rod, N > 128, single shooting, kr_ode_batch / kr_step_batch,
- * networks of differing shape in one bank, training.
+ * networks of differing shape in one bank, training (kr_train_bank_*, below, trains K networks in one call per epoch).
  * The handle's own MLP (kr_set_mlp) is neither read nor changed by a bank or a bank call. */
 typedef struct kr_mlp_bank kr_mlp_bank;
 
@@ -483,6 +484,59 @@ int kr_train_epochs(kr_handle* h, int64_t n_epochs, int64_t S, int K, int n_laye
                     const float* x, int in_pad, const float* base, const float* target_rows, double denom, float* dout, void* ws,
                     double beta1, double beta2, double eps, double weight_decay, int64_t step, double factor, int patience,
                     double threshold, double min_lr, float* loss_log, int repack, void* stream);
+
+/* ---- banks of trainings: n_nets independent KNODE trainings per epoch call ---- */
+/* The reference trains a grid of networks, not one: physics_multitrain.py:140-157 starts one physics_train.py process
+ * per (data set, model variant, seed), each running the epoch loop of physics_train.py:306-408 on its own imperfect rod
+ * model, two processes at a time.  At the reference's own size (train_len 30, 4 key points: 116 rows) an epoch of
+ * kr_train_epoch occupies 1 and then 8 of the chip's 256 compute units, three launches in a row.  A bank of trainings
+ * runs n_nets such trainings in the SAME three launches per epoch, training k in blockIdx.y = k of every kernel.
+ *
+ * Shared by all trainings: the network shape (n_layers, dims, acts), K, in_pad, denom (the loss weights depend on K and
+ * denom only), the Adam and plateau constants and the step count.
+ * Per training: everything in kr_train_bank_net - parameters, gradients, moments, the clamp, the schedule (the learning
+ * rate lives in sched: every training has its own plateau history), the data rows (S may differ between trainings), ds
+ * of the rod model that produced them, the loss log.
+ * Served: exactly what kr_train_epoch serves in phase 0 with the LDS-resident forward kernels - 28 -> H1 <= 512 -> 25 and
+ * 28 -> H1 <= 64 -> H2 <= 64 -> 25, one activation on the hidden layers, none after the last, in_pad 32, n_nets <= 65535.
+ * Anything else: KR_E_UNSUPPORTED, or KR_E_ARG for malformed input, with kr_last_error() naming the rule and the first
+ * offending network; nothing is launched and no buffer is touched.
+ * Result: training k performs the arithmetic of kr_train_epoch(s) on the same buffers in the same order (its row blocks
+ * are dealt out over the workgroups kr_train_epoch would launch for its S alone) - params, moments, sched and the logged
+ * losses are bit-identical to the training run alone.
+ * NOT served with a bank of trainings: phases 1 / 2 (data parallel), networks of differing shape, the generic GEMM path
+ * (other shapes, two-layer networks with H1 > 512), S = 0.
+ * The bank owns its scratch (weight fragments, activation images, gradient slabs, loss partials, dout) in one device
+ * allocation sized from each training's real need; it neither reads nor changes the handle's own training state, and
+ * calls are ordered on the handle like every other call. */
+typedef struct kr_train_bank kr_train_bank;
+typedef struct kr_train_bank_net {      /* one training; all pointers DEVICE, owned by the caller */
+  int64_t S;                            /* window steps x trajectories of THIS training; rows = S * K */
+  double  ds;                           /* arc-length step of the rod that produced x / base (kr_get_derived().ds) */
+  float *params, *grads, *exp_avg, *exp_avg_sq;   /* as kr_train_epoch; grads has its trailing loss slot, zero on entry */
+  const float* lower;                   /* nullable */
+  double* sched;                        /* 6 doubles, as kr_adam_plateau_step */
+  const float *x, *base, *target_rows;  /* [S*K][in_pad], [S*K][25], [S*K][25] */
+  float* loss_log;                      /* nullable; epoch e of a call writes loss_log[log_offset + e] */
+} kr_train_bank_net;
+
+/* Host arithmetic only (no handle, no GPU - like kr_param_table_check): may these trainings ride in one bank?  KR_OK, or
+ * KR_E_ARG / KR_E_UNSUPPORTED with kr_last_error() naming the rule and, where the fault is in a row, the network. */
+int kr_train_bank_check(int n_nets, const kr_train_bank_net* nets_host, int K, int n_layers,
+                        const int32_t* dims, const int32_t* acts, int in_pad, double denom);
+/* kr_train_bank_check, then allocates the bank's scratch and writes the per-training kernel arguments to the device
+ * (synchronous copies; nothing is launched).  The pointers of nets_host are kept: the buffers must outlive the bank.
+ * nets_host itself has been read when the call returns.  Destroy the bank after its last call has finished. */
+int kr_train_bank_create(kr_handle* h, int n_nets, const kr_train_bank_net* nets_host, int K, int n_layers,
+                         const int32_t* dims, const int32_t* acts, int in_pad, double denom, kr_train_bank** out);
+/* n_epochs epochs of every training, queued as n_epochs x 3 launches; epoch e uses step + e and logs to
+ * loss_log[log_offset + e].  The first call on a bank packs the weight fragments from params (one more launch);
+ * repack != 0 packs again (the caller wrote some params from outside, e.g. loaded a checkpoint) - later epochs rely on
+ * the tail's own fragment update, as kr_train_epoch does.  Arguments are checked before anything is queued. */
+int kr_train_bank_epochs(kr_handle* h, kr_train_bank* bank, int64_t n_epochs, int64_t step, double beta1, double beta2,
+                         double eps, double weight_decay, double factor, int patience, double threshold, double min_lr,
+                         int64_t log_offset, int repack, void* stream);
+int kr_train_bank_destroy(kr_train_bank* bank);
 
 /* The same loss against pre-gathered targets: the states a training set is scored against never
  * change between epochs, so kr_gather_targets extracts rows[S*K][25] once (y rows at column idx[k],

@@ -32,8 +32,11 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include <vector>
+
 #include "kr_internal.hpp"
 #include "kr_loss_device.hpp"
+#include "kr_train_bank.hpp"
 
 namespace kr {
 
@@ -96,37 +99,13 @@ struct PackArgs {
   int L;
 };
 __global__ void pack_all_kernel(const PackArgs P) {
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
-  for (int k = 0; k < P.L; ++k) {
-    const float* __restrict__ W = P.W[k];
-    const int in = P.in[k], out = P.out[k], ks = P.ks[k];
-    const int n = P.tiles[k] * ks * 64;
-    for (int i = tid; i < n; i += nth) {
-      // element i = ((t * ks / 4 + s / 4) * 64 + lane) * 4 + s % 4: four consecutive k-steps of a lane are ONE 16-byte load
-      const int e = i & 3, lane = (i >> 2) & 63, g = (i >> 8) % (ks / 4), t = (i >> 8) / (ks / 4);
-      const int s = 4 * g + e;
-      const int uo = 16 * t + (lane & 15), q = lane >> 4;
-      const int ui = k == 0 ? 4 * s + q : 16 * (s / 4) + 4 * q + (s % 4);
-      P.wf[k][i] = (uo < out && ui < in) ? W[(size_t)uo * in + ui] : 0.f;
-    }
-    const int nb = P.tiles[k] * 4 * 64;
-    for (int i = tid; i < nb; i += nth) {
-      const int lane = i & 63, r = (i >> 6) & 3, t = i >> 8;
-      const int u = 16 * t + 4 * (lane >> 4) + r;
-      P.bf[k][i] = u < out ? P.b[k][u] : 0.f;
-    }
-    if (k > 0) {
-      const int kst = P.kst[k];
-      const int nt = P.in_tiles[k] * kst * 64;
-      for (int i = tid; i < nt; i += nth) {
-        const int e = i & 3, lane = (i >> 2) & 63, g = (i >> 8) % (kst / 4), ti = (i >> 8) / (kst / 4);
-        const int s = 4 * g + e;
-        const int ui = 16 * ti + (lane & 15), q = lane >> 4;
-        const int uo = P.natural[k] ? 4 * s + q : 16 * (s / 4) + 4 * q + (s % 4);
-        P.wt[k][i] = (uo < out && ui < in) ? W[(size_t)uo * in + ui] : 0.f;
-      }
-    }
-  }
+#define KR_BODY_PACK
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_PACK
+#undef KR_BX
+#undef KR_NBX
 }
 
 // ---- register-level building blocks ------------------------------------------------------------------
@@ -746,91 +725,17 @@ __device__ __forceinline__ void fwd2_epilogue(const FusedArgs& A, float* to, con
 // lane), and base and target rows pass through the output tile one after the other (3.2 KB per wavefront).
 constexpr int FW2 = 8;
 constexpr int FW2_OUT = FR * 25;
+// (The bodies of the kernels an epoch launches are in kr_mlp_fused_bodies.inc: their bank forms further down include the
+// same text under another meaning of "my workgroup" and "the workgroups that share this network's row blocks".)
 template <int ACT>
 __global__ __launch_bounds__(64 * FW2) void mlp_fwd2_kernel(const FusedArgs A) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int c1 = A.c1;
-  float* const wl0 = wg_lds;
-  float* const wl1 = wl0 + c1 * 2048;
-  float* const bl1 = wl1 + c1 * 2048;
-  float* const bl2 = bl1 + 64 * c1;
-  float* const to = bl2 + 32 + wv * FW2_OUT;
-  {
-    const int t = threadIdx.x;
-    const f4* s0 = reinterpret_cast<const f4*>(A.wf[0]);
-    const f4* s1 = reinterpret_cast<const f4*>(A.wf[1]);
-    f4* d0 = reinterpret_cast<f4*>(wl0);
-    f4* d1 = reinterpret_cast<f4*>(wl1);
-    for (int i = t; i < c1 * 512; i += 64 * FW2) { d0[i] = s0[i]; d1[i] = s1[i]; }
-    for (int u = t; u < 64 * c1; u += 64 * FW2) bl1[u] = A.bfr[0][((u >> 4) * 4 + (u & 3)) * 64 + 16 * ((u & 15) >> 2)];
-    if (t < 32) bl2[t] = A.bfr[1][((t >> 4) * 4 + (t & 3)) * 64 + 16 * ((t & 15) >> 2)];
-  }
-  __syncthreads();
-  const int64_t nblk = (A.Q + FR - 1) / FR;
-  const bool with_loss = A.lbase != nullptr;
-  const int gid = blockIdx.x * FW2 + wv;
-  const int c = lane & 15, g = lane >> 4;
-  float loss_part = 0.f;
-  for (int64_t rb = gid; rb < nblk; rb += (int64_t)gridDim.x * FW2) {
-    float bin[FT][8];
-#pragma unroll
-    for (int s = 0; s < FT; ++s) {
-      const int64_t row = rb * FR + 16 * s + c;
-      const float* xr = A.x + (row < A.Q ? row : A.Q - 1) * F_LDX + g;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float v = xr[4 * k];
-        bin[s][k] = row < A.Q ? v : 0.f;
-      }
-    }
-    constexpr int LNV = (FR * 25 / 4 + 63) / 64;
-    f4 lvb[LNV], lvt[LNV];
-    if (with_loss) {
-      const int64_t e0 = rb * FR * 25, eN = A.Q * 25;
-      const f4* sb = reinterpret_cast<const f4*>(A.lbase + e0);
-      const f4* st = reinterpret_cast<const f4*>(A.ltarget + e0);
-#pragma unroll
-      for (int q = 0; q < LNV; ++q) {
-        const int i = lane + 64 * q;
-        lvb[q] = f4{0.f, 0.f, 0.f, 0.f};
-        lvt[q] = f4{1.f, 0.f, 0.f, 0.f};
-        if (i < FR * 25 / 4) {
-          if (e0 + 4 * i + 3 < eN) {
-            lvb[q] = sb[i];
-            lvt[q] = st[i];
-          } else {
-            for (int cc = 0; cc < 4; ++cc)
-              if (e0 + 4 * i + cc < eN) { lvb[q][cc] = A.lbase[e0 + 4 * i + cc]; lvt[q][cc] = A.ltarget[e0 + 4 * i + cc]; }
-          }
-        }
-      }
-    }
-    f4 oacc[2][FT];
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-      const f4 b = *reinterpret_cast<const f4*>(bl2 + 16 * o + 4 * g);
-#pragma unroll
-      for (int s = 0; s < FT; ++s) oacc[o][s] = b;
-    }
-    for (int ch = 0; ch < c1; ++ch) {
-      FChunk h;
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        const f4 b = *reinterpret_cast<const f4*>(bl1 + 64 * ch + 16 * o + 4 * g);
-#pragma unroll
-        for (int s = 0; s < FT; ++s) h.a[o][s] = b;
-      }
-      facc<4, 8>(h.a, wl0, 8, 4 * ch, 0, lane, [&](int s, int k) { return bin[s][k]; });
-      chunk_act_only<ACT>(h);
-      facc<2, 16>(oacc, wl1, 16 * c1, 0, 16 * ch, lane, [&](int s, int k) { return h.a[k >> 2][s][k & 3]; });
-    }
-    fwd2_epilogue(A, to, lvb, lvt, oacc, rb, lane, loss_part);
-  }
-  if (with_loss) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) loss_part += __shfl_xor(loss_part, m, 64);
-    if (lane == 0) A.lpart[gid] = loss_part;
-  }
+#define KR_BODY_FWD2
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_FWD2
+#undef KR_BX
+#undef KR_NBX
 }
 
 template <int ACT>
@@ -842,27 +747,13 @@ __global__ __launch_bounds__(64, 2) void mlp_fwd_fused_kernel(const FusedArgs A)
 
 template <int ACT>
 __global__ __launch_bounds__(64 * FW3, 1) void mlp_fwd3_kernel(const FusedArgs A) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* const wl = wg_lds;
-  {
-    const int t = threadIdx.x;
-    const f4* s0 = reinterpret_cast<const f4*>(A.wf[0]);
-    const f4* s1 = reinterpret_cast<const f4*>(A.wf[1]);
-    const f4* s2 = reinterpret_cast<const f4*>(A.wf[2]);
-    f4* d = reinterpret_cast<f4*>(wl);
-    for (int i = t; i < FW3_W1 / 4; i += 64 * FW3) d[FW3_W0 / 4 + i] = s0[i];
-    for (int i = t; i < (FW3_W2 - FW3_W1) / 4; i += 64 * FW3) d[FW3_W1 / 4 + i] = s1[i];
-    for (int i = t; i < (FW3_B - FW3_W2) / 4; i += 64 * FW3) d[FW3_W2 / 4 + i] = s2[i];
-    if (t < 160) {  // compact biases out of the bias fragments: b[u] sits at fragment slot ((u / 16) 4 + u % 4) 64 + 16 ((u % 16) / 4)
-      const int k = t < 64 ? 0 : t < 128 ? 1 : 2, u = t - 64 * k;
-      wl[FW3_B + t] = A.bfr[k][((u >> 4) * 4 + (u & 3)) * 64 + 16 * ((u & 15) >> 2)];
-    }
-  }
-  __syncthreads();
-  float* const tx = wg_lds + FW3_FRAG + wv * FW3_WAVE;
-  float* const tbt = tx + 2 * FR * F_LDX;
-  const int gid = blockIdx.x * FW3 + wv;
-  fwd_rows<ACT, true>(A, tx, tbt, wl, lane, gid, (int64_t)gridDim.x * FW3, gid);
+#define KR_BODY_FWD3
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_FWD3
+#undef KR_BX
+#undef KR_NBX
 }
 
 // sum of the per-workgroup loss partials of a fused forward + loss launch, added to *loss
@@ -1052,90 +943,13 @@ constexpr int BW3 = 8;
 constexpr int BW3_LDS = (64 + 64) * TP;
 template <int ACT>
 __global__ __launch_bounds__(64 * BW3) void mlp_bwd3_kernel(const FusedArgs A) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* const tu = wg_lds + wv * BW3_LDS;  // dOUT^T, then A1, then dZ1
-  float* const tv = tu + 64 * TP;           // A2, then dZ2, then X^T
-  float* const wl3 = wg_lds + BW3 * BW3_LDS;  // W3^T fragments: 4 x 8 x 64
-  float* const wl2 = wl3 + B3A_WT;            // W2^T fragments: 4 x 16 x 64
-  {
-    const f4* s3 = reinterpret_cast<const f4*>(A.wt[2]);
-    const f4* s2 = reinterpret_cast<const f4*>(A.wt[1]);
-    f4* d3 = reinterpret_cast<f4*>(wl3);
-    f4* d2 = reinterpret_cast<f4*>(wl2);
-    for (int i = threadIdx.x; i < B3A_WT / 4; i += 64 * BW3) d3[i] = s3[i];
-    for (int i = threadIdx.x; i < B3B_WT / 4; i += 64 * BW3) d2[i] = s2[i];
-  }
-  __syncthreads();
-  const int64_t nblk = (A.Q + FR - 1) / FR;
-  const int64_t wave0 = (int64_t)blockIdx.x * BW3 + wv, nwaves = (int64_t)gridDim.x * BW3;
-  f4 aW1[4][2], aW2[4][4], aW3[2][4];
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) aW1[o][i] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) aW2[o][i] = f4{0.f, 0.f, 0.f, 0.f};
-  }
-#pragma unroll
-  for (int o = 0; o < 2; ++o)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) aW3[o][i] = f4{0.f, 0.f, 0.f, 0.f};
-  float pb1 = 0.f, pb2 = 0.f, pbo = 0.f;
-  for (int64_t rb = wave0; rb < nblk; rb += nwaves) {
-    stage_rows_T(A.dout, rb * FR, A.Q, tu, lane);
-    FChunk d2;
-    {
-      FChunk h1;
-      {
-        FChunk h;
-        chunk_undump(h, A.a2d, rb, lane);
-        chunk_undump(h1, A.a1d, rb, lane);
-        chunk_to_T(tv, h, lane);  // A2
-      }
-      fsync();
-      if (lane < 32) pbo += row_sum_T(tu, lane);
-      wgrad_T<2, 4>(aW3, tu, tv, lane);  // dW3 += dOUT^T A2
-      chunk_zero(d2);
-      float bd[FT][8];
-      load_bops_T(bd, tu, lane);
-      fsync();
-      chunk_to_T(tu, h1, lane);  // A1 over dOUT^T
-      facc<4, 8>(d2.a, wl3, 8, 0, 0, lane, [&](int s, int k) { return bd[s][k]; });
-    }
-    chunk_mul_grad_T<ACT>(d2, tv, lane);
-    fsync();
-    chunk_to_T(tv, d2, lane);  // dZ2 (A2 is consumed)
-    fsync();
-    pb2 += row_sum_T(tv, lane);
-    wgrad_T<4, 4>(aW2, tv, tu, lane);  // dW2 += dZ2^T A1
-    fsync();
-    // ---- what used to be the second pass
-    stage_rows_T(A.x, rb * FR, A.Q, tv, lane);  // X^T over dZ2 (its first 32 rows)
-    FChunk d1;
-    chunk_zero(d1);
-    facc<4, 16>(d1.a, wl2, 16, 0, 0, lane, [&](int s, int k) { return d2.a[k >> 2][s][k & 3]; });
-    chunk_mul_grad_T<ACT>(d1, tu, lane);
-    fsync();
-    chunk_to_T(tu, d1, lane);  // dZ1 (A1 is consumed)
-    fsync();
-    pb1 += row_sum_T(tu, lane);
-    wgrad_T<4, 2>(aW1, tu, tv, lane);  // dW1 += dZ1^T X
-    fsync();
-  }
-  wg_tree_sum<BW3>(aW2, aW3, pb2, pbo, wg_lds, wv, lane);
-  {
-    f4 none[1][1] = {{f4{0.f, 0.f, 0.f, 0.f}}};
-    float unused = 0.f;
-    wg_tree_sum<BW3>(aW1, none, pb1, unused, wg_lds, wv, lane);
-  }
-  if (wv != 0) return;
-  float* slab = A.slab + (size_t)blockIdx.x * A.P;
-  wgrad_flush<2, 4>(aW3, slab + A.poff[4], A.nout, A.h2, 0, 0, lane);
-  wgrad_flush<4, 4>(aW2, slab + A.poff[2], A.h2, A.h1, 0, 0, lane);
-  wgrad_flush<4, 2>(aW1, slab + A.poff[0], A.h1, A.in, 0, 0, lane);
-  if (lane < A.h1) slab[A.poff[1] + lane] = pb1;
-  if (lane < A.h2) slab[A.poff[3] + lane] = pb2;
-  if (lane < A.nout) slab[A.poff[5] + lane] = pbo;
+#define KR_BODY_BWD3
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_BWD3
+#undef KR_BX
+#undef KR_NBX
 }
 
 template <int ACT>
@@ -1285,92 +1099,13 @@ constexpr int B2_LDS = (32 + 64) * TP;                    // floats per wavefron
 constexpr int B2_FRAG = 4 * 8 * 64 + 4 * 8 * 64 + 4 * 4 * 64;  // W1 chunk, W2^T chunk, bias chunk
 template <int ACT>
 __global__ __launch_bounds__(64 * WPB, 2) void mlp_bwd2_kernel(const FusedArgs A) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* const ts = wg_lds + wv * B2_LDS;  // X^T, then dOUT^T, then X^T again
-  float* const tu = ts + 32 * TP;          // A1
-  float* const tv = tu;                    // dZ1 (A1 is consumed when it is written)
-  float* const wl0 = wg_lds + WPB * B2_LDS;
-  float* const wl1 = wl0 + 4 * 8 * 64;
-  float* const bl = wl1 + 4 * 8 * 64;
-  const int64_t nblk = (A.Q + FR - 1) / FR;
-  const int nchunk = A.c1;
-  const int chunk = blockIdx.x % nchunk;
-  const int64_t group = blockIdx.x / nchunk, ngroups = gridDim.x / nchunk;
-  {
-    const f4* s0 = reinterpret_cast<const f4*>(A.wf[0] + (size_t)4 * chunk * 8 * 64);
-    const f4* s1 = reinterpret_cast<const f4*>(A.wt[1] + (size_t)4 * chunk * 8 * 64);
-    const f4* s2 = reinterpret_cast<const f4*>(A.bfr[0] + (size_t)4 * chunk * 4 * 64);
-    f4* d0 = reinterpret_cast<f4*>(wl0);
-    f4* d1 = reinterpret_cast<f4*>(wl1);
-    f4* d2 = reinterpret_cast<f4*>(bl);
-    for (int i = threadIdx.x; i < 512; i += 64 * WPB) { d0[i] = s0[i]; d1[i] = s1[i]; }
-    for (int i = threadIdx.x; i < 256; i += 64 * WPB) d2[i] = s2[i];
-  }
-  __syncthreads();
-  f4 aW1[4][2], aWo[2][4];
-#pragma unroll
-  for (int o = 0; o < 4; ++o)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) aW1[o][i] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int o = 0; o < 2; ++o)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) aWo[o][i] = f4{0.f, 0.f, 0.f, 0.f};
-  float pb1 = 0.f, pbo = 0.f;
-  // the rows of X and dOUT of a block are requested while the previous block finishes (registers: the fragments in the
-  // LDS freed 45 of them); X is staged twice from the same registers
-  f4 xr[RNV], dr[RNV];
-  {
-    const int64_t rb = group * WPB + wv;
-    rows_request(xr, A.x, rb * FR, rb < nblk ? A.Q : 0, lane);
-    rows_request(dr, A.dout, rb * FR, rb < nblk ? A.Q : 0, lane);
-  }
-  for (int64_t rb = group * WPB + wv; rb < nblk; rb += ngroups * WPB) {
-    rows_to_T(xr, ts, lane);
-    fsync();
-    {
-      FChunk h1;
-      float bin[FT][8];
-      load_bops_T(bin, ts, lane);
-      chunk_set_bias(h1, bl, 0, lane);
-      facc<4, 8>(h1.a, wl0, 8, 0, 0, lane, [&](int s, int k) { return bin[s][k]; });
-      fsync();
-      rows_to_T(dr, ts, lane);
-      chunk_act_only<ACT>(h1);
-      chunk_to_T(tu, h1, lane);  // A1 chunk
-    }
-    fsync();
-    if (chunk == 0 && lane < 32) pbo += row_sum_T(ts, lane);
-    wgrad_T<2, 4>(aWo, ts, tu, lane);  // dW2[:, chunk] += dOUT^T A1
-    // dZ1 = (W2^T[chunk] dOUT) * act'(Z1)
-    FChunk d1;
-    chunk_zero(d1);
-    {
-      float bd[FT][8];
-      load_bops_T(bd, ts, lane);
-      facc<4, 8>(d1.a, wl1, 8, 0, 0, lane, [&](int s, int k) { return bd[s][k]; });
-    }
-    chunk_mul_grad_T<ACT>(d1, tu, lane);
-    fsync();
-    rows_to_T(xr, ts, lane);
-    {
-      const int64_t rn = rb + ngroups * WPB;
-      rows_request(xr, A.x, rn * FR, rn < nblk ? A.Q : 0, lane);
-      rows_request(dr, A.dout, rn * FR, rn < nblk ? A.Q : 0, lane);
-    }
-    chunk_to_T(tv, d1, lane);
-    fsync();
-    pb1 += row_sum_T(tv, lane);
-    wgrad_T<4, 2>(aW1, tv, ts, lane);  // dW1[chunk] += dZ1^T X
-    fsync();
-  }
-  wg_tree_sum(aW1, aWo, pb1, pbo, wg_lds, wv, lane);
-  if (wv != 0) return;
-  float* slab = A.slab + (size_t)group * A.P;  // one slab per group of row-block streams; its chunks write disjoint parts
-  wgrad_flush<2, 4>(aWo, slab + A.poff[2], A.nout, A.h1, 0, 64 * chunk, lane);
-  wgrad_flush<4, 2>(aW1, slab + A.poff[0], A.h1, A.in, 64 * chunk, 0, lane);
-  if (64 * chunk + lane < A.h1) slab[A.poff[1] + 64 * chunk + lane] = pb1;
-  if (chunk == 0 && lane < A.nout) slab[A.poff[3] + lane] = pbo;
+#define KR_BODY_BWD2
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_BWD2
+#undef KR_BX
+#undef KR_NBX
 }
 
 // dW[k] += sum over the slabs.  Thread (parameter i, group g) adds up the slabs g, g + RG, g + 2 RG, ... (consecutive
@@ -1431,133 +1166,119 @@ struct TailArgs {
   float* wt[3];
 };
 constexpr int TAIL_T = 1024, TAIL_G = TAIL_T / 16;  // threads of a workgroup, slab groups (16 lanes x 16 bytes = 64 parameters each)
+// What changes from epoch to epoch in a tail launch.  train_tail_kernel reads it from its TailArgs; the bank kernel gets
+// ONE for all its networks by value (the per-network TailArgs live in device memory, written once).
+struct TailStep {
+  int parity;
+  float inv_bc1, b1, b2, inv_sqrt_bc2, eps, wd;
+  double factor, threshold, min_lr;
+  int patience;
+  float* loss_log;
+};
 __global__ __launch_bounds__(TAIL_T) void train_tail_kernel(const TailArgs T) {
-  __shared__ __attribute__((aligned(16))) float red[TAIL_G][64];
-  __shared__ float lred[TAIL_T];
-  const int tid = threadIdx.x, c0 = blockIdx.x * 64;
-  // the optimizer state of this workgroup's parameters is requested first, so that it travels with the slabs
-  float g_in = 0.f, p_in = 0.f, m_in = 0.f, v_in = 0.f, lo_in = 0.f;
-  if (tid < 64 && c0 + tid <= T.nparams) {
-    g_in = T.g[c0 + tid];
-    if (T.update && c0 + tid < T.nparams) {
-      p_in = T.p[c0 + tid];
-      m_in = T.m[c0 + tid];
-      v_in = T.v[c0 + tid];
-      if (T.lower) lo_in = T.lower[c0 + tid];
-    }
-  }
-  {
-    const int l16 = tid & 15, sg = tid >> 4;
-    f4 a0 = f4{0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-    if (c0 + 4 * l16 < T.P) {
-      const float* src = T.slab + c0 + 4 * l16;
-      int w = sg;
-      for (; w + 3 * TAIL_G < T.nslab; w += 4 * TAIL_G) {
-        const f4 v0 = *reinterpret_cast<const f4*>(src + (size_t)w * T.P);
-        const f4 v1 = *reinterpret_cast<const f4*>(src + (size_t)(w + TAIL_G) * T.P);
-        const f4 v2 = *reinterpret_cast<const f4*>(src + (size_t)(w + 2 * TAIL_G) * T.P);
-        const f4 v3 = *reinterpret_cast<const f4*>(src + (size_t)(w + 3 * TAIL_G) * T.P);
-        a0 = a0 + v0; a1 = a1 + v1; a2 = a2 + v2; a3 = a3 + v3;
-      }
-      for (; w < T.nslab; w += TAIL_G) a0 = a0 + *reinterpret_cast<const f4*>(src + (size_t)w * T.P);
-    }
-    *reinterpret_cast<f4*>(&red[sg][4 * l16]) = (a0 + a1) + (a2 + a3);
-  }
-  const bool loss_blk = T.nparams >= c0 && T.nparams < c0 + 64;  // (uniform over the workgroup)
-  float lsum = 0.f;
-  if (loss_blk && T.nlpart > 0) {
-    for (int j = tid; j < T.nlpart; j += TAIL_T) lsum += T.lpart[j];
-    lred[tid] = lsum;
-  }
-  __syncthreads();
-  if (loss_blk && T.nlpart > 0) {
-    for (int o = TAIL_T / 2; o > 0; o >>= 1) {
-      if (tid < o) lred[tid] += lred[tid + o];
-      __syncthreads();
-    }
-    lsum = lred[0];
-  }
-  if (T.nslab > 0) {  // 64 x TAIL_G partial sums -> 64 x 4 (every thread of the first four wavefronts adds sixteen)
-    float part = 0.f;
-    if (tid < 256) {
-#pragma unroll
-      for (int k = 0; k < TAIL_G / 4; ++k) part += red[(tid >> 6) * (TAIL_G / 4) + k][tid & 63];
-    }
-    __syncthreads();
-    if (tid < 256) red[tid >> 6][tid & 63] = part;
-    __syncthreads();
-  }
-  if (tid >= 64) return;
-  const int i = c0 + tid;
-  if (i > T.nparams) return;
-  if (i == T.nparams) {  // the loss slot
-    const float cur_f = g_in + lsum;
-    if (!T.update) {
-      T.g[i] = cur_f;
-      return;
-    }
-    const double lr = T.sched[T.parity];
-    const double cur = (double)cur_f;
-    double best = T.sched[2], bad = T.sched[3], nred = T.sched[5];
-    if (cur < best * (1.0 - T.threshold)) { best = cur; bad = 0.0; }
-    else bad += 1.0;
-    double next = lr;
-    if (bad > (double)T.patience) {
-      const double cand = fmax(lr * T.factor, T.min_lr);
-      if (lr - cand > 1e-8) { next = cand; nred += 1.0; }
-      bad = 0.0;
-    }
-    T.sched[T.parity ^ 1] = next;
-    T.sched[2] = best; T.sched[3] = bad; T.sched[4] = cur; T.sched[5] = nred;
-    if (T.loss_log) *T.loss_log = cur_f;
-    T.g[i] = 0.f;
-    return;
-  }
-  float gi = g_in;
-  if (T.nslab > 0) gi += (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-  if (!T.update) {
-    T.g[i] = gi;
-    return;
-  }
-  float pi = p_in;
-  {
-    const float step_size = (float)(T.sched[T.parity] * (double)T.inv_bc1);
-    if (T.wd != 0.f) gi = fmaf(T.wd, pi, gi);
-    const float mi = fmaf(T.b1, m_in, (1.f - T.b1) * gi);
-    const float vi = fmaf(T.b2, v_in, (1.f - T.b2) * gi * gi);
-    T.m[i] = mi;
-    T.v[i] = vi;
-    const float denom = sqrtf(vi) * T.inv_sqrt_bc2 + T.eps;
-    pi -= step_size * (mi / denom);
-    if (T.lower) pi = fmaxf(pi, lo_in);
-    T.p[i] = pi;
-    T.g[i] = 0.f;
-  }
-  int seg = 0;
-#pragma unroll
-  for (int k = 1; k < 6; ++k)
-    if (i >= T.poff[k]) seg = k;
-  const int k = seg >> 1, r = i - T.poff[seg];
-  if (seg & 1) {  // bias b_k[u]: bf[(t*4 + r4)*64 + lane] = b[16 t + 4 (lane >> 4) + r4] for the sixteen lanes of a quad
-    const int u = r;
-    float* dst = T.bf[k] + ((size_t)(u >> 4) * 4 + (u & 3)) * 64 + 16 * ((u & 15) >> 2);
-#pragma unroll
-    for (int c = 0; c < 16; ++c) dst[c] = pi;
-  } else {
-    const int in = T.in[k], uo = r / in, ui = r - uo * in;
-    {
-      const int sfw = k == 0 ? ui >> 2 : 4 * (ui >> 4) + (ui & 3);
-      const int q = k == 0 ? ui & 3 : (ui & 15) >> 2;
-      const int lane = 16 * q + (uo & 15);
-      T.wf[k][(((size_t)(uo >> 4) * (T.ks[k] >> 2) + (sfw >> 2)) * 64 + lane) * 4 + (sfw & 3)] = pi;
-    }
-    if (k > 0) {
-      const int st = T.natural[k] ? uo >> 2 : 4 * (uo >> 4) + (uo & 3);
-      const int q = T.natural[k] ? uo & 3 : (uo & 15) >> 2;
-      const int lane = 16 * q + (ui & 15);
-      T.wt[k][(((size_t)(ui >> 4) * (T.kst[k] >> 2) + (st >> 2)) * 64 + lane) * 4 + (st & 3)] = pi;
-    }
-  }
+#define KR_BODY_TAIL
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#define KR_TE T
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_TAIL
+#undef KR_BX
+#undef KR_NBX
+#undef KR_TE
+}
+
+// ---- bank forms: n_nets independent trainings of ONE network shape in the three launches of an epoch ------------------
+// (kr_train_bank_epochs; reference: physics_multitrain.py:140-157, one physics_train.py process per training.)  Network
+// k = blockIdx.y runs the body of its one-network twin on its own FusedArgs / TailArgs, which sit in device memory, written
+// once when the bank is created.  gridDim.x is sized for the largest network; a network's row blocks are dealt out over ITS
+// OWN number of workgroups - the number fused_mlp_forward / fused_mlp_backward choose for its Q alone - so that every sum
+// it forms has the terms and the order of kr_train_epoch on the same buffers: the results are bit-identical.  Surplus
+// workgroups return as a whole before the body's first barrier and write nothing.  nets[blockIdx.y] is read at a
+// wavefront-uniform address before any store of the kernel: its fields arrive in SGPRs, as kernel arguments do.
+struct BankNet {
+  FusedArgs A;
+  unsigned nfwd, nbwd;  // workgroups of this network's forward / backward decomposition
+};
+__global__ void pack_all_bank_kernel(const PackArgs* __restrict__ packs) {
+  const PackArgs& P = packs[blockIdx.y];  // (plain copies: any decomposition gives the same fragments)
+#define KR_BODY_PACK
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_PACK
+#undef KR_BX
+#undef KR_NBX
+}
+template <int ACT>
+__global__ __launch_bounds__(64 * FW2) void mlp_fwd2_bank_kernel(const BankNet* __restrict__ nets) {
+  const BankNet N = nets[blockIdx.y];
+  if (blockIdx.x >= N.nfwd) return;
+  const FusedArgs& A = N.A;
+#define KR_BODY_FWD2
+#define KR_BX blockIdx.x
+#define KR_NBX N.nfwd
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_FWD2
+#undef KR_BX
+#undef KR_NBX
+}
+template <int ACT>
+__global__ __launch_bounds__(64 * FW3, 1) void mlp_fwd3_bank_kernel(const BankNet* __restrict__ nets) {
+  // (read in place: fwd_rows hands the address of A.lw to the loss, so a local copy would live in scratch memory - the
+  // twin's arguments stay in the kernel-argument segment the same way)
+  const BankNet& N = nets[blockIdx.y];
+  if (blockIdx.x >= N.nfwd) return;
+  const FusedArgs& A = N.A;
+#define KR_BODY_FWD3
+#define KR_BX blockIdx.x
+#define KR_NBX N.nfwd
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_FWD3
+#undef KR_BX
+#undef KR_NBX
+}
+template <int ACT>
+__global__ __launch_bounds__(64 * WPB, 2) void mlp_bwd2_bank_kernel(const BankNet* __restrict__ nets) {
+  const BankNet N = nets[blockIdx.y];
+  if (blockIdx.x >= N.nbwd) return;
+  const FusedArgs& A = N.A;
+#define KR_BODY_BWD2
+#define KR_BX blockIdx.x
+#define KR_NBX N.nbwd
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_BWD2
+#undef KR_BX
+#undef KR_NBX
+}
+template <int ACT>
+__global__ __launch_bounds__(64 * BW3) void mlp_bwd3_bank_kernel(const BankNet* __restrict__ nets) {
+  const BankNet N = nets[blockIdx.y];
+  if (blockIdx.x >= N.nbwd) return;
+  const FusedArgs& A = N.A;
+#define KR_BODY_BWD3
+#define KR_BX blockIdx.x
+#define KR_NBX N.nbwd
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_BWD3
+#undef KR_BX
+#undef KR_NBX
+}
+// the tail's grid depends on the parameter count alone, which the networks of a bank share: no surplus workgroups.
+// T.loss_log of a bank network is the BASE of its log; epoch `log_index` of it is written.
+__global__ __launch_bounds__(TAIL_T) void train_tail_bank_kernel(const TailArgs* __restrict__ nets, const TailStep E,
+                                                                 const long long log_index) {
+  const TailArgs& T = nets[blockIdx.y];
+  TailStep Ek = E;
+  Ek.loss_log = T.loss_log ? T.loss_log + log_index : nullptr;
+#define KR_TE Ek
+#define KR_BODY_TAIL
+#define KR_BX blockIdx.x
+#define KR_NBX gridDim.x
+#include "kr_mlp_fused_bodies.inc"
+#undef KR_BODY_TAIL
+#undef KR_BX
+#undef KR_NBX
+#undef KR_TE
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
@@ -1571,6 +1292,20 @@ bool fused_mlp_supported(int n_layers, const int32_t* dims, const int32_t* acts,
   if (acts[n_layers - 1] != KR_ACT_NONE) return false;
   if (n_layers == 3 && (dims[1] > 64 || dims[2] > 64 || acts[0] != acts[1])) return false;
   return true;
+}
+
+// How an epoch's kernels split the row blocks of ONE network (the bank path repeats these choices per network)
+static int fwd_lds_wgs(int64_t nblk, int waves) {  // mlp_fwd2 / mlp_fwd3: one workgroup per CU
+  const int64_t w = (nblk + waves - 1) / waves;
+  return (int)(w < 256 ? w : 256);
+}
+static int bwd3_wgs(int64_t nblk) { return fwd_lds_wgs(nblk, BW3); }
+static int64_t bwd2_groups(int64_t nblk, int nchunk) {  // groups of WPB row-block streams: as many workgroups as the LDS of the chip holds
+  int64_t ngroups = (nblk + WPB - 1) / WPB;
+  const int64_t cap = F_MAXW / WPB / nchunk;
+  if (ngroups > cap) ngroups = cap;
+  if (ngroups < 1) ngroups = 1;
+  return ngroups;
 }
 
 // workspace for the packed fragments (floats)
@@ -1668,7 +1403,7 @@ int fused_mlp_forward(int64_t Q, int n_layers, const int32_t* dims, const int32_
   int nparts = grid;
   int lrc = KR_OK;
   if (n_layers == 3 && dims[3] <= 25) {
-    const int wgs = (int)((nblk + FW3 - 1) / FW3 < 256 ? (nblk + FW3 - 1) / FW3 : 256);  // one workgroup per CU
+    const int wgs = fwd_lds_wgs(nblk, FW3);
     nparts = wgs * FW3;
     launch_by_act(acts[0], [&](auto act) {
       constexpr int a = decltype(act)::value;
@@ -1677,7 +1412,7 @@ int fused_mlp_forward(int64_t Q, int n_layers, const int32_t* dims, const int32_
       hipLaunchKernelGGL((mlp_fwd3_kernel<a>), dim3(wgs), dim3(64 * FW3), lb, s, A);
     });
   } else if (n_layers == 2 && A.c1 <= 8 && dims[2] <= 25) {
-    const int wgs = (int)((nblk + FW2 - 1) / FW2 < 256 ? (nblk + FW2 - 1) / FW2 : 256);
+    const int wgs = fwd_lds_wgs(nblk, FW2);
     nparts = wgs * FW2;
     launch_by_act(acts[0], [&](auto act) {
       constexpr int a = decltype(act)::value;
@@ -1738,7 +1473,7 @@ int fused_mlp_backward(int64_t Q, int n_layers, const int32_t* dims, const int32
     A.nslab = grid3;
     int lrc = KR_OK;
     if (merged_bwd3()) {  // both passes in one launch, one workgroup per CU (kr_train_epoch and, since round 5, kr_mlp_backward)
-      const int wgs = (int)((nblk + BW3 - 1) / BW3 < 256 ? (nblk + BW3 - 1) / BW3 : 256);
+      const int wgs = bwd3_wgs(nblk);
       A.nslab = wgs;
       launch_by_act(acts[0], [&](auto act) {
         constexpr int a = decltype(act)::value;
@@ -1757,11 +1492,7 @@ int fused_mlp_backward(int64_t Q, int n_layers, const int32_t* dims, const int32
     });
     if (lrc) return lrc;
   } else {
-    // groups of WPB row-block streams x hidden chunks: as many workgroups as the LDS of the chip holds
-    int64_t ngroups = (nblk + WPB - 1) / WPB;
-    const int64_t cap = F_MAXW / WPB / nchunk;
-    if (ngroups > cap) ngroups = cap;
-    if (ngroups < 1) ngroups = 1;
+    const int64_t ngroups = bwd2_groups(nblk, nchunk);  // x hidden chunks
     A.nslab = (int)ngroups;
     int lrc = KR_OK;
     launch_by_act(acts[0], [&](auto act) {
@@ -1836,6 +1567,172 @@ int fused_train_epoch(const FusedEpoch& E, hipStream_t s) {
   hipLaunchKernelGGL(train_tail_kernel, dim3(grid), dim3(TAIL_T), 0, s, T);
   KR_HIP(hipGetLastError());
   return KR_OK;
+}
+
+
+// ---- a bank of trainings (kr_train_bank_*) -------------------------------------------------------------------------------
+// One allocation: the three descriptor arrays, then per network (every piece a multiple of 256 bytes) its fragments, the
+// A1 / A2 images of a three-layer network, nslab_k gradient slabs, the forward kernel's loss partials and dout.
+struct FusedBank {
+  int n_nets = 0, n_layers = 0, act = 0, c1 = 0, nparams = 0;
+  unsigned max_fwd = 0, max_bwd = 0;
+  void* mem = nullptr;
+  const BankNet* nets = nullptr;
+  const TailArgs* tails = nullptr;
+  const PackArgs* packs = nullptr;
+  bool packed = false;
+};
+static size_t up256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+
+bool fused_bank_shape_served(int n_layers, const int32_t* dims) {
+  // (what fused_mlp_forward gives to mlp_fwd3_kernel / mlp_fwd2_kernel, whose bank forms exist)
+  return dims[n_layers] == 25 && (n_layers == 3 || (n_layers == 2 && (dims[1] + 63) / 64 <= 8));
+}
+
+int fused_bank_create(int n_nets, const BankNetDesc* nd, int K, int n_layers, const int32_t* dims, const int32_t* acts,
+                      float inv_denom, FusedBank** out) {
+  const int n = n_layers;
+  int P = 0, poff[7];
+  for (int k = 0; k < n; ++k) {
+    poff[2 * k] = P; P += dims[k] * dims[k + 1];
+    poff[2 * k + 1] = P; P += dims[k + 1];
+  }
+  for (int k = 2 * n; k < 7; ++k) poff[k] = P;
+  const int nparams = P, Ppad = (P + 63) & ~63;
+  const int c1 = (dims[1] + 63) / 64, nchunk = n == 2 ? c1 : 1;
+  const size_t frag_b = up256(fused_frag_floats(n, dims) * sizeof(float));
+  const size_t head_b = up256(sizeof(BankNet) * n_nets) + up256(sizeof(TailArgs) * n_nets) + up256(sizeof(PackArgs) * n_nets);
+  struct Split { int64_t nblk; int nfwd, nslab, nbwd; size_t img_b, slab_b, lpart_b, dout_b, off; };
+  std::vector<Split> sp((size_t)n_nets);
+  size_t total = head_b;
+  for (int k = 0; k < n_nets; ++k) {
+    Split& s = sp[(size_t)k];
+    s.nblk = (nd[k].Q + FR - 1) / FR;
+    s.nfwd = fwd_lds_wgs(s.nblk, n == 3 ? FW3 : FW2);
+    s.nslab = n == 3 ? bwd3_wgs(s.nblk) : (int)bwd2_groups(s.nblk, nchunk);
+    s.nbwd = s.nslab * nchunk;
+    s.img_b = n == 3 ? (size_t)s.nblk * 4 * FT * 64 * 16 : 0;
+    s.slab_b = up256((size_t)s.nslab * Ppad * sizeof(float));
+    s.lpart_b = up256((size_t)s.nfwd * (n == 3 ? FW3 : FW2) * sizeof(float));
+    s.dout_b = up256((size_t)nd[k].Q * 32 * sizeof(float));
+    s.off = total;
+    total += frag_b + 2 * s.img_b + s.slab_b + s.lpart_b + s.dout_b;
+  }
+  FusedBank* B = new FusedBank();
+  if (hipMalloc(&B->mem, total) != hipSuccess) {
+    (void)hipGetLastError();
+    delete B;
+    set_error("kr_train_bank_create: could not allocate " + std::to_string(total) + " bytes of device scratch");
+    return KR_E_HIP;
+  }
+  auto fail = [&](int rc) { (void)hipFree(B->mem); delete B; return rc; };
+  if (hipMemset(B->mem, 0, total) != hipSuccess) { set_error("kr_train_bank_create: hipMemset failed"); return fail(KR_E_HIP); }
+  char* mem = static_cast<char*>(B->mem);
+  B->nets = reinterpret_cast<const BankNet*>(mem);
+  B->tails = reinterpret_cast<const TailArgs*>(mem + up256(sizeof(BankNet) * n_nets));
+  B->packs = reinterpret_cast<const PackArgs*>(mem + up256(sizeof(BankNet) * n_nets) + up256(sizeof(TailArgs) * n_nets));
+  std::vector<BankNet> hn((size_t)n_nets);
+  std::vector<TailArgs> ht((size_t)n_nets);
+  std::vector<PackArgs> hp((size_t)n_nets);
+  for (int k = 0; k < n_nets; ++k) {
+    const Split& s = sp[(size_t)k];
+    const BankNetDesc& d = nd[k];
+    const float* W[3];
+    const float* b[3];
+    size_t off = 0;
+    for (int l = 0; l < n; ++l) {
+      W[l] = d.p + off; off += (size_t)dims[l] * dims[l + 1];
+      b[l] = d.p + off; off += (size_t)dims[l + 1];
+    }
+    char* q = mem + s.off;
+    BankNet N{};
+    FusedArgs& A = N.A;
+    PackArgs PA{};
+    if (int rc = fused_pack(A, n, dims, W, b, reinterpret_cast<float*>(q), false, nullptr, &PA)) return fail(rc);
+    A.stamps = nullptr;
+    q += frag_b;
+    if (n == 3) { A.a1d = reinterpret_cast<float*>(q); A.a2d = reinterpret_cast<float*>(q + s.img_b); q += 2 * s.img_b; }
+    A.slab = reinterpret_cast<float*>(q); q += s.slab_b;
+    A.lpart = reinterpret_cast<float*>(q); q += s.lpart_b;
+    float* dout = reinterpret_cast<float*>(q);
+    A.Q = d.Q; A.x = d.x; A.dout = dout; A.ldout = dout;
+    A.lbase = d.base; A.ltarget = d.target_rows; A.lds = d.ds;
+    A.lw = loss_weights(inv_denom, K);
+    for (int j = 0; j < 6; ++j) A.poff[j] = poff[j];
+    A.nparams = nparams; A.P = Ppad; A.nslab = s.nslab;
+    N.nfwd = (unsigned)s.nfwd; N.nbwd = (unsigned)s.nbwd;
+    TailArgs T{};
+    T.slab = A.slab; T.nslab = s.nslab; T.P = Ppad; T.nparams = nparams;
+    T.p = d.p; T.g = d.g; T.m = d.m; T.v = d.v; T.lower = d.lower; T.sched = d.sched;
+    T.loss_log = d.loss_log;
+    T.lpart = A.lpart; T.nlpart = s.nfwd * (n == 3 ? FW3 : FW2);
+    T.update = 1;
+    T.L = n;
+    for (int j = 0; j < 7; ++j) T.poff[j] = poff[j];
+    for (int l = 0; l < n; ++l) {
+      T.in[l] = PA.in[l]; T.out[l] = PA.out[l]; T.ks[l] = PA.ks[l]; T.kst[l] = PA.kst[l]; T.natural[l] = PA.natural[l];
+      T.wf[l] = PA.wf[l]; T.bf[l] = PA.bf[l]; T.wt[l] = PA.wt[l];
+    }
+    hn[(size_t)k] = N; ht[(size_t)k] = T; hp[(size_t)k] = PA;
+    if ((unsigned)s.nfwd > B->max_fwd) B->max_fwd = (unsigned)s.nfwd;
+    if ((unsigned)s.nbwd > B->max_bwd) B->max_bwd = (unsigned)s.nbwd;
+  }
+  if (hipMemcpy(const_cast<BankNet*>(B->nets), hn.data(), sizeof(BankNet) * n_nets, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(const_cast<TailArgs*>(B->tails), ht.data(), sizeof(TailArgs) * n_nets, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(const_cast<PackArgs*>(B->packs), hp.data(), sizeof(PackArgs) * n_nets, hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("kr_train_bank_create: upload of the network descriptors failed");
+    return fail(KR_E_HIP);
+  }
+  B->n_nets = n_nets; B->n_layers = n; B->act = acts[0]; B->c1 = c1; B->nparams = nparams;
+  *out = B;
+  return KR_OK;
+}
+
+int fused_bank_epochs(FusedBank* B, const BankStep& st, hipStream_t s) {
+  const dim3 gy_pack(64, B->n_nets), gy_fwd(B->max_fwd, B->n_nets), gy_bwd(B->max_bwd, B->n_nets);
+  const dim3 gy_tail((B->nparams + 1 + 63) / 64, B->n_nets);
+  if (!B->packed || st.repack) {
+    hipLaunchKernelGGL(pack_all_bank_kernel, gy_pack, dim3(256), 0, s, B->packs);
+    KR_HIP(hipGetLastError());
+    B->packed = true;
+  }
+  int lrc = KR_OK;
+  for (int64_t e = 0; e < st.n_epochs && !lrc; ++e) {
+    launch_by_act(B->act, [&](auto act) {
+      constexpr int a = decltype(act)::value;
+      if (B->n_layers == 3) {  // (always the one-pass backward kernel, the default of kr_train_epoch)
+        const size_t lf = sizeof(float) * (FW3_FRAG + FW3 * FW3_WAVE), lb = sizeof(float) * (BW3 * BW3_LDS + B3A_WT + B3B_WT);
+        if ((lrc = dyn_lds(reinterpret_cast<const void*>(&mlp_fwd3_bank_kernel<a>), lf))) return;
+        if ((lrc = dyn_lds(reinterpret_cast<const void*>(&mlp_bwd3_bank_kernel<a>), lb))) return;
+        hipLaunchKernelGGL((mlp_fwd3_bank_kernel<a>), gy_fwd, dim3(64 * FW3), lf, s, B->nets);
+        hipLaunchKernelGGL((mlp_bwd3_bank_kernel<a>), gy_bwd, dim3(64 * BW3), lb, s, B->nets);
+      } else {
+        const size_t lf = sizeof(float) * ((size_t)B->c1 * (4096 + 64) + 32 + FW2 * FW2_OUT);
+        const size_t lb = sizeof(float) * (WPB * B2_LDS + B2_FRAG);
+        if ((lrc = dyn_lds(reinterpret_cast<const void*>(&mlp_fwd2_bank_kernel<a>), lf))) return;
+        if ((lrc = dyn_lds(reinterpret_cast<const void*>(&mlp_bwd2_bank_kernel<a>), lb))) return;
+        hipLaunchKernelGGL((mlp_fwd2_bank_kernel<a>), gy_fwd, dim3(64 * FW2), lf, s, B->nets);
+        hipLaunchKernelGGL((mlp_bwd2_bank_kernel<a>), gy_bwd, dim3(64 * WPB), lb, s, B->nets);
+      }
+    });
+    if (lrc) return lrc;
+    const int64_t step = st.step + e;
+    TailStep E{};
+    E.parity = (int)((step - 1) & 1);
+    const double bc1 = 1.0 - std::pow(st.beta1, (double)step), bc2 = 1.0 - std::pow(st.beta2, (double)step);
+    E.inv_bc1 = (float)(1.0 / bc1); E.b1 = (float)st.beta1; E.b2 = (float)st.beta2;
+    E.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2)); E.eps = (float)st.eps; E.wd = (float)st.weight_decay;
+    E.factor = st.factor; E.threshold = st.threshold; E.min_lr = st.min_lr; E.patience = st.patience;
+    hipLaunchKernelGGL(train_tail_bank_kernel, gy_tail, dim3(TAIL_T), 0, s, B->tails, E, (long long)(st.log_offset + e));
+    KR_HIP(hipGetLastError());
+  }
+  return lrc;
+}
+
+void fused_bank_destroy(FusedBank* B) {
+  if (!B) return;
+  if (B->mem) (void)hipFree(B->mem);
+  delete B;
 }
 
 }  // namespace kr

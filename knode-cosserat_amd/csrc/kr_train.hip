@@ -16,9 +16,12 @@
 // segment ("y and z are not updated here", cosserat_ode_torch.py:391), so d loss / d theta flows only
 // through the MLP output: training = elementwise physics (forward only) + MLP forward/backward.
 #include <cmath>
+#include <string>
+#include <vector>
 
 #include "kr_internal.hpp"
 #include "kr_loss_device.hpp"
+#include "kr_train_bank.hpp"
 
 namespace kr {
 
@@ -740,6 +743,103 @@ int kr_train_epochs(kr_handle* h, int64_t n_epochs, int64_t S, int K, int n_laye
                                   threshold, min_lr, loss_log ? loss_log + e : nullptr, 0, e == 0 ? repack : 0, stream);
     if (rc) return rc;
   }
+  return KR_OK;
+}
+
+// ---- a bank of trainings -------------------------------------------------------------------------------------------------
+struct kr_train_bank {
+  kr::FusedBank* fb = nullptr;
+  int device = 0;
+};
+
+static int bank_error(int code, int net, const std::string& rule) {
+  set_error("kr_train_bank: " + (net >= 0 ? "network " + std::to_string(net) + ": " : std::string()) + rule);
+  return code;
+}
+
+int kr_train_bank_check(int n_nets, const kr_train_bank_net* nets_host, int K, int n_layers, const int32_t* dims,
+                        const int32_t* acts, int in_pad, double denom) {
+  if (n_nets < 1) return bank_error(KR_E_ARG, -1, "n_nets must be at least 1");
+  if (n_nets > 65535) return bank_error(KR_E_UNSUPPORTED, -1, "at most 65535 networks ride in one launch (gridDim.y)");
+  if (!nets_host) return bank_error(KR_E_ARG, -1, "null pointer argument: nets_host");
+  if (K < 1) return bank_error(KR_E_ARG, -1, "K (key points per window step) must be at least 1");
+  if (!(denom > 0)) return bank_error(KR_E_ARG, -1, "denom must be positive");
+  if (n_layers < 1 || n_layers > KR_MAX_LAYERS || !dims || !acts) return bank_error(KR_E_ARG, -1, "n_layers out of range, or null dims / acts");
+  for (int k = 0; k <= n_layers; ++k)
+    if (dims[k] <= 0) return bank_error(KR_E_ARG, -1, "bad layer width");
+  if (n_layers != 2 && n_layers != 3)
+    return bank_error(KR_E_UNSUPPORTED, -1, "networks of " + std::to_string(n_layers) + " layers are not served (two or three: the "
+                      "generic GEMM path has no bank form)");
+  if (in_pad != 32) return bank_error(KR_E_UNSUPPORTED, -1, "in_pad must be 32 (the 28-wide MLP input, no input history)");
+  if (acts[n_layers - 1] != KR_ACT_NONE) return bank_error(KR_E_UNSUPPORTED, -1, "an activation after the last layer is not served");
+  if (dims[0] > 32) return bank_error(KR_E_UNSUPPORTED, -1, "at most 32 inputs");
+  if (dims[n_layers] != 25) return bank_error(KR_E_UNSUPPORTED, -1, "the last layer must have the rod's 25 outputs");
+  if (n_layers == 3 && (dims[1] > 64 || dims[2] > 64))
+    return bank_error(KR_E_UNSUPPORTED, -1, "three-layer networks need H1, H2 <= 64");
+  if (n_layers == 3 && acts[0] != acts[1]) return bank_error(KR_E_UNSUPPORTED, -1, "one activation for both hidden layers");
+  if (n_layers == 2 && dims[1] > 512) return bank_error(KR_E_UNSUPPORTED, -1, "two-layer networks need H1 <= 512");
+  if (!fused_mlp_supported(n_layers, dims, acts, in_pad) || !fused_bank_shape_served(n_layers, dims))
+    return bank_error(KR_E_UNSUPPORTED, -1, "a shape the fused training kernels do not serve");
+  for (int k = 0; k < n_nets; ++k) {
+    const kr_train_bank_net& t = nets_host[k];
+    if (t.S < 1) return bank_error(KR_E_ARG, k, "S must be at least 1 (an empty training is not served)");
+    if (t.S > ((int64_t)1 << 30) / K) return bank_error(KR_E_ARG, k, "need S * K <= 2^30");
+    if (!(t.ds > 0) || !std::isfinite(t.ds)) return bank_error(KR_E_ARG, k, "ds must be positive and finite");
+#define KR_BANK_PTR(f) if (!t.f) return bank_error(KR_E_ARG, k, "null pointer: " #f)
+    KR_BANK_PTR(params); KR_BANK_PTR(grads); KR_BANK_PTR(exp_avg); KR_BANK_PTR(exp_avg_sq); KR_BANK_PTR(sched);
+    KR_BANK_PTR(x); KR_BANK_PTR(base); KR_BANK_PTR(target_rows);
+#undef KR_BANK_PTR
+  }
+  return KR_OK;
+}
+
+int kr_train_bank_create(kr_handle* h, int n_nets, const kr_train_bank_net* nets_host, int K, int n_layers,
+                         const int32_t* dims, const int32_t* acts, int in_pad, double denom, kr_train_bank** out) {
+  KR_CHECK_H(h);
+  KR_CHECK_PTR(out);
+  *out = nullptr;
+  if (int rc = kr_train_bank_check(n_nets, nets_host, K, n_layers, dims, acts, in_pad, denom)) return rc;
+  if (!h->fused_mlp) return bank_error(KR_E_UNSUPPORTED, -1, "the option fused_mlp is off on this handle");
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
+    return bank_error(KR_E_ARG, -1, "the current HIP device is not the one the handle was created on: call hipSetDevice first");
+  std::vector<BankNetDesc> nd((size_t)n_nets);
+  for (int k = 0; k < n_nets; ++k) {
+    const kr_train_bank_net& t = nets_host[k];
+    nd[(size_t)k] = BankNetDesc{t.S * K, (float)t.ds, t.params, t.grads, t.exp_avg, t.exp_avg_sq, t.lower, t.sched,
+                                t.x, t.base, t.target_rows, t.loss_log};
+  }
+  kr_train_bank* b = new kr_train_bank();
+  b->device = dev;
+  if (int rc = fused_bank_create(n_nets, nd.data(), K, n_layers, dims, acts, (float)(1.0 / denom), &b->fb)) {
+    delete b;
+    return rc;
+  }
+  *out = b;
+  return KR_OK;
+}
+
+int kr_train_bank_epochs(kr_handle* h, kr_train_bank* bank, int64_t n_epochs, int64_t step, double beta1, double beta2,
+                         double eps, double weight_decay, double factor, int patience, double threshold, double min_lr,
+                         int64_t log_offset, int repack, void* stream) {
+  KR_CHECK_H(h);
+  KR_CHECK_PTR(bank);
+  if (n_epochs < 0) return bank_error(KR_E_ARG, -1, "n_epochs < 0");
+  if (step < 1) return bank_error(KR_E_ARG, -1, "step counts from 1");
+  if (!(factor > 0.0 && factor < 1.0) || patience < 0) return bank_error(KR_E_ARG, -1, "need 0 < factor < 1, patience >= 0");
+  if (log_offset < 0) return bank_error(KR_E_ARG, -1, "log_offset < 0");
+  if (bank->device != h->device) return bank_error(KR_E_ARG, -1, "the bank belongs to another device than the handle");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc_order_ = order_stream(h, s)) return rc_order_;
+  if (n_epochs == 0 && !repack) return KR_OK;
+  const BankStep st{n_epochs, step, beta1, beta2, eps, weight_decay, factor, threshold, min_lr, patience, log_offset, repack != 0};
+  return fused_bank_epochs(bank->fb, st, s);
+}
+
+int kr_train_bank_destroy(kr_train_bank* bank) {
+  if (!bank) return KR_OK;
+  fused_bank_destroy(bank->fb);
+  delete bank;
   return KR_OK;
 }
 

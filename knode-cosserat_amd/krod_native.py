@@ -55,6 +55,18 @@ class KrDerived(C.Structure):
 _vp = C.c_void_p
 _i64 = C.c_int64
 _int = C.c_int
+_dbl = C.c_double
+
+
+class KrTrainBankNet(C.Structure):
+    """kr_train_bank_net: one training of a bank; every pointer is a device address."""
+    _fields_ = [
+        ("S", C.c_int64), ("ds", C.c_double),
+        ("params", _vp), ("grads", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp),
+        ("lower", _vp), ("sched", _vp), ("x", _vp), ("base", _vp), ("target_rows", _vp), ("loss_log", _vp),
+    ]
+
+
 _PROTOS = {
     "kr_last_error": (C.c_char_p, []),
     "kr_version": (_int, []),
@@ -113,6 +125,12 @@ _PROTOS = {
     "kr_train_epochs": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                C.c_double, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i64, C.c_double,
                                _int, C.c_double, C.c_double, _vp, _int, _vp]),
+    "kr_train_bank_check": (_int, [_int, C.POINTER(KrTrainBankNet), _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _int,
+                                   _dbl]),
+    "kr_train_bank_create": (_int, [_vp, _int, C.POINTER(KrTrainBankNet), _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    _int, _dbl, C.POINTER(_vp)]),
+    "kr_train_bank_epochs": (_int, [_vp, _vp, _i64, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _int, _dbl, _dbl, _i64, _int, _vp]),
+    "kr_train_bank_destroy": (_int, [_vp]),
     "kr_loss_rows_fwd_bwd": (_int, [_vp, _i64, _int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "kr_estimate_ws_bytes": (C.c_size_t, [_i64, _int]),
     "kr_estimate_state": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),

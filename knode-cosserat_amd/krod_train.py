@@ -468,3 +468,236 @@ class KnodeTrainer:
             self.pred[: self.Q, :19] += ds * self.out[: self.Q, :19]   # cosserat_ode_torch.py:386-393: y + ds ys, z as is
             self.pred[: self.Q, 19:] += self.out[: self.Q, 19:25]
         return self.pred[: self.Q].reshape(self.S, self.K, 25).transpose(1, 2)
+
+
+class KnodeBankTrainer:
+    """``len(robots)`` independent one-step-ahead trainings in ONE library call per epoch (``kr_train_bank_epochs``) - the
+    train half of ``physics_multitrain.py:140-157``, which starts one ``physics_train.py`` process per (data set, model
+    variant, seed).  Training k is ``KnodeTrainer(robots[k], trajs[k], controls[k], key_pt_idx, ...)`` bit for bit: its
+    rows come from robot k's own handle (its parameters and its ``ds``), its epoch performs the same arithmetic in the same
+    order, and it has its own learning-rate schedule.
+
+    robots    list of CosseratRodTorch, each with its own ``setup_robot`` modifier and its own ``nn_models`` of ONE structure
+    trajs     list of float32 [M_k, T, 25, N] (T shared, M_k free);  controls  list of float32 [M_k, T, 4]
+
+    Parameters, gradients, moments and schedules are ``[n_nets][...]`` buffers; robot k's ``nn_models`` parameters become
+    views of row k, so checkpoints, ``krod_eval.evaluate`` and ``simulate_batch(..., per_robot_nn=True)`` see the live
+    weights.  Not served (KrError, never a loop over single trainings): robots of differing MLP structure, networks the
+    bank kernels do not take, data-parallel training."""
+
+    def __init__(self, robots, trajs, controls, key_pt_idx, lr=1e-2, weight_decay=0.0, clamp_weights=True,
+                 patience=80, factor=0.5):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise kn.KrError("KnodeBankTrainer: data-parallel bank training is not served (a process group is initialised)")
+        robots = list(robots)
+        if not robots or len(trajs) != len(robots) or len(controls) != len(robots):
+            raise kn.KrError("KnodeBankTrainer: need one trajectory set and one control set per robot, and at least one robot")
+        self.robots = robots
+        self.n_nets = len(robots)
+        self.h = robots[0]._native()
+        self.clamp_weights = clamp_weights
+        self.weight_decay = float(weight_decay)
+        self.patience, self.factor, self.threshold, self.min_lr = int(patience), float(factor), 1e-4, 0.0
+        self.betas, self.adam_eps = (0.9, 0.999), 1e-8
+        self.idx = np.asarray(key_pt_idx, dtype=np.int32)
+        self.K = len(self.idx)
+        dev = trajs[0].device
+        self.idx_t = torch.as_tensor(self.idx, device=dev)
+        # one network structure for all trainings
+        structs = [mlp_structure(r.nn_models) for r in robots]
+        shape = lambda st: ([st[0][0].in_features] + [l.out_features for l, _ in st], [a for _, a in st])
+        dims, acts = shape(structs[0])
+        for k, st in enumerate(structs):
+            if shape(st) != (dims, acts):
+                raise kn.KrError(f"KnodeBankTrainer: robot {k} has layers {shape(st)[0]} / activations {shape(st)[1]}, robot 0 "
+                                 f"{dims} / {acts}: the trainings of a bank share one MLP structure")
+        self.n = len(dims) - 1
+        self.dims_c = (C.c_int32 * (self.n + 1))(*dims)
+        self.acts_c = (C.c_int32 * self.n)(*acts)
+        in_dim = 53 if robots[0].nn_input_history else 28
+        self.in_pad = (in_dim + 31) // 32 * 32
+        # rows of every training, from ITS robot (KnodeTrainer.__init__, physics_train.py:318-333)
+        self.T = int(trajs[0].shape[1])
+        self.steps = self.T - 1
+        self.S, self.x, self.base, self.target_rows = [], [], [], []
+        for k, (rob, tr, ct) in enumerate(zip(robots, trajs, controls)):
+            tr = tr.float().contiguous()
+            ct = ct.float().contiguous()
+            M, T, _, N = tr.shape
+            if T != self.T or N != int(rob.N) or bool(rob.nn_input_history) != bool(robots[0].nn_input_history):
+                raise kn.KrError(f"KnodeBankTrainer: training {k}: T = {T}, N = {N} against T = {self.T}, robot N = {int(rob.N)}")
+            S = M * (T - 1)
+            if S < 1:
+                raise kn.KrError(f"KnodeBankTrainer: training {k} has no window steps")
+            h = rob._native()
+            ys, zs = tr[:, : T - 1, :19], tr[:, : T - 1, 19:]
+            y_prev = torch.cat([ys[:, :1], ys[:, :-1]], dim=1)
+            z_prev = torch.cat([zs[:, :1], zs[:, :-1]], dim=1)
+            yh = (rob.c1 * ys + rob.c2 * y_prev).reshape(S, 19, N).contiguous()
+            zh = (rob.c1 * zs + rob.c2 * z_prev).reshape(S, 6, N).contiguous()
+            target = tr[:, 1:T].reshape(S, 25, N).contiguous()
+            tens = ct[:, : T - 1].reshape(S, 4).contiguous()
+            Q = S * self.K
+            x = torch.empty((Q, self.in_pad), dtype=torch.float32, device=dev)
+            base = torch.empty((Q, 25), dtype=torch.float32, device=dev)
+            rows = torch.empty((Q, 25), dtype=torch.float32, device=dev)
+            kn.check(h.lib.kr_gather_targets(h._h, S, self.K, kn._ptr(target), kn._ptr(self.idx_t), kn._ptr(rows), kn._stream()))
+            kn.check(h.lib.kr_next_segment_physics(h._h, S, self.K, kn._ptr(target), kn._ptr(yh), kn._ptr(zh), kn._ptr(tens),
+                                                   kn._ptr(self.idx_t), kn._ptr(x), self.in_pad, kn._ptr(base), kn.KR_F32,
+                                                   kn._stream()))
+            self.S.append(S); self.x.append(x); self.base.append(base); self.target_rows.append(rows)
+        # stacked optimizer state; robot k's parameters become views of row k
+        self.params = [[p for l, _ in st for p in (l.weight, l.bias)] for st in structs]
+        self.sizes = [int(p.numel()) for p in self.params[0]]
+        n = sum(self.sizes)
+        self.nparams = n
+        nn_ = self.n_nets
+        self.flat_p = torch.empty((nn_, n), dtype=torch.float32, device=dev)
+        self.grads = torch.zeros((nn_, n + 1), dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros((nn_, n), dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros((nn_, n), dtype=torch.float32, device=dev)
+        self.lower = torch.full((nn_, n), float("-inf"), dtype=torch.float32, device=dev)
+        self.sched = torch.tensor([[lr, lr, float("inf"), 0.0, 0.0, 0.0]] * nn_, dtype=torch.float64, device=dev)
+        for k in range(nn_):
+            off = 0
+            for j, (p, sz) in enumerate(zip(self.params[k], self.sizes)):
+                view = self.flat_p[k, off:off + sz].view(p.shape)
+                view.copy_(p.data)
+                p.data = view
+                p.grad = self.grads[k, off:off + sz].view(p.shape)
+                if clamp_weights and j % 2 == 0:
+                    self.lower[k, off:off + sz] = 0.0
+                off += sz
+        self.adam_step = 0
+        self.loss_log = torch.zeros((nn_, 4096), dtype=torch.float32, device=dev)
+        self._bank = None
+        self._repack = True
+        self._param_versions = None
+        self._make_bank()
+
+    def _make_bank(self):
+        """(Re)creates the library's bank over the current buffers; the first epoch call on a bank packs the fragments."""
+        self.close()
+        h = self.h
+        nets = (kn.KrTrainBankNet * self.n_nets)()
+        for k in range(self.n_nets):
+            t = nets[k]
+            t.S, t.ds = self.S[k], float(self.robots[k]._native().derived().ds)
+            t.params, t.grads = self.flat_p[k].data_ptr(), self.grads[k].data_ptr()
+            t.exp_avg, t.exp_avg_sq = self.exp_avg[k].data_ptr(), self.exp_avg_sq[k].data_ptr()
+            t.lower = self.lower[k].data_ptr() if self.clamp_weights else None
+            t.sched = self.sched[k].data_ptr()
+            t.x, t.base, t.target_rows = self.x[k].data_ptr(), self.base[k].data_ptr(), self.target_rows[k].data_ptr()
+            t.loss_log = self.loss_log[k].data_ptr()
+        out = C.c_void_p()
+        kn.check(h.lib.kr_train_bank_create(h._h, self.n_nets, nets, self.K, self.n, self.dims_c, self.acts_c, self.in_pad,
+                                            float(self.steps), C.byref(out)))
+        self._bank = out
+
+    def close(self):
+        """Frees the library's bank (after everything queued on it has finished)."""
+        if getattr(self, "_bank", None) is not None:
+            torch.cuda.synchronize()
+            self.h.lib.kr_train_bank_destroy(self._bank)
+            self._bank = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def weights_changed(self):
+        """Tell the trainer that some parameters were written from outside (a loaded checkpoint): the next epoch packs the
+        kernels' weight fragments of every training afresh."""
+        self._repack = True
+
+    def _epochs(self, n_epochs):
+        if self.adam_step + n_epochs > self.loss_log.shape[1]:  # the log's address is part of the bank: grow both
+            log = torch.zeros((self.n_nets, 2 * (self.adam_step + n_epochs)), dtype=torch.float32, device=self.loss_log.device)
+            log[:, : self.loss_log.shape[1]] = self.loss_log
+            self.loss_log = log
+            self._make_bank()
+        # in-place writes to the parameters from outside bump torch's version counters; the kernels' own updates do not
+        ver = tuple(p._version for ps in self.params for p in ps) + (self.flat_p._version,)
+        if ver != self._param_versions:
+            self._repack = self._repack or self._param_versions is not None
+            self._param_versions = ver
+        h = self.h
+        kn.check(h.lib.kr_train_bank_epochs(h._h, self._bank, n_epochs, self.adam_step + 1, self.betas[0], self.betas[1],
+                                            self.adam_eps, self.weight_decay, self.factor, self.patience, self.threshold,
+                                            self.min_lr, self.adam_step, 1 if self._repack else 0, kn._stream()))
+        self._repack = False
+        self.adam_step += n_epochs
+
+    def step(self, sync_loss=True):
+        """One epoch of every training.  ``sync_loss``: the n_nets losses as floats (one device read), else None."""
+        self._epochs(1)
+        if sync_loss:
+            return self.loss_log[:, self.adam_step - 1].cpu().tolist()
+        return None
+
+    def run(self, n_epochs):
+        """n_epochs epochs of every training queued by ONE library call; nothing waits for the GPU."""
+        if n_epochs > 0:
+            self._epochs(int(n_epochs))
+
+    def losses(self):
+        """[n_nets][epochs]: the loss of every epoch taken so far (one device read)."""
+        return self.loss_log[:, : self.adam_step].cpu().tolist()
+
+    def get_last_lr(self):
+        """The rate each training's NEXT epoch will use (what torch reports after scheduler.step())."""
+        return self.sched[:, self.adam_step & 1].cpu().tolist()
+
+    def optimizer_state_dict(self, k):
+        """Training k's ``torch.optim.Adam.state_dict()``, in the layout ``KnodeTrainer.optimizer_state_dict`` writes."""
+        state, off = {}, 0
+        for j, (p, sz) in enumerate(zip(self.params[k], self.sizes)):
+            if self.adam_step > 0:
+                state[j] = {"step": torch.tensor(float(self.adam_step)),
+                            "exp_avg": self.exp_avg[k, off:off + sz].view(p.shape).clone(),
+                            "exp_avg_sq": self.exp_avg_sq[k, off:off + sz].view(p.shape).clone()}
+            off += sz
+        group = {"lr": self.get_last_lr()[k], "betas": tuple(self.betas), "eps": self.adam_eps,
+                 "weight_decay": self.weight_decay, "amsgrad": False, "maximize": False, "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
+                 "params": list(range(len(self.params[k])))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, k, sd):
+        """Resume training k from an Adam ``state_dict``.  The trainings of a bank share the step count and the Adam
+        constants: load every training from checkpoints of one epoch (a state whose step count differs from the bank's
+        is accepted only while the bank has not taken or loaded a step of its own)."""
+        group = sd["param_groups"][0]
+        if len(group["params"]) != len(self.params[k]):
+            raise kn.KrError("optimizer state does not match the network (number of parameters)")
+        if group.get("amsgrad") or group.get("maximize"):
+            raise kn.KrError("only plain Adam state can be resumed (amsgrad / maximize are not implemented)")
+        steps = set()
+        for j, p in enumerate(self.params[k]):
+            st = sd["state"].get(group["params"][j])
+            steps.add(0 if st is None else int(float(st["step"])))
+            if st is not None and tuple(st["exp_avg"].shape) != tuple(p.shape):
+                raise kn.KrError(f"optimizer state of parameter {j} has shape {tuple(st['exp_avg'].shape)}")
+        if len(steps) != 1:
+            raise kn.KrError("per-parameter step counts differ: not a state the fused Adam can continue")
+        step = steps.pop()
+        if step != self.adam_step and self.adam_step != 0:
+            raise kn.KrError(f"training {k}: the state is at step {step}, the bank at step {self.adam_step}: the trainings of a "
+                             "bank share one step count")
+        if (tuple(group["betas"]), float(group["eps"]), float(group["weight_decay"])) != (tuple(self.betas), self.adam_eps, self.weight_decay):
+            raise kn.KrError(f"training {k}: betas / eps / weight_decay differ from the bank's (they are shared)")
+        off = 0
+        for j, (p, sz) in enumerate(zip(self.params[k], self.sizes)):
+            st = sd["state"].get(group["params"][j])
+            if st is None:
+                self.exp_avg[k, off:off + sz].zero_()
+                self.exp_avg_sq[k, off:off + sz].zero_()
+            else:
+                self.exp_avg[k, off:off + sz].copy_(st["exp_avg"].reshape(-1).to(self.exp_avg))
+                self.exp_avg_sq[k, off:off + sz].copy_(st["exp_avg_sq"].reshape(-1).to(self.exp_avg_sq))
+            off += sz
+        self.sched[k, 0:2] = float(group["lr"])
+        self.adam_step = step
