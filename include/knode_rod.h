@@ -387,6 +387,34 @@ int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_b
                            int ring, void* G, void* tip, double tol, int maxit, int32_t* status,
                            const void* state_prev_init, int dtype, void* stream);
 
+/* ---- per-step tip loads: a wrench history per rod ---------------------- */
+/* Every simulate call above freezes the tip wrench for the whole call (the handle's F_tip / M_tip, or the rod's table
+ * row).  In the reference the wrench is a pair of plain attributes (cosserat_ode.py:28-29) that getResidualEuler reads
+ * at every solve (:206-207): a caller who picks up a payload, pushes against the tip or probes a trained model under a
+ * disturbance assigns robot.F_tip / robot.M_tip between two steps of knode.simulate's loop.  Here that history is a
+ * second time-varying input next to ctl, and the whole experiment - heterogeneous rods included - stays one launch.
+ *
+ * kr_simulate_batch_table with the tip wrench of every rod and step given like ctl:
+ * loads[B][T][6] = F_tip (3), M_tip (3).  The solve of step t (the one that reads ctl[b][t] and writes states[t+1])
+ * uses loads[b][t] in its tip condition r = [F - n(L), M - m(L)] - the reference with robot.F_tip / robot.M_tip
+ * assigned before that solve.  The values REPLACE F_tip / M_tip of the rod's table row (they are not added to them);
+ * everything else of the row is used as in kr_simulate_batch_table.  Element type = dtype, like ctl.  A call cut into
+ * pieces (state_prev_init, keep_predictor) slices loads like ctl.
+ * t is required (KR_E_ARG without it, or without loads): build a table of identical rows when only the loads vary.
+ * Served: exactly what kr_simulate_batch_table serves - one wavefront per rod in one persistent launch; scheme
+ * KR_EULER; 9 <= N <= 128; diagonal material matrices; MLP off (the overlapped kernel with its take-over launch, or
+ * with overlap = 0 the plain persistent kernel) or the handle's MLP where that kernel evaluates it; KR_F32 and KR_F64;
+ * ring, state_prev_init and the options keep_predictor, residual_test, predictor, nn_* as there.  Afterwards
+ * last_sim_path = 2, last_waves_per_rod = 1, last_overlap as for the table call.  Everything the table call refuses is
+ * refused here with KR_E_UNSUPPORTED and a message that names the rule; no output buffer is touched.
+ * NOT served with loads: a network bank, several wavefronts per rod, N > 128, RK4, one launch per step, kr_step_batch
+ * (per-step launches take their wrench from kr_set_params).  A distributed load along the rod and a moving base are
+ * outside this call.  The first call of a shape does the one-time host work kr_simulate_prepare does for
+ * kr_simulate_batch itself. */
+int kr_simulate_batch_loads(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl,
+                            const void* loads, void* states, int ring, void* G, void* tip, double tol, int maxit,
+                            int32_t* status, int use_nn, const void* state_prev_init, int dtype, void* stream);
+
 /* ---- KNODE one-step-ahead training path -------------------------------- */
 /* CosseratRodTorch.parallelGetNextSegmentEuler (cosserat_ode_torch.py:401-437)
  * and, with idx = 1..N-1, getNextSegmentEuler (:370-399), plus the four-term

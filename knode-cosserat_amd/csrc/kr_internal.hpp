@@ -301,6 +301,7 @@ struct PlanQuery {
   const void* prev_init = nullptr;
   const void* states = nullptr;
   int64_t slot_elems = 0;
+  bool loads = false;                  // kr_simulate_batch_loads: a table call with a tip-wrench history
 };
 template <typename T>
 SimPlan plan_simulate(const kr_handle* h, const PlanQuery& q);
@@ -348,6 +349,7 @@ struct SimSrc {
   const kr_param_table* table = nullptr;
   const kr_mlp_bank* bank = nullptr;
   const int32_t* net_idx = nullptr;  // device copy of the caller's index array
+  const void* loads = nullptr;       // kr_simulate_batch_loads: [B][T][6], element type of the call
 };
 template <typename T>
 int launch_step(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);            // kr_sim_*.hip
@@ -372,6 +374,8 @@ int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hi
 template <typename T>
 int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, const int32_t* net_idx, const SimPlan& p,
                     const SimArgs<T>& a, const LaunchAt& at);                                    // kr_bank_*.hip
+template <typename T>
+int launch_load_sim(kr_handle* h, const kr_param_table* t, const T* loads, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_load_*.hip
 int ensure_resume(kr_handle* h, int64_t B);
 int ensure_hist_ws(kr_handle* h, size_t bytes);
 
@@ -386,6 +390,7 @@ inline int launch_sim(kr_handle* h, const SimPlan& p, const SimSrc& src, SimArgs
     if (int rc = ensure_hist_ws(h, p.hist_ws_bytes)) return rc;
     a.hist_ws = static_cast<T*>(h->hist_ws);
   }
+  if (src.loads) return launch_load_sim<T>(h, src.table, static_cast<const T*>(src.loads), p, a, at);
   if (src.bank) return launch_bank_sim<T>(h, src.table, src.bank, src.net_idx, p, a, at);
   if (src.table) return launch_tab_sim<T>(h, src.table, p, a, at);
   switch (p.family) {

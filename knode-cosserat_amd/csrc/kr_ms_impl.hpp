@@ -1638,6 +1638,9 @@ constexpr int MS_NPL = 2;  // grid points per lane held in registers by the pers
 // kr_tab_impl.hpp); see rod_src_row (rod_device.hpp).
 // MSRC: the network is the kernel argument itself (MlpDev<T>, one network for every rod) or the rod's entry of a bank
 // (MlpBank<T>, kr_bank_impl.hpp); see mlp_src_net.
+// PSRC = RodTableLoads<T> (kr_load_impl.hpp): the tip wrench of step t is loads[rod][t] - six lanes put it where the
+// cold block keeps F_tip / M_tip before the step's first sweep (every reader of the wrench - the sweeps, the retry from
+// the warm start, the damped fallback - reads that block), once per step and outside the sweeps.
 template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1, typename PSRC = RodConst<T>, typename MSRC = MlpDev<T>>
 __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC Pa, const SimArgs<T> A, const MSRC Ma) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1710,6 +1713,15 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
   T tens[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) tens[k] = ctl[t0 * 4 + k];
+  constexpr bool LOADS = rod_src_has_loads<T, PSRC>::value;
+  const T* wrench = nullptr;  // loads only: [T_steps][6] of this rod
+  T wnext = T(0);             // ... lanes 0..5: the wrench of the coming step, requested one step ahead like the tensions
+  if constexpr (LOADS) {
+    wrench = Pa.loads + rod * A.T_steps * 6;
+    if constexpr (!NN) {
+      if (lane < 6) wnext = wrench[t0 * 6 + lane];
+    }
+  }
   wave_sync();
 
   MsStamps stamps;
@@ -1731,6 +1743,12 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
       A.dbg[A.B * 24 + 2 * t + 1] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
+    // (MLP on: every register that lives across a solve is a spilled one there, so the step's wrench is requested here,
+    //  under the history records, instead of a step ahead - against sweeps of ~300 k cycles the wait does not show)
+    T wcur = wnext;
+    if constexpr (LOADS && NN) {
+      if (lane < 6) wcur = wrench[t * 6 + lane];
+    }
     // ---- history records from c12 (newest) and regP (the one before) ----------
 #pragma unroll
     for (int q = 0; q < MS_NPL; ++q) {
@@ -1753,6 +1771,14 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
     if (t + 1 < A.T_steps) {  // next step's tensions: issued now, consumed after this step's solve
 #pragma unroll
       for (int k = 0; k < 4; ++k) tens[k] = ctl[(t + 1) * 4 + k];
+    }
+    if constexpr (LOADS) {  // (the fences of the start values below stand between this store and the first sweep)
+      if (lane < 6) {
+        L.cold[CD_FTIP + lane] = wcur;  // F_tip (3) and M_tip (3) are adjacent
+        if constexpr (!NN) {
+          if (t + 1 < A.T_steps) wnext = wrench[(t + 1) * 6 + lane];
+        }
+      }
     }
     const int64_t inx = A.ring ? (t + 1) % 3 : t + 1;
     S.out_rod = A.states + inx * A.slot_elems + rod * rod_elems;

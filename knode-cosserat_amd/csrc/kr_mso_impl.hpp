@@ -204,6 +204,12 @@ struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 
 // runs two rods on every SIMD, whose issue-bound sweeps and latency-bound algebra overlap (as kr_ms_impl.hpp's OCC).
 // PSRC: where a rod's constants come from - the kernel argument itself (RodConst<T>, all rods alike) or a per-rod
 // table (RodTable<T>, kr_tab_impl.hpp); see rod_src_row (rod_device.hpp).
+// PSRC = RodTableLoads<T> (kr_load_impl.hpp): the tip wrench of step t is loads[rod][t].  A merged sweep holds two time
+// levels - the verifying lanes close step tA - 1 against ITS wrench while the forward-difference lanes condense step tA -
+// so there are two sets of six slots, step t's in set t & 1: set 0 is the cold block's own F_tip / M_tip, set 1 lies in
+// the part of the record area this kernel leaves unused (it keeps 12 of a record's HS slots, the odd tile).  Every read
+// of the wrench names the step it belongs to (cold_of), so a rejected verification, the rebuild, a plain step and a chord
+// update find their step's values whatever sweep they run in; a set is written once per step, at the hand-over.
 template <typename T, bool DIAG, int HS, int OCC = 1, typename PSRC = RodConst<T>>
 __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC Pa, const SimArgs<T> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -272,6 +278,17 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     }
     wave_sync();
   };
+  constexpr bool LOADS = rod_src_has_loads<T, PSRC>::value;
+  static_assert(!LOADS || HS >= 18, "the second wrench set lives behind the odd tile in the record area");
+  // the cold block as step t sees it: L.cold itself, or (loads, odd t) moved so that CD_FTIP .. + 5 fall on the second set
+  // (offset arithmetic like lead_of; only the six wrench slots may be read through it)
+  const ptrdiff_t wr_d = LOADS ? (L.hist + (size_t)N * 12) - (L.cold + CD_FTIP) : 0;
+  auto cold_of = [&](int t) -> const T* {
+    if constexpr (LOADS) return L.cold + (ptrdiff_t)(t & 1) * wr_d;
+    else return L.cold;
+  };
+  const T* wrench = nullptr;  // loads only: [T_steps][6] of this rod
+  if constexpr (LOADS) wrench = Pa.loads + rod * A.T_steps * 6;
   const T* ctl = A.ctl + rod * A.T_steps * 4;
   auto load_fc = [&](int t) -> V3<T> {  // rhoA g + tendon force of step t (cosserat_ode.py:151,195)
     V3<T> tf{T(0), T(0), T(0)};
@@ -336,6 +353,13 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   // the hand-over of a step and the sweep that follows)
   V3<T> fcA = load_fc(0), fcB = fcA;
   V3<T> fcN = load_fc(T_steps > 1 ? 1 : 0);
+  T wN = T(0);  // loads, lanes 0..5: the wrench of step tA + 1, requested like fcN
+  if constexpr (LOADS) {
+    if (lane < 6) {
+      L.cold[CD_FTIP + lane] = wrench[lane];  // step 0 (set 0; the fences of the start values below come before any read)
+      wN = wrench[(size_t)(T_steps > 1 ? 1 : 0) * 6 + lane];
+    }
+  }
   // av = hk_a + hk_b v_h, au = hk_c u_h (diagonal material matrices): kept in registers so that forming a history
   // record inside a sweep does not go back to the parameter table
   static_assert(DIAG, "the in-sweep history record assumes diagonal material matrices");
@@ -702,7 +726,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       } else if (ln < 3 * MS_YP + 6) {
         const int k = ln - 3 * MS_YP;
         const T e = EsB[(MS_P - 1) * MS_YP + 7 + k];
-        rn = update_ratio(L.cold[CD_FTIP + k] - e, e);
+        rn = update_ratio(cold_of(tB)[CD_FTIP + k] - e, e);
       }
       rn = wave_max_nonneg(rn);
 #ifdef KR_MS_STAMPS
@@ -743,7 +767,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
             areg[g] = e0 - ynext + part;
             if (kp == 0) ach[(g + 1) * MS_YP + r] = areg[g];
           } else if (kp == 0 && r >= 7 && r < 13) {
-            rt[r - 7] = L.cold[CD_FTIP + (r - 7)] - e0 - part;
+            rt[r - 7] = cold_of(tB)[CD_FTIP + (r - 7)] - e0 - part;
           }
           wave_sync_lds();
         }
@@ -831,6 +855,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         rsA = a_ring ? (rsA == 0 ? 2 : rsA - 1) : rsA - 1;
         fcN = fcA;
         fcA = fcB;
+        if constexpr (LOADS) {  // (set tA & 1 still holds this step's wrench; the next hand-over writes the other set again)
+          if (lane < 6) wN = wrench[(size_t)(tA + 1 < T_steps ? tA + 1 : tA) * 6 + lane];
+        }
         order = orderB;
         it = itB;
         dn_prev = ok ? (T)dnv : T(-1);
@@ -869,7 +896,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         }
         wave_sync_lds();
       }
-      res_full = ms_residual_norm<T>(Es, Xs, L.cold, ln);
+      res_full = ms_residual_norm<T>(Es, Xs, cold_of(tA), ln);
       if (isA && col > 0) {
         const T ih = fast_rcp(hstep);
         T e0[19];  // all loads first: the compiler cannot tell that they never alias the stores below
@@ -930,7 +957,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         store_pair(xnext + r * 8 + 2 * kp, n0, n1);
       } else if (r >= 7 && r < 13) {
         // tip rows: [n;m](E_{P-1} + A_{P-1} dY_{P-1}) = [F_tip; M_tip]  ->  row [rhs | T] of T dG = rhs
-        if (kp == 0) n0 = L.cold[CD_FTIP + (r - 7)] - e0 - n0;  // F_tip (3) and M_tip (3) are adjacent
+        if (kp == 0) n0 = cold_of(tA)[CD_FTIP + (r - 7)] - e0 - n0;  // F_tip (3) and M_tip (3) are adjacent
         store_pair(Tm + (r - 7) * 8 + 2 * kp, n0, n1);
       }
       wave_sync_lds();
@@ -1044,6 +1071,14 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       if (tA < T_steps) {
         fcA = fcN;
         fcN = load_fc(tA + 1 < T_steps ? tA + 1 : tA);
+        if constexpr (LOADS) {
+          // the step handed over above keeps set (tA - 1) & 1; the set written here last served step tA - 2, accepted
+          // before this hand-over (the fences of the start values below come before any read)
+          if (lane < 6) {
+            L.cold[CD_FTIP + wr_d * (tA & 1) + lane] = wN;
+            wN = wrench[(size_t)(tA + 1 < T_steps ? tA + 1 : tA) * 6 + lane];
+          }
+        }
         order = Q.next_order;
         ms_pred_guess<T>(Q, order, lane, L.cold, Xs);
         wave_sync_lds();

@@ -73,6 +73,17 @@ struct RodTable {
   const KR_CONSTANT_AS RodConst<T>* rows;
   int N;
 };
+// A table plus a tip-wrench history (kr_simulate_batch_loads, kr_load_impl.hpp): loads[B][T_steps][6] = F_tip (3),
+// M_tip (3) of rod b while it solves step t, in place of Ftip / Mtip of the rod's row.  The pointer rides in the
+// parameter source, i.e. in the kernel arguments of the loads instantiations alone.
+template <typename T>
+struct RodTableLoads : RodTable<T> {
+  const T* loads;
+};
+template <typename T, typename PSRC>
+struct rod_src_has_loads { static constexpr bool value = false; };
+template <typename T>
+struct rod_src_has_loads<T, RodTableLoads<T>> { static constexpr bool value = true; };
 // What a persistent kernel takes as its first argument: the launch-uniform RodConst<T> by value (every rod alike), or a
 // RodTable<T>.  rod_src_row yields the constants of one rod for the kernel's arithmetic: the kernel argument itself,
 // or - table - a local copy of the rod's row, read ONCE, unconditionally, where the kernel starts: scalar loads (the

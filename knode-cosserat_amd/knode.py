@@ -159,6 +159,30 @@ def _robots_networks(robot, robots):
     return networks, net_of_rod
 
 
+def _tip_loads(tip_loads, B, T):
+    """``loads[B, T, 6]`` (float64, contiguous) of ``simulate_batch(..., tip_loads=...)`` from ``[B, T, 6]`` or ``[T, 6]``
+    (one history for all rods); host-side validation only (no device call)."""
+    try:
+        L = np.asarray(tip_loads, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise kn.KrError("simulate_batch: tip_loads must be a numeric array [B, T, 6] or [T, 6]") from None
+    if L.ndim == 2:
+        if L.shape != (T, 6):
+            raise kn.KrError(f"simulate_batch: tip_loads must be [T, 6] = [{T}, 6] (F_tip, M_tip per step); got {L.shape}")
+        L = np.broadcast_to(L[None], (B, T, 6))
+    elif L.ndim == 3:
+        if L.shape[0] != B:
+            raise kn.KrError(f"simulate_batch: tip_loads holds {L.shape[0]} rods, ctl {B}")
+        if L.shape[1:] != (T, 6):
+            raise kn.KrError(f"simulate_batch: tip_loads must be [B, T, 6] = [{B}, {T}, 6] (F_tip, M_tip per step); got {L.shape}")
+    else:
+        raise kn.KrError(f"simulate_batch: tip_loads must be [B, T, 6] or [T, 6]; got shape {L.shape}")
+    if not np.isfinite(L).all():
+        b, t, _ = np.argwhere(~np.isfinite(L))[0]
+        raise kn.KrError(f"simulate_batch: tip_loads is not finite at rod {b}, step {t}")
+    return np.ascontiguousarray(L)
+
+
 def _score_reference(robot, score, B, T, tip_only):
     """``(reference[R, Tr, >=7, N], point)`` of ``simulate_batch(..., score=...)``, R = 1 or B; host-side validation only
     (no device call)."""
@@ -190,7 +214,7 @@ def _score_reference(robot, score, B, T, tip_only):
 
 
 def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
-                   robots=None, per_robot_nn=False, score=None):
+                   robots=None, per_robot_nn=False, score=None, tip_loads=None):
     """B rods, each with its own tension history.
 
     robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
@@ -214,7 +238,20 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     or [B, Tr, >=7, N], Tr <= T + 1; states 0 .. Tr-1 are compared.  The result gains ``dtw`` float64[B], the exact DTW
     distance (L1) of the path of grid point p (default N - 1, the tip - the reference's literal 9 at its N = 10) to the
     reference's, and ``mse`` float64[B], the position + zyx-Euler MSE x 1000 (``krod_eval.dtw_distance`` /
-    ``pos_euler_mse``).  With ``return_states=False`` no trajectory leaves the device."""
+    ``pos_euler_mse``).  With ``return_states=False`` no trajectory leaves the device.
+
+    tip_loads: a tip wrench that varies in time, [B, T, 6] or [T, 6] (shared by all rods): rod b solves step t with
+    F_tip, M_tip = tip_loads[b, t, :3], tip_loads[b, t, 3:] - the reference with ``robot.F_tip`` / ``robot.M_tip``
+    assigned before that solve.  The values replace the robot's own wrench; with ``robots=`` row b keeps everything else.
+    Composes with ``score`` and ``tip_only``; not served with ``per_robot_nn``."""
+    loads = None
+    if tip_loads is not None:  # (validated on the host before anything touches the device)
+        if per_robot_nn:
+            raise kn.KrError("simulate_batch: tip_loads with per_robot_nn=True is not served (per-step tip loads have no network-bank form)")
+        ctl_shape = np.asarray(ctl).shape
+        if len(ctl_shape) != 3:
+            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+        loads = _tip_loads(tip_loads, int(ctl_shape[0]), int(ctl_shape[1]))
     if score is not None:  # (validated on the host before anything touches the device)
         ctl_shape = np.asarray(ctl).shape
         if len(ctl_shape) != 3:
@@ -225,6 +262,8 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     if robots is not None:  # (validated on the host before anything touches the device)
         robots = list(robots)
         rows = _robots_rows(robot, robots, int(np.asarray(ctl).shape[0]))
+    elif loads is not None:  # only the loads vary: a table of identical rows
+        rows = _robots_rows(robot, [robot] * loads.shape[0], loads.shape[0])
     if per_robot_nn:
         if robots is None:
             raise kn.KrError("simulate_batch: per_robot_nn needs robots=[...]")
@@ -243,9 +282,10 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     G = torch.zeros((B, 6), dtype=tdt, device=dev)  # knode.py:67
     tip = torch.empty((B, T, 3), dtype=tdt, device=dev)
     status = torch.zeros((B, T), dtype=torch.int32, device=dev)
+    loads_t = torch.as_tensor(loads, device=dev).to(tdt).contiguous() if loads is not None else None
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
                scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
-               table=table, bank=bank, net_of_rod=net_of_rod)
+               table=table, bank=bank, net_of_rod=net_of_rod, loads=loads_t)
     if score is not None:  # queued behind the run; the copies below wait for both
         Tr = score_ref.shape[1]
         ref_states = h.pack_poses(score_ref, tdt)  # [Tr, 1 or B, N, KR_SLOTS], packed once

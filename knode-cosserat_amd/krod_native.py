@@ -101,6 +101,8 @@ _PROTOS = {
     "kr_param_table_destroy": (_int, [_vp]),
     "kr_state_init_straight_table": (_int, [_vp, _vp, _vp, _int, _vp]),
     "kr_simulate_batch_table": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int, _vp]),
+    "kr_simulate_batch_loads": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int,
+                                       _vp]),
     "kr_mlp_bank_check": (_int, [C.POINTER(KrParams), _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kr_mlp_bank_create": (_int, [_vp, _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _int, _vp,
                                   C.POINTER(_vp)]),
@@ -549,8 +551,21 @@ class Handle:
         check(self.lib.kr_set_option(self._h, name.encode(), int(value)))
 
     def simulate(self, ctl, states, G, ring=False, tip=None, status=None, scheme=KR_EULER, tol=0.0, maxit=0,
-                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None):
+                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None, loads=None):
         B, T = ctl.shape[0], ctl.shape[1]
+        if loads is not None:  # rod b, step t: tip wrench loads[b, t] = F_tip (3), M_tip (3) in place of its row's
+            if bank is not None or net_of_rod is not None:
+                raise KrError("loads= together with bank=: per-step tip loads are not served with a network bank")
+            if table is None:
+                raise KrError("a loads call needs table= (a table of identical rows when only the loads vary)")
+            if B != table.B:
+                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
+            if tuple(loads.shape) != (B, T, 6) or loads.dtype != ctl.dtype or not loads.is_contiguous():
+                raise KrError(f"loads must be a contiguous [{B}, {T}, 6] tensor of {ctl.dtype}; got {tuple(loads.shape)} {loads.dtype}")
+            check(self.lib.kr_simulate_batch_loads(self._h, table._t, T, scheme, _ptr(ctl), _ptr(loads), _ptr(states),
+                                                   int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
+                                                   int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+            return
         if bank is not None or net_of_rod is not None:  # rod b: row b of the table, network net_of_rod[b] of the bank
             if bank is None or net_of_rod is None or table is None:
                 raise KrError("a bank call needs table=, bank= and net_of_rod= together")
