@@ -276,7 +276,15 @@ int kr_residual_mid_batch(kr_handle* h, int64_t B, int scheme, const void* G, co
  * reference's warm start, knode.py:89); 1 / 2 extrapolate the unknowns linearly /
  * quadratically in time from state_cur, state_prev (and state_prev2, may be
  * NULL; it may alias state_next, it is read before anything is written);
- * -1 = the highest order the given states allow (prev == cur means "no history"). */
+ * -1 = the highest order the given states allow (prev == cur means "no history").
+ * FAILED STEPS.  Values that are not finite are ordinary input, not an error: the call returns KR_OK and every entry of
+ * status / iters is written.  A rod whose tensions, states or parameters make its update non-finite reports
+ * KR_ST_NONFINITE (a finite input that merely overflows the arithmetic reports KR_ST_NONFINITE or KR_ST_MAXIT), with
+ * 1 <= iters <= maxit + 8 maxit - the two caps above; a non-finite update ends either phase at once, and backtracking
+ * never runs past its cap on a NaN norm.  Its G and state_next are then the last iterate and its sweep (NaN where the
+ * input reached them) and carry no meaning.  Whatever the kernel family (eight rods of single shooting share a
+ * wavefront), status, iters, G and state_next of every OTHER rod are bit for bit those of the call without the failing
+ * rod's bad values.  Nothing of a failed step stays in the handle: the next call is not affected. */
 int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, const void* state_cur,
                   void* state_next, void* G, const void* tensions, double tol, int maxit, int32_t* status,
                   int32_t* iters, int use_nn, const void* state_prev2, int predictor, int dtype, void* stream);
@@ -293,7 +301,26 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
  * step, knode.py:65-66); otherwise the packed state one step before states[0],
  * which makes a second call continue a run exactly (it may point into the ring).
  * When the multiple-shooting kernel applies (see kr_set_option) all T steps run
- * in ONE launch: every wavefront keeps its rod's history in LDS / registers. */
+ * in ONE launch: every wavefront keeps its rod's history in LDS / registers.
+ * FAILED STEPS (this call and its table / bank / loads forms).  Values that are not finite are ordinary input: the call
+ * returns KR_OK and every entry of status[B][T] is written.  A rod whose inputs stop being finite at step t0 (a NaN
+ * tension or tip load of that step; a NaN parameter of its table row: t0 = 0) reports 0 before t0 and KR_ST_NONFINITE at
+ * t0, whichever kernel family runs the call; a finite input that overflows the arithmetic reports a nonzero status at
+ * t0 (and, entering the sweeps, on every later step).  Its tips and states before t0 (states 0 .. t0) are those of
+ * the run without the bad value, bit for bit - the
+ * prefetch of step t0's inputs and, in the overlapped kernels, the sweep that carries step t0 next to the verification
+ * of step t0 - 1 do not reach back.  From t0 on the rod's outputs carry no meaning: where the bad value enters the
+ * sweeps (tensions, parameters other than the tip wrench) the stored states are NaN and every later step reports a
+ * nonzero status (KR_ST_NONFINITE in every kernel today; rely on "nonzero").  A tip wrench (loads[b][t0], F_tip / M_tip
+ * of a row) enters the tip condition only: the state stored for the failed step is the finite sweep of the last finite
+ * iterate, and later steps whose own wrench is finite solve from it and may report 0 again - status 2 at t0 is the
+ * only mark that the trajectory from there on is not the rod's.
+ * Every OTHER rod's status, tips, G and states are bit for bit those of the call without the bad value, in every kernel
+ * family; on a ring its last three states are complete.  Nothing of a failed step stays behind in the handle's scratch,
+ * the history workspace or (keep_predictor = 0) the predictor images; with keep_predictor = 1 the failing rod's own
+ * image holds its failed steps, the other rods' images are those of the clean run.
+ * No kernel reads a state slot, a tip or a status entry before it has written it: what the output buffers hold when
+ * the call starts (states[0] excepted) has no influence on any result. */
 /* Optional: the host-side one-time work of the first kr_simulate_batch call for batches of B rods (per-batch scratch
  * allocation, kernel lookup in the code object, LDS limits: ~0.4 ms) ahead of time, so that a latency-critical first
  * call does not carry it.  Launches nothing.  No counterpart in the reference. */

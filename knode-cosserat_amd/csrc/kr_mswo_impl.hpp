@@ -297,19 +297,26 @@ __global__ __launch_bounds__(WAVE * W) void mswo_sim_kernel(const RodConst<T> Pc
     // and write the tile of state tB + 1 = tA - with three tiles nothing anybody still reads.
     const T* const lead_n = tile(isB ? tB : tA);
     const T* const lead_o = tile(isB ? tB - 1 : tB);
+    // What a forward-difference lane of a merged sweep reads BEFORE its first live trip - the records requested in front of
+    // the trips - is evaluated and dropped (dsl = 0 below), but 0 x NaN is NaN: tile tA is not written at that lane's first
+    // grid point yet (the verifying lanes are only about to) and holds what was there before - state tA - 3, at the first
+    // merged sweep of a call whatever the previous launch left in the LDS, with GT the caller's output memory.  Those
+    // reads take state tB in its place, which is complete; their values reach no result.
+    const T* const lead_f = tile((isB || merged) ? tB : tA);
     auto lead_load = [&](const T* p, int j, T (&v)[12]) __attribute__((always_inline)) {
       if constexpr (GT) load_hist_vec<T, 12>(p + (size_t)j * LS, v);
       else lds_load_vec<T, 12>(p + (size_t)j * 12, v);
     };
-    auto hist_at = [&](int j, T (&hv)[HS_LEAN]) __attribute__((always_inline)) {
+    auto hist_from = [&](const T* newest, int j, T (&hv)[HS_LEAN]) __attribute__((always_inline)) {
       T la[12], lb[12];
-      lead_load(lead_n, j, la);
+      lead_load(newest, j, la);
       lead_load(lead_o, j, lb);
 #pragma unroll
       for (int c = 0; c < 12; ++c) hv[c] = A.hc1 * la[c] + A.hc2 * lb[c];
     };
+    auto hist_at = [&](int j, T (&hv)[HS_LEAN]) __attribute__((always_inline)) { hist_from(lead_n, j, hv); };
     T hv[HS_LEAN];
-    hist_at(point_of(0), hv);
+    hist_from(lead_f, point_of(0), hv);
     if (!merged) {
       // plain forward-difference sweep (start-up, rough inputs, after a rejection); every interval has sbase or sbase + 1
       // segments, so only the last grid point needs a predicate
@@ -329,8 +336,8 @@ __global__ __launch_bounds__(WAVE * W) void mswo_sim_kernel(const RodConst<T> Pc
       const bool lean = A.ring && tB + 4 <= T_steps;  // (the last three states of a call stay complete)
       T* const tnew = tile(tB + 1);        // leading slots of the state this sweep produces (over those of state tB - 2)
       T la[12], lb[12];                    // GT: leading slots in flight for the trip after the one being worked on
-      if constexpr (GT) {
-        lead_load(lead_n, point_of(1), la);
+      if constexpr (GT) {  // (LAGV = 2: a forward-difference lane is not live in the trip that consumes this either)
+        lead_load(lead_f, point_of(1), la);
         lead_load(lead_o, point_of(1), lb);
       }
       auto trip = [&](int k, auto full_tag) __attribute__((always_inline)) {

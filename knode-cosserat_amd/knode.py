@@ -159,7 +159,7 @@ def _robots_networks(robot, robots):
     return networks, net_of_rod
 
 
-def _tip_loads(tip_loads, B, T):
+def _tip_loads(tip_loads, B, T, check_finite=True):
     """``loads[B, T, 6]`` (float64, contiguous) of ``simulate_batch(..., tip_loads=...)`` from ``[B, T, 6]`` or ``[T, 6]``
     (one history for all rods); host-side validation only (no device call)."""
     try:
@@ -177,7 +177,9 @@ def _tip_loads(tip_loads, B, T):
             raise kn.KrError(f"simulate_batch: tip_loads must be [B, T, 6] = [{B}, {T}, 6] (F_tip, M_tip per step); got {L.shape}")
     else:
         raise kn.KrError(f"simulate_batch: tip_loads must be [B, T, 6] or [T, 6]; got shape {L.shape}")
-    if not np.isfinite(L).all():
+    # (check_finite=False: a wrench that is not finite is ordinary input to the library - that rod reports status 2 at that
+    #  step and no other rod of the batch notices, knode_rod.h "failed steps")
+    if check_finite and not np.isfinite(L).all():
         b, t, _ = np.argwhere(~np.isfinite(L))[0]
         raise kn.KrError(f"simulate_batch: tip_loads is not finite at rod {b}, step {t}")
     return np.ascontiguousarray(L)
@@ -214,7 +216,7 @@ def _score_reference(robot, score, B, T, tip_only):
 
 
 def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
-                   robots=None, per_robot_nn=False, score=None, tip_loads=None):
+                   robots=None, per_robot_nn=False, score=None, tip_loads=None, check_finite=True):
     """B rods, each with its own tension history.
 
     robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
@@ -243,7 +245,16 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     tip_loads: a tip wrench that varies in time, [B, T, 6] or [T, 6] (shared by all rods): rod b solves step t with
     F_tip, M_tip = tip_loads[b, t, :3], tip_loads[b, t, 3:] - the reference with ``robot.F_tip`` / ``robot.M_tip``
     assigned before that solve.  The values replace the robot's own wrench; with ``robots=`` row b keeps everything else.
-    Composes with ``score`` and ``tip_only``; not served with ``per_robot_nn``."""
+    Composes with ``score`` and ``tip_only``; not served with ``per_robot_nn``.
+
+    check_finite: True (default) refuses ``tip_loads`` that are not finite before anything touches the device; False hands
+    them to the library, for which they are ordinary input (domain randomisation, a diverging row of a sweep).
+
+    Failed steps (knode_rod.h): a rod whose inputs stop being finite at step t0 reports ``status`` 2 at t0; the call returns
+    normally and every other rod's outputs are bit for bit those of the batch without the failure.  Where the value enters
+    the sweeps (a NaN tension or rod parameter) the rod's states, tips, ``dtw`` and ``mse`` are NaN from there on and every
+    later step reports a nonzero status.  A NaN tip wrench (``tip_loads``, ``F_tip`` / ``M_tip``) enters the tip condition
+    only: states and scores stay finite and later steps may report 0 again - ``status`` 2 at t0 is the only mark."""
     loads = None
     if tip_loads is not None:  # (validated on the host before anything touches the device)
         if per_robot_nn:
@@ -251,7 +262,7 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         ctl_shape = np.asarray(ctl).shape
         if len(ctl_shape) != 3:
             raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
-        loads = _tip_loads(tip_loads, int(ctl_shape[0]), int(ctl_shape[1]))
+        loads = _tip_loads(tip_loads, int(ctl_shape[0]), int(ctl_shape[1]), check_finite)
     if score is not None:  # (validated on the host before anything touches the device)
         ctl_shape = np.asarray(ctl).shape
         if len(ctl_shape) != 3:

@@ -116,6 +116,10 @@ def test_simulate_batch_validates_tip_loads_on_the_host(kn, monkeypatch):
     bad = good.copy()
     bad[1, 3, 2] = np.nan
     refused("not finite at rod 1, step 3", tip_loads=bad)
+    # check_finite=False hands it on unchanged: to the library a wrench that is not finite is ordinary input, answered with
+    # status 2 for that rod (knode_rod.h, "failed steps"; tests/test_gpu_sick_rod.py)
+    passed = knode._tip_loads(bad, B, T, check_finite=False)
+    assert passed.shape == (B, T, 6) and np.isnan(passed[1, 3, 2]) and np.isnan(passed).sum() == 1
     refused("not served", tip_loads=good, robots=[robot] * B, per_robot_nn=True)
     refused("not served", tip_loads=good, per_robot_nn=True)
     # ... and the binding refuses loads next to a bank before it calls the library
