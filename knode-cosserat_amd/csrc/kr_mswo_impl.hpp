@@ -138,9 +138,15 @@ __global__ __launch_bounds__(WAVE * W) void mswo_sim_kernel(const RodConst<T> Pc
     }
     __syncthreads();
   };
-  // history records of step t (knode.py:74-75, raw terms) from the tiles of the states t and t - 1
+  // history records of step t (knode.py:74-75, raw terms) from the tiles of the states t and t - 1.  Every thread strides
+  // over ALL grid points.  With GT the tiles are the states in global memory, and the records of another wavefront's
+  // intervals were stored by THAT wavefront's verifying lanes, one or two merged sweeps back, with nothing but LDS
+  // barriers since (both ways into plain_step: a rejected verdict at the iteration cap, and forward-difference sweeps that
+  // find no root): the barrier in front must also wait for every wavefront's stores (vmcnt), as tile_from_hbm's does.
+  // The sweeps themselves need no such wait: a lane only reads records its own wavefront stored.
   auto rebuild = [&](int64_t t) {
-    msw_lds_barrier();
+    if constexpr (GT) __syncthreads();
+    else msw_lds_barrier();
     const T* cur = tile(t);
     const T* prv = tile(t - 1);
     for (int j = threadIdx.x; j < N; j += WAVE * W) {

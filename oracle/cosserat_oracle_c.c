@@ -49,6 +49,10 @@ static int inv3(const double* A, double* I) {
   return 0;
 }
 
+/* Test hook (tests/test_oracle_golden.py: the resolving power of the long-run windows): the BDF2 coefficient c2 of the
+ * history terms is multiplied by this.  1.0 everywhere else. */
+double orc_c2_scale = 1.0;
+
 /* compute_intermediate_terms, cosserat_ode.py:58-78 */
 static int derive(const orc_params* P, derived* D) {
   const double pi = 3.14159265358979323846;
@@ -57,7 +61,7 @@ static int derive(const orc_params* P, derived* D) {
   D->N = P->N;
   const double r2 = P->r * P->r, A = pi * r2, G = P->E / (2 * (1 + 0.3)), Ixx = pi * r2 * r2 / 4;
   D->ds = P->L / (P->N - 1);
-  D->c0 = 1.5 / P->del_t; D->c1 = -2.0 / P->del_t; D->c2 = 0.5 / P->del_t;
+  D->c0 = 1.5 / P->del_t; D->c1 = -2.0 / P->del_t; D->c2 = 0.5 / P->del_t * orc_c2_scale;
   double Kse[9] = {G * A, 0, 0, 0, G * A, 0, 0, 0, P->E * A};
   double Kbt[9] = {P->E * Ixx, 0, 0, 0, P->E * Ixx, 0, 0, 0, G * 2 * Ixx};
   double t[9];

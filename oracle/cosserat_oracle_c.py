@@ -43,15 +43,22 @@ def params_from(P) -> OrcParams:
     return o
 
 
-def simulate(P, ctl, traj=True):
-    """-> (tip[T, 3], traj[T+1, 25, N] or None, n_unconverged).  Releases the GIL: call it from threads."""
+def simulate(P, ctl, traj=True, c2_scale=1.0):
+    """-> (tip[T, 3], traj[T+1, 25, N] or None, n_unconverged).  Releases the GIL: call it from threads.
+    c2_scale != 1 (a test of the tests: a BDF2 history coefficient that is slightly wrong) is a process-wide setting for
+    the duration of the call - not for threads."""
     lib = load()
+    scale = C.c_double.in_dll(lib, "orc_c2_scale")
     ctl = np.ascontiguousarray(ctl, dtype=np.float64).reshape(-1, 4)
     T = ctl.shape[0]
     tip = np.empty((T, 3))
     tr = np.empty((T + 1, 25, int(P.N))) if traj else None
     o = params_from(P)
-    bad = lib.orc_simulate(C.byref(o), T, ctl.ctypes.data, tip.ctypes.data, tr.ctypes.data if traj else None)
+    scale.value = float(c2_scale)
+    try:
+        bad = lib.orc_simulate(C.byref(o), T, ctl.ctypes.data, tip.ctypes.data, tr.ctypes.data if traj else None)
+    finally:
+        scale.value = 1.0
     if bad < 0:
         raise ValueError("bad parameters")
     return tip, tr, bad

@@ -753,7 +753,96 @@ def gen_bc():
     save("bc", **out)
 
 
+def checked_sim(r, ctl, what):
+    """run_sim that refuses a run the reference did not solve throughout (the long fixtures hold whole trajectories
+    against it: one unconverged step would poison everything after)."""
+    t0 = time.time()
+    traj, ier, nfev = run_sim(r, ctl)
+    ok = bool(np.all(ier == 1)) and bool(np.all(np.isfinite(traj)))
+    print(f"  {what}: {len(ctl)} steps in {time.time()-t0:.1f} s, ier all 1 and finite = {ok}, mean nfev {nfev.mean():.1f}")
+    return traj, ier, nfev, ok
+
+
+def gen_sim_long_n100():
+    """BASELINE cfg2 at its full length: N = 100, setup_robot(None), T = 200.  Rod A = rod 0 of the
+    ``batch_sine_controls(256, 200, del_t, 1234)`` draw (round3.npz: cfg2_tip[0] continued from 50 to 200 steps).
+    Rod B = rod A's history with +a N on tendon 0 from step 120 and -a N on tendon 2 from step 170, a the first of
+    0.5 / 0.25 / 0.1 the reference solves throughout (stored as ``jump_a``); if it solves none the fixture carries
+    rod A only and ``jump_a`` is 0.  Tips [T, 3] (entry 0 = initial tip), every 20th state and the last one."""
+    r = np_robot(None, 100)
+    T = 200
+    ctl_a = orc.batch_sine_controls(256, T, r.del_t, 1234)[0]
+    traj, ier, nfev, ok = checked_sim(r, ctl_a, "rod A")
+    if not ok:
+        raise RuntimeError("sim_long_n100: the reference did not solve rod A throughout")
+    old = np.load(os.path.join(HERE, "round3.npz"))
+    assert int(old["cfg2_rods"][0]) == 0 and np.array_equal(traj[:50, :3, -1], old["cfg2_tip"][0])
+    ctls, trajs, iers, nfevs, jump_a = [ctl_a], [traj], [ier], [nfev], 0.0
+    for a in (0.5, 0.25, 0.1):
+        ctl_b = ctl_a.copy()
+        ctl_b[120:, 0] += a
+        ctl_b[170:, 2] -= a
+        tb, ib, nb, okb = checked_sim(np_robot(None, 100), ctl_b, f"rod B, a = {a}")
+        if okb:
+            assert np.array_equal(tb[:120], traj[:120])
+            ctls.append(ctl_b), trajs.append(tb), iers.append(ib), nfevs.append(nb)
+            jump_a = a
+            break
+    trajs = np.array(trajs)
+    save("sim_long_n100", ctl=np.array(ctls), tip=trajs[:, :, :3, -1], every20=trajs[:, ::20, :25],
+         last=trajs[:, -1, :25], ier=np.array(iers), nfev=np.array(nfevs), jump_a=np.array(jump_a),
+         jump_steps=np.array([120, 170]))
+
+
+def gen_sim_long_n400():
+    """BASELINE cfg5 at its full length: N = 400, T = 100, calc_controls('sine', 1.0) (sim_n400.npz continued from
+    12 to 100 steps).  Tips, every 25th state and the last one."""
+    r = np_robot(None, 400)
+    T = 100
+    ctl = np.array(ref_ctl.calc_controls("sine", 1.0, r.del_t, T))
+    traj, ier, nfev, ok = checked_sim(r, ctl, "N = 400")
+    if not ok:
+        raise RuntimeError("sim_long_n400: the reference did not solve the run throughout")
+    old = np.load(os.path.join(HERE, "sim_n400.npz"))
+    assert np.array_equal(ctl[:12], old["ctl"]) and np.array_equal(traj[:12, :3, -1], old["tip"])
+    save("sim_long_n400", ctl=ctl, tip=traj[:, :3, -1], every25=traj[::25, :25], last=traj[-1, :25], ier=ier, nfev=nfev)
+
+
+def gen_sim_long_nn():
+    """BASELINE cfg3 at its full length: N = 100, T = 64, the MLP 28 -> 64 -> 64 -> 25 (elu, seed 7) in every sweep.
+    Rods 3 and 1000 of ``batch_sine_controls(1024, 64, del_t, 1235)``; where the reference does not solve one of
+    them throughout, the next of the draw that it does solve (``rods`` holds the indices kept).  Tips, every 8th
+    state, the last state and the network."""
+    T = 64
+    mlp = orc.make_mlp([28, 64, 64, 25], "elu", seed=7)
+    r = np_robot(None, 100)
+    inject_nn(r, mlp)
+    ctl_all = orc.batch_sine_controls(1024, T, r.del_t, 1235)
+    rods, trajs, iers, nfevs = [], [], [], []
+    for first in (3, 1000):
+        for cand in range(first, min(first + 12, 1024)):
+            if cand in rods:
+                continue
+            traj, ier, nfev, ok = checked_sim(r, ctl_all[cand], f"MLP on, rod {cand}")
+            if ok:
+                rods.append(cand), trajs.append(traj), iers.append(ier), nfevs.append(nfev)
+                break
+        else:
+            raise RuntimeError(f"sim_long_nn: no rod from {first} on that the reference solves throughout")
+    trajs = np.array(trajs)
+    r_off = np_robot(None, 100)
+    for k, b in enumerate(rods):  # the network must matter, otherwise the fixture pins the physics only
+        off, _, _, ok = checked_sim(r_off, ctl_all[b], f"MLP off, rod {b}")
+        d = np.linalg.norm(off[:, :3, -1] - trajs[k, :, :3, -1]) / np.linalg.norm(off[:, :3, -1])
+        print(f"  rod {b}: MLP on vs off, tips differ by {d:.3e}")
+        assert ok and d > 1e-4
+    save("sim_long_nn", rods=np.array(rods), ctl=ctl_all[rods], tip=trajs[:, :, :3, -1], every8=trajs[:, ::8, :25],
+         last=trajs[:, -1, :25], ier=np.array(iers), nfev=np.array(nfevs), seed=np.array(1235), B=np.array(1024),
+         **mlp_arrays("mlp", mlp))
+
+
 ALL = {
+    "sim_long_n100": gen_sim_long_n100, "sim_long_n400": gen_sim_long_n400, "sim_long_nn": gen_sim_long_nn,
     "ode_kat": gen_ode_kat, "ode_torch_kat": gen_ode_torch_kat, "residual_kat": gen_residual_kat,
     "sim_cfg1": gen_sim_cfg1, "sim_n100": gen_sim_n100, "sim_n400": gen_sim_n400, "sim_misc": gen_sim_misc,
     "sim_nn": gen_sim_nn, "sim_more": gen_sim_more, "train_step": gen_train_step, "small": gen_small,

@@ -39,7 +39,8 @@ def torch_cuda():
 def test_cfg2_full_size_auto_kernel(torch_cuda, monkeypatch, dtype):
     """B = 256 rods, N = 100, T = 200, tensions of SURVEY 8d cfg2 (default_rng(1234)), kernel choice left to the
     library: the persistent kernel with four wavefronts per rod must run, every step converges, and the eight rods the
-    reference itself solved with ier == 1 (knode.py:55-102, 50 steps) agree to 1e-8 (fp64) / 1e-5 (fp32)."""
+    reference itself solved with ier == 1 (knode.py:55-102, 50 steps) agree to 1e-8 (fp64) / 1e-5 (fp32).  Rod 0 is held
+    against the reference over ALL 200 steps (sim_long_n100.npz, rod A), whole run and every 50-step window."""
     import cosserat_oracle as orc
     from knode import simulate_batch
     for v in ("KR_MS_MODE", "KR_PERSISTENT", "KR_WAVES_PER_ROD"):
@@ -60,6 +61,11 @@ def test_cfg2_full_size_auto_kernel(torch_cuda, monkeypatch, dtype):
         # reference entry t (t >= 1) is the state after solve t; simulate_batch's tip[t - 1] is the same solve
         ref = g["cfg2_tip"][k][1:Tf]
         assert rel_l2(out["tip"][b, : Tf - 1], ref) < tol, (int(b), dtype)
+    long_run = load_golden("sim_long_n100")
+    assert np.all(long_run["ier"][0] == 1) and np.array_equal(long_run["ctl"][0], ctl[0])
+    assert np.array_equal(long_run["tip"][0][:Tf], g["cfg2_tip"][0])  # (the 50-step fixture, continued)
+    for a, b in [(0, T - 1)] + [(a, min(a + 50, T - 1)) for a in range(0, T - 1, 50)]:
+        assert rel_l2(out["tip"][0, a:b], long_run["tip"][0][1 + a:1 + b]) < tol, (a, b, dtype)
     # the long run stays on the attractor of the same motion: bounded, and rods differ
     assert np.abs(out["tip"]).max() < 1.0 and np.std(out["tip"][:, -1, 0]) > 1e-3
 

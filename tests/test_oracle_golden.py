@@ -402,3 +402,79 @@ def test_c_oracle_under_sanitizers():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
     assert r.stdout.count("unconverged=0") == 8, r.stdout
+
+
+# ---------------------------------------------------------------------------
+# the reference at the lengths the BASELINE configurations run (tests/golden/sim_long_*.npz, tests/long_run_cases.py)
+# ---------------------------------------------------------------------------
+def _c_oracle_long(case, b, c2_scale=1.0):
+    import cosserat_oracle_c as oc
+    T = case["T"]
+    tip, tr, bad = oc.simulate(orc.params_for(None, case["N"]), case["ctl"][b][: T - 1], c2_scale=c2_scale)
+    return np.concatenate([tr[0, :3, -1][None], tip]), tr, bad
+
+
+@pytest.mark.parametrize("name,b", [("n100", 0), ("n100", 1), ("n400", 0)])
+def test_c_oracle_long_runs_vs_reference(name, b):
+    """The C oracle against the reference over cfg2's 200 steps (rod A smooth, rod B with two late tension jumps) and cfg5's
+    100 steps at N = 400: tips per 50-step window and over the whole run to 1e-9, the stored states to 1e-8.  Measured:
+    LABBOOK.md (long runs)."""
+    import long_run_cases as lc
+    case = lc.long_case(name)
+    if name == "n100":
+        assert case["B"] == 2 and case["jump_a"] == 0.5  # rod B is there, with the largest of the three jumps
+    got, tr, bad = _c_oracle_long(case, b)
+    assert bad == 0
+    errs = lc.window_errors(got, case["tip"][b], case["window"])
+    print(f"C oracle {name} rod {b}: tip windows {['%.1e' % e for e in errs]}")
+    assert max(errs) < 1e-9, errs
+    serr = {k: rel_l2(tr[k], v[b]) for k, v in case["states"].items() if k > 0}
+    print(f"C oracle {name} rod {b}: states {{{', '.join('%d: %.1e' % kv for kv in serr.items())}}}")
+    assert max(serr.values()) < 1e-8, serr
+
+
+def test_long_run_windows_resolve_a_history_error():
+    """The test of the tests: the C oracle with the BDF2 history coefficient c2 scaled by 1 + 1e-6 must MISS 1e-8 in the last
+    50-step window of rod A - an error of that size in what a step carries over from two steps back is visible there."""
+    import long_run_cases as lc
+    case = lc.long_case("n100")
+    got, _, bad = _c_oracle_long(case, 0, c2_scale=1.0 + 1e-6)
+    assert bad == 0
+    errs = lc.window_errors(got, case["tip"][0], case["window"])
+    print(f"c2 (1 + 1e-6): tip windows {['%.1e' % e for e in errs]}")
+    assert errs[-2] > 1e-8, errs
+    clean, _, _ = _c_oracle_long(case, 0)
+    assert lc.window_errors(clean, case["tip"][0], case["window"])[-2] < 1e-9  # (the hook is off again)
+
+
+@pytest.mark.parametrize("solver", ["newton", "fsolve"])
+@pytest.mark.parametrize("b", [0, 1])
+def test_numpy_oracle_long_run_with_mlp(solver, b):
+    """cfg3's network (28 -> 64 -> 64 -> 25, elu, seed 7) in every sweep over cfg3's 64 steps at N = 100, rods 3 and 1000 of
+    its draw: tips per 16-step window and the stored states to 1e-8, the bound of the short MLP fixtures."""
+    import long_run_cases as lc
+    case = lc.long_case("nn")
+    assert case["rods"] == [3, 1000]
+    D = orc.params_for(None, case["N"]).derived()
+    with np.errstate(all="ignore"):
+        traj = orc.simulate(D, case["ctl"][b], mlp=case["mlp"], solver=solver)
+    errs = lc.window_errors(traj[:, :3, -1], case["tip"][b], case["window"])
+    print(f"NumPy oracle ({solver}) nn rod {b}: tip windows {['%.1e' % e for e in errs]}")
+    assert max(errs) < 1e-8, errs
+    serr = {k: rel_l2(traj[k, :25], v[b]) for k, v in case["states"].items() if k > 0}
+    print(f"NumPy oracle ({solver}) nn rod {b}: states {{{', '.join('%d: %.1e' % kv for kv in serr.items())}}}")
+    assert max(serr.values()) < 1e-8, serr
+
+
+@pytest.mark.parametrize("N", [100, 400])
+def test_rough_batch_is_mostly_solved_by_the_oracle(N):
+    """tests/test_gpu_long_runs.py holds the kernels against the C oracle on the rods it converged on at every step: at
+    least ten of the twelve, and the rough ones must really differ from their smooth base late in the run."""
+    import long_run_cases as lc
+    case = lc.rough_case(N)
+    assert int(case["good"].sum()) >= lc.ROUGH_MIN_GOOD, case["good"].tolist()
+    base = orc.batch_sine_controls(256, case["T"], lc.DEL_T, 1234)[: lc.ROUGH_B]
+    first = [int(np.argmax(np.any(case["ctl"][b] != base[b], axis=1))) for b in range(4, 12)]
+    assert np.array_equal(case["ctl"][:4], base[:4]) and all(f >= min(case["T"] - case["T"] // 3, case["T"] - 30) for f in first), first
+    assert all(np.any(case["ctl"][b] != base[b]) for b in range(4, 12))
+    assert np.abs(case["tip"][4:]).max() < 1.0
