@@ -113,6 +113,18 @@ __device__ __forceinline__ U* own_sgpr_global(U* p) {
   return (U*)(__attribute__((address_space(1))) U*)v;
 }
 
+// One of four values by the lane's place in its quad, as three selects on the values.  (Written as a chain of
+// conditional expressions the compiler emits a ladder of nested exec-mask blocks with one move in each; the wavefront
+// that runs this kernel alone on its SIMD pays full latency for every instruction of such a ladder.)
+template <typename T>
+__device__ __forceinline__ T quad_pick(int kp, T v0, T v1, T v2, T v3) {
+  T v = v3;
+  v = kp == 2 ? v2 : v;
+  v = kp == 1 ? v1 : v;
+  v = kp == 0 ? v0 : v;
+  return v;
+}
+
 // ms_pred_update for this kernel (every step it hands over has converged).  While the fitted recurrence is in use and
 // predicted the step to better than 1e-3 (ms_pred_update's poly_eval == false) no polynomial order is measured: every
 // em[p] is 3.0e38f there, the order-choice loop ends at nxt = pmax and eb = 3.0e38f.  That case is written out straight -
@@ -378,8 +390,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 
   // p rows, scaled update norm and the per-lane pieces of an update of the unknowns X from base end states Eb(g)
   // (A: Es slot of the interval's unperturbed lane; B: EsB) - the tail both the chord and the Newton update share.
-  // Returns the norm; the update itself is left in updP / updG / updY with the current values xsP / xsG / xsY.
-  struct Upd { T updP, updG, xsP, xsG, xsY[MS_P - 1]; };
+  // Returns the norm; the updated unknowns are left in U, one value per lane and family: newPG for the owner of a p row
+  // or of a component of G (no lane owns both), newY[g - 1] for the owner of a row of Y_g.  Other lanes hold there
+  // what the clamped reads gave them; apply() stores under the owners' masks.
+  struct Upd { T newPG, newY[MS_P - 1]; };
 
   while (true) {
     const bool runA = tA < T_steps;  // (false only for the sweep that verifies the last step)
@@ -625,60 +639,88 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       }
       wave_sync_lds();
       if (plane) {
-        const int l0 = pi == 0 ? 0 : 7 + 17 * (pi - 1);
+        // Every read below is unconditional, from a slot this launch has written, and the terms a lane does not have
+        // are dropped by selects on the VALUES (never by a product with zero: DESIGN section 6).  Term 0 has the six
+        // columns of A_0 with dG: its lane reads the Es slots of lanes 1..16 and row 1 of dYb like the others read
+        // theirs, takes d[] for the first six elements and keeps its two sums as they stand behind the sixth
+        // (what follows there is fma(0, 0, s) = s in the form with per-element conditions).
+        const bool p0 = pi == 0;
+        const int l0 = p0 ? 0 : 7 + 17 * (pi - 1);
+        const int drow = p0 ? 1 : pi;
         T s = Es[base_slot(pi) * MS_YP + prow] - X[(pi + 1) * MS_YP + prow];
         T av[16], dv[16];
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
-          const bool use = pi > 0 || c < 6;
-          av[c] = use ? Es[(l0 + 1 + c) * MS_YP + prow] : T(0);
-          dv[c] = pi > 0 ? dYb[pi * MS_YP + 3 + c] : T(0);
+          av[c] = Es[(l0 + 1 + c) * MS_YP + prow];
+          dv[c] = dYb[drow * MS_YP + 3 + c];
         }
         __builtin_amdgcn_sched_barrier(0);
         T s2 = T(0);
 #pragma unroll
-        for (int c = 0; c < 16; c += 2) {
-          const T da = pi > 0 ? dv[c] : (c < 6 ? d[c < 6 ? c : 0] : T(0));
-          const T db = pi > 0 ? dv[c + 1] : (c + 1 < 6 ? d[c + 1 < 6 ? c + 1 : 0] : T(0));
-          s = fma(av[c], da, s);
-          s2 = fma(av[c + 1], db, s2);
+        for (int c = 0; c < 6; c += 2) {
+          s = fma(av[c], p0 ? d[c] : dv[c], s);
+          s2 = fma(av[c + 1], p0 ? d[c + 1] : dv[c + 1], s2);
         }
+        const T s_6 = s, s2_6 = s2;
+#pragma unroll
+        for (int c = 6; c < 16; c += 2) {
+          s = fma(av[c], dv[c], s);
+          s2 = fma(av[c + 1], dv[c + 1], s2);
+        }
+        s = p0 ? s_6 : s;
+        s2 = p0 ? s2_6 : s2;
         sp[pi * 3 + prow] = s + s2;
       }
       wave_sync_lds();
-      float nf = 0.f;
-      U.updP = T(0); U.updG = T(0); U.xsP = T(0); U.xsG = T(0);
-      if (plane) {  // this lane owns Y_{pi+1}[prow]
-        U.xsP = X[(pi + 1) * MS_YP + prow];
+      // Every lane reads its operands from clamped indices and forms the update ratio of what it read; the selects come
+      // last, on the ratios (never NaN).  A read under its own mask is a block of its own for every element.  The ratios
+      // are pinned: left alone the compiler puts each of them back under its mask.
+      const T xp = X[(pi + 1) * MS_YP + prow];  // lanes 0 .. 3 (P-1) - 1 own Y_{pi+1}[prow] (the others: row 1, element 0)
+      T up = T(0);
 #pragma unroll
-        for (int i = 0; i < MS_P - 1; ++i) {
-          const T t = sp[i * 3 + prow];
-          U.updP += i <= pi ? t : T(0);
-        }
-        nf = update_ratio(U.updP, U.xsP);
+      for (int i = 0; i < MS_P - 1; ++i) {
+        const T t = sp[i * 3 + prow];
+        up += i <= pi ? t : T(0);
       }
-      if (glane) {
-        const int k = ln - (WAVE - 6);
-        U.xsG = X[0 * MS_YP + 7 + k];
-        U.updG = k == 0 ? d[0] : k == 1 ? d[1] : k == 2 ? d[2] : k == 3 ? d[3] : k == 4 ? d[4] : d[5];
-        nf = fmaxf(nf, update_ratio(U.updG, U.xsG));
-      }
+      const int kg = glane ? ln - (WAVE - 6) : 0;  // the last six lanes own G
+      const T xg = X[0 * MS_YP + 7 + kg];
+      T ug = d[5];  // (pinned: as a plain chain of selects it becomes a table in scratch memory, indexed by kg)
+      asm volatile("" : "+v"(ug));
+      ug = kg == 4 ? d[4] : ug;
+      ug = kg == 3 ? d[3] : ug;
+      asm volatile("" : "+v"(ug));
+      ug = kg == 2 ? d[2] : ug;
+      ug = kg == 1 ? d[1] : ug;
+      asm volatile("" : "+v"(ug));
+      ug = kg == 0 ? d[0] : ug;
+      const T newP = xp + up, newG = xg + ug;
+      U.newPG = plane ? newP : newG;
+      // (the maximum of this lane's ratios on their bit patterns: they are non-negative and never NaN, so the order of
+      //  the patterns is the order of the values, and an integer maximum needs no canonicalising of pinned operands)
+      float np = update_ratio(up, xp), ng = update_ratio(ug, xg);
+      asm volatile("" : "+v"(np), "+v"(ng));
+      unsigned nb = plane ? __float_as_uint(np) : (glane ? __float_as_uint(ng) : 0u);
 #pragma unroll
-      for (int g = 1; g < MS_P; ++g) {
-        U.xsY[g - 1] = T(0);
-        if (((g - 1) & 3) == kp) {  // one lane of the quad owns Y_g[r]
-          U.xsY[g - 1] = X[g * MS_YP + r];
-          nf = fmaxf(nf, update_ratio(updY[g - 1], U.xsY[g - 1]));
-        }
+      for (int g = 1; g < MS_P; ++g) {  // one lane of the quad owns Y_g[r]
+        const T xy = X[g * MS_YP + r];
+        float ny = update_ratio(updY[g - 1], xy);
+        U.newY[g - 1] = xy + updY[g - 1];
+        asm volatile("" : "+v"(ny));
+        nb = max(nb, ((g - 1) & 3) == kp ? __float_as_uint(ny) : 0u);
       }
+      const float nf = __uint_as_float(nb);
       return wave_max_nonneg(nf);  // +inf if any update is not finite
     };
     auto apply = [&](T* X) {
-      if (plane) X[(pi + 1) * MS_YP + prow] = U.xsP + U.updP;
-      if (glane) X[0 * MS_YP + 7 + (ln - (WAVE - 6))] = U.xsG + U.updG;
+      // (the owners' masks afresh from the lane index: kept across finish() they would sit in a spill register)
+      int la = ln;
+      asm volatile("" : "+v"(la));
+      const bool pl = la < 3 * (MS_P - 1), gl = la >= WAVE - 6;
+      const int pa = pl ? la / 3 : 0;
+      if (pl || gl) X[pl ? (pa + 1) * MS_YP + (la - 3 * pa) : 0 * MS_YP + 7 + (la - (WAVE - 6))] = U.newPG;
 #pragma unroll
       for (int g = 1; g < MS_P; ++g)
-        if (((g - 1) & 3) == kp) X[g * MS_YP + r] = U.xsY[g - 1] + updY[g - 1];
+        if (g - 1 == (la & 3)) X[g * MS_YP + r] = U.newY[g - 1];
     };
 
     // =============================================================================================================
@@ -784,8 +826,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           }
         }
         {
-          const T dd0 = kp == 0 ? T(0) : kp == 1 ? d[1] : kp == 2 ? d[3] : d[5];  // (the a column is the new one)
-          const T dd1 = kp == 0 ? d[0] : kp == 1 ? d[2] : kp == 2 ? d[4] : T(0);
+          const T dd0 = quad_pick<T>(kp, T(0), d[1], d[3], d[5]);  // (the a column is the new one)
+          const T dd1 = quad_pick<T>(kp, d[0], d[2], d[4], T(0));
 #pragma unroll
           for (int g = 1; g < MS_P; ++g) {
             T sx = fma(Xreg[g - 1][1], dd1, Xreg[g - 1][0] * dd0);
@@ -990,8 +1032,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       have_fac = true;
     }
     {
-      const T dd0 = kp == 0 ? T(1) : kp == 1 ? d[1] : kp == 2 ? d[3] : d[5];
-      const T dd1 = kp == 0 ? d[0] : kp == 1 ? d[2] : kp == 2 ? d[4] : T(0);
+      const T dd0 = quad_pick<T>(kp, T(1), d[1], d[3], d[5]);
+      const T dd1 = quad_pick<T>(kp, d[0], d[2], d[4], T(0));
 #pragma unroll
       for (int g = 1; g < MS_P; ++g) {
         T s = fma(Xreg[g - 1][1], dd1, Xreg[g - 1][0] * dd0);
