@@ -225,12 +225,20 @@ def quat_rotation(h) -> np.ndarray:
     ])
 
 
-def ode(D: Derived, y, yh, zh, tendon_forces, mlp: Mlp | None = None):
+def ode(D: Derived, y, yh, zh, tendon_forces, mlp: Mlp | None = None, leaves=None):
     """One evaluation of the rod's arc-length derivative.
 
     Returns ``(ys[19], z[6])``.  With an MLP the network correction is added to
     ``ys`` and ``z`` *after* every physics term has been formed from the
-    uncorrected ``z`` (cosserat_ode.py:178-184)."""
+    uncorrected ``z`` (cosserat_ode.py:178-184).
+
+    ``leaves`` (oracle/ode_derivative.py only; the default path does not look at it) replaces pieces of the map by
+    values that do not move with the inputs, which is how a derivative of the map is restricted: ``sign_q`` stands
+    for sign(q) in |q| = sign(q) q (so that q = 0 has the derivative 0 that it has analytically), ``h_quad`` are the
+    quaternion entries the quadratic part of R is assembled from and ``u_rate`` the entries of Omega(u) in h_s - the
+    two places where the torch twin's serial ODE builds a matrix as new leaves (cosserat_ode_torch.py:159-162, :185-189)."""
+    if leaves is not None:
+        return _ode_leaves(D, y, yh, zh, tendon_forces, leaves)
     h, n, m, q, w = y[3:7], y[7:10], y[10:13], y[13:16], y[16:19]
     vh, uh = zh[0:3], zh[3:6]
     R = quat_rotation(h)
@@ -266,6 +274,48 @@ def ode(D: Derived, y, yh, zh, tendon_forces, mlp: Mlp | None = None):
         ys = ys + out[:NY]
         z = z + out[NY:]
     return ys, z
+
+
+def _ode_leaves(D, y, yh, zh, tendon_forces, leaves):
+    """``ode`` without a network and with the pieces named in ``leaves`` held fixed (see there); with nothing
+    held it is the same arithmetic in the same order."""
+    h, n, m, q, w = y[3:7], y[7:10], y[10:13], y[13:16], y[16:19]
+    vh, uh = zh[0:3], zh[3:6]
+    hq = leaves.get("h_quad")
+    if hq is None:
+        R = quat_rotation(h)
+    else:  # R = I + (2 / h.h) quad(hq): h reaches R through the scalar factor only
+        a, b, c, d = hq
+        s = 2.0 / (h[0] * h[0] + h[1] * h[1] + h[2] * h[2] + h[3] * h[3])
+        R = np.array([
+            [1 + s * (-c * c - d * d), s * (b * c - d * a), s * (b * d + c * a)],
+            [s * (b * c + d * a), 1 + s * (-b * b - d * d), s * (c * d - b * a)],
+            [s * (b * d - c * a), s * (c * d + b * a), 1 + s * (-b * b - c * c)],
+        ])
+    v = D.Kse_inv @ (R.T @ n + D.Kse_vstar - D.Bse @ vh)
+    u = D.Kbt_inv @ (R.T @ m - D.Bbt @ uh)
+    qt = D.c0 * q + yh[13:16]
+    wt = D.c0 * w + yh[16:19]
+    vt = D.c0 * v + vh
+    ut = D.c0 * u + uh
+    sq = leaves.get("sign_q")
+    absq = np.abs(q) if sq is None else sq * q
+    f = D.rhoAg - R @ (D.C * q * absq) + tendon_forces
+    ps = R @ v
+    ns = D.rhoA * (R @ (_cross(w, q) + qt)) - f
+    ms = R @ (_cross(w, D.rhoJ @ w) + D.rhoJ @ wt) - _cross(ps, n)
+    qs = vt - _cross(u, q) + _cross(w, v)
+    ws = ut - _cross(u, w)
+    uo = leaves.get("u_rate")
+    if uo is None:
+        uo = u
+    hs = 0.5 * np.array([
+        -uo[0] * h[1] - uo[1] * h[2] - uo[2] * h[3],
+        uo[0] * h[0] + uo[2] * h[2] - uo[1] * h[3],
+        uo[1] * h[0] - uo[2] * h[1] + uo[0] * h[3],
+        uo[2] * h[0] + uo[1] * h[1] - uo[0] * h[2],
+    ])
+    return np.concatenate([ps, hs, ns, ms, qs, ws]), np.concatenate([v, u])
 
 
 # --------------------------------------------------------------------------

@@ -603,6 +603,83 @@ def gen_tres_grad():
     save("tres_grad", **out)
 
 
+def gen_ode_deriv():
+    """Derivative fixture (tests/ode_derivative_cases.py holds the sets, rows and sweep cases):
+    (a) the reference's autograd Jacobians d(y_s, z) / d(y, yh, zh, tendon force) of ODE_parallel (complete graph) and
+    of the serial ODE (graph cut at quad(h) and Omega(u), cosserat_ode_torch.py:159-162, :185-189), both with the
+    reference run in fp64 - the default dtype is float64 while its objects are built and used, and restored after;
+    (b) getResidualEuler with autograd as in gen_tres_grad (fp32, as the reference runs it), L = total + sum(full * Wgt):
+    N in {4, 10, 33} x {None, full} x {no network, 28 -> 64 -> 25, 53 -> 64 -> 25 with history inputs}."""
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import ode_derivative_cases as dc
+    out = {}
+    # ---- (b) sweep cases, fp32 ----
+    rng = np.random.default_rng(77)
+    for N in dc.SWEEP_N:
+        rn = np_robot(None, N)
+        y, z, yp, zp, G0, tens = converged_state(rn, 6, lambda T: ref_ctl.calc_controls("sine", 1.0, rn.del_t, T))
+        G = G0 * 1.03 + 1e-3
+        Wgt = rng.standard_normal((25, N)).astype(np.float32)
+        for k, v in (("y", y), ("z", z), ("yp", yp), ("zp", zp), ("G", G), ("tens", tens), ("Wgt", Wgt)):
+            out[f"sw_N{N}_{k}"] = v
+        for s in dc.SWEEP_SETS:
+            for net in dc.SWEEP_NETS:
+                mlp = dc.sweep_mlp(net)
+                rob = ref_torch.CosseratRodTorch("cpu", 64, nn_input_history=bool(mlp is not None and mlp.history))
+                rob.N = N
+                dc.apply_to_torch_rod(rob, s)
+                if mlp is not None:
+                    rob.nn_models = torch_module_list(mlp)
+                rob.use_nn = mlp is not None
+                ty, tz = torch.tensor(y).float(), torch.tensor(z).float()
+                typ, tzp = torch.tensor(yp).float(), torch.tensor(zp).float()
+                rob.y, rob.z = ty.clone(), tz.clone()
+                rob.tendon_tensions = torch.tensor(tens).float()
+                rob.residualArgs["yh"] = rob.c1 * ty + rob.c2 * typ
+                rob.residualArgs["zh"] = rob.c1 * tz + rob.c2 * tzp
+                Gt = torch.tensor(G).float().requires_grad_(True)
+                tot, full = rob.getResidualEuler(Gt)
+                L = tot + (full * torch.tensor(Wgt)).sum()
+                L.backward()
+                tag = dc.sweep_tag(N, s, net)
+                out[f"{tag}_L"] = np.array(float(L))
+                out[f"{tag}_dG"] = Gt.grad.numpy().copy()
+                if mlp is not None:
+                    for k, prm in enumerate(rob.nn_models.parameters()):
+                        out[f"{tag}_dparam{k}"] = prm.grad.numpy().copy()
+    for net in dc.SWEEP_NETS[1:]:
+        out.update(mlp_arrays(f"mlp_{net}", dc.sweep_mlp(net)))
+    # ---- (a) Jacobians of one grid point, fp64 ----
+    y, yh, zh, tf = dc.rows()
+    out["rows_y"], out["rows_yh"], out["rows_zh"], out["rows_tf"] = y, yh, zh, tf
+    x = np.concatenate([y, yh, zh, tf], axis=1)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        for s in dc.SETS:
+            rob = ref_torch.CosseratRodTorch("cpu", 64)
+            dc.apply_to_torch_rod(rob, s)
+            for k, v in list(rob.__dict__.items()):
+                if torch.is_tensor(v):
+                    setattr(rob, k, v.detach().double())
+            rob.compute_intermediate_terms()
+            rob.use_nn = False
+            P = dc.rod_params(s)
+            for f in dc.PARAM_FIELDS:
+                out[f"set_{s}_{f}"] = np.asarray(getattr(P, f), np.float64)
+                mine = getattr(rob, f)
+                assert np.array_equal(out[f"set_{s}_{f}"], mine.numpy() if torch.is_tensor(mine) else np.float64(mine)), (s, f)
+            par = lambda v: torch.cat(rob.ODE_parallel(v[None, 0:19], v[None, 19:38], v[None, 38:44], v[None, 44:47]), 1)[0]
+            ser = lambda v: torch.cat(rob.ODE(v[0:19], v[19:38], v[38:44], v[44:47]), 0)
+            for name, fn in (("uncut", par), ("cut", ser)):
+                Js = [torch.autograd.functional.jacobian(fn, torch.tensor(x[i], dtype=torch.float64)).numpy() for i in range(x.shape[0])]
+                out[f"J_{name}_{s}"] = np.stack(Js)
+                assert out[f"J_{name}_{s}"].shape == (x.shape[0], 25, 47) and out[f"J_{name}_{s}"].dtype == np.float64
+    finally:
+        torch.set_default_dtype(prev)
+    save("ode_deriv", **out)
+
+
 def gen_small():
     """F8: calc_controls and quaternion_to_euler."""
     out = {}
@@ -848,6 +925,7 @@ ALL = {
     "sim_nn": gen_sim_nn, "sim_more": gen_sim_more, "train_step": gen_train_step, "small": gen_small,
     "checkpoint": gen_checkpoint, "estimate_state": gen_estimate_state, "tres_grad": gen_tres_grad,
     "round3": gen_round3, "bc": gen_bc,
+    "ode_deriv": gen_ode_deriv,
 }
 
 if __name__ == "__main__":
