@@ -302,7 +302,7 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
  * which makes a second call continue a run exactly (it may point into the ring).
  * When the multiple-shooting kernel applies (see kr_set_option) all T steps run
  * in ONE launch: every wavefront keeps its rod's history in LDS / registers.
- * FAILED STEPS (this call and its table / bank / loads forms).  Values that are not finite are ordinary input: the call
+ * FAILED STEPS (this call and its table / bank / loads / boundary forms).  Values that are not finite are ordinary input: the call
  * returns KR_OK and every entry of status[B][T] is written.  A rod whose inputs stop being finite at step t0 (a NaN
  * tension or tip load of that step; a NaN parameter of its table row: t0 = 0) reports 0 before t0 and KR_ST_NONFINITE at
  * t0, whichever kernel family runs the call; a finite input that overflows the arithmetic reports a nonzero status at
@@ -315,6 +315,9 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
  * of a row) enters the tip condition only: the state stored for the failed step is the finite sweep of the last finite
  * iterate, and later steps whose own wrench is finite solve from it and may report 0 again - status 2 at t0 is the
  * only mark that the trajectory from there on is not the rod's.
+ * kr_simulate_batch_boundary: a non-finite base value (p0, h0, q0, w0 of bnd[b][t0]) enters the sweeps - the rod reports
+ * 0 before t0, KR_ST_NONFINITE at t0 and nonzero afterwards; a non-finite wrench value of bnd[b][t0] behaves as
+ * documented for loads; every other rod is bit for bit the clean call.
  * Every OTHER rod's status, tips, G and states are bit for bit those of the call without the bad value, in every kernel
  * family; on a ring its last three states are complete.  Nothing of a failed step stays behind in the handle's scratch,
  * the history workspace or (keep_predictor = 0) the predictor images; with keep_predictor = 1 the failing rod's own
@@ -435,12 +438,37 @@ int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_b
  * last_sim_path = 2, last_waves_per_rod = 1, last_overlap as for the table call.  Everything the table call refuses is
  * refused here with KR_E_UNSUPPORTED and a message that names the rule; no output buffer is touched.
  * NOT served with loads: a network bank, several wavefronts per rod, N > 128, RK4, one launch per step, kr_step_batch
- * (per-step launches take their wrench from kr_set_params).  A distributed load along the rod and a moving base are
- * outside this call.  The first call of a shape does the one-time host work kr_simulate_prepare does for
+ * (per-step launches take their wrench from kr_set_params).  A distributed load along the rod is outside this call
+ * (a moving base: kr_simulate_batch_boundary below).  The first call of a shape does the one-time host work kr_simulate_prepare does for
  * kr_simulate_batch itself. */
 int kr_simulate_batch_loads(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl,
                             const void* loads, void* states, int ring, void* G, void* tip, double tol, int maxit,
                             int32_t* status, int use_nn, const void* state_prev_init, int dtype, void* stream);
+
+/* ---- per-step boundary data: a moving base per rod --------------------- */
+/* The other half of the boundary data.  Every simulate call above freezes the base of the rod for the whole call: p0,
+ * h0, q0, w0 come from the handle or from the rod's table row.  In the reference they are plain attributes
+ * (cosserat_ode.py:44-47) that getResidualEuler reads at every solve (:194), exactly as it reads F_tip / M_tip: a
+ * caller whose rod sits on a moving platform, on a carriage or at the wrist of an arm assigns them between two steps of
+ * knode.simulate's loop (a base velocity q0 / w0 with a base that never moves is not a motion).
+ *
+ * kr_simulate_batch_loads with bnd[B][T][KR_BND] in place of loads: per rod and step p0 (3), h0 (4), q0 (3), w0 (3),
+ * F_tip (3), M_tip (3) - base and wrench in ONE array (the kernels have one pointer and one layout; a caller without a
+ * wrench history repeats the row's F_tip / M_tip in the last six columns).  The solve of step t (the one that reads
+ * ctl[b][t] and writes states[t+1]) uses bnd[b][t] for the base state and the tip condition - the reference with the
+ * six attributes assigned before that solve.  The values REPLACE those of the rod's row (they are not added to them),
+ * and h0 is NOT normalised, as in the reference.  Record 0 of states[t+1] then holds p0, h0, q0, w0 of step t exactly.
+ * states[0] is the caller's and need not agree with bnd[b][0] (the reference starts from the straight rod in the same
+ * way).  Element type = dtype, like ctl.  A call cut into pieces (state_prev_init, keep_predictor) slices bnd like ctl.
+ * t and bnd are required (KR_E_ARG without either).
+ * Served and refused: exactly as kr_simulate_batch_loads, with messages that name this call; no output buffer of a
+ * refused call is touched.  Afterwards last_sim_path = 2, last_waves_per_rod = 1, last_overlap as for the table call.
+ * Deriving q0 / w0 from a pose history is the caller's: the values are used as given, consistent or not.
+ * Failed steps: see FAILED STEPS at kr_simulate_batch. */
+#define KR_BND 19 /* p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3): the order of the cold block */
+int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl,
+                               const void* bnd, void* states, int ring, void* G, void* tip, double tol, int maxit,
+                               int32_t* status, int use_nn, const void* state_prev_init, int dtype, void* stream);
 
 /* ---- KNODE one-step-ahead training path -------------------------------- */
 /* CosseratRodTorch.parallelGetNextSegmentEuler (cosserat_ode_torch.py:401-437)

@@ -249,6 +249,7 @@ static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, int64_t T_s
   if (src.table) q.N = src.table->N;
   q.bank = src.bank;
   q.loads = src.loads != nullptr;
+  q.bnd = src.bnd != nullptr;
   q.prev_init = prev_init; q.states = states; q.slot_elems = (int64_t)slot;
   const SimPlan plan = plan_simulate<T>(h, q);
   if (plan.rc) return refuse_plan(plan);
@@ -1118,6 +1119,27 @@ int kr_simulate_batch_loads(kr_handle* h, const kr_param_table* t, int64_t T, in
   SimSrc src;
   src.table = t;
   src.loads = loads;
+  return dtype == KR_F32
+             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                    state_prev_init, s)
+             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                     state_prev_init, s);
+}
+
+// kr_simulate_batch_loads with the base state of every rod and step beside its wrench: bnd[B][T][KR_BND]
+int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, const void* bnd,
+                               void* states, int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
+                               const void* state_prev_init, int dtype, void* stream) {
+  KR_CHECK_PTR(t);
+  KR_CHECK_PTR(bnd);
+  KR_BATCH_PROLOGUE(t->B);
+  if (int rc = tab_matches(h, t)) return rc;
+  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
+  if (T == 0) return KR_OK;
+  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  SimSrc src;
+  src.table = t;
+  src.bnd = bnd;
   return dtype == KR_F32
              ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
                                     state_prev_init, s)

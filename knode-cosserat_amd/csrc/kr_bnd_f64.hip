@@ -1,0 +1,6 @@
+// double instantiation of the persistent kernels with per-rod parameter tables and per-step boundary data (kr_bnd_impl.hpp)
+#define KR_MS_NO_INST
+#include "kr_bnd_impl.hpp"
+namespace kr {
+template int launch_bnd_sim<double>(kr_handle*, const kr_param_table*, const double*, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
+}

@@ -302,6 +302,7 @@ struct PlanQuery {
   const void* states = nullptr;
   int64_t slot_elems = 0;
   bool loads = false;                  // kr_simulate_batch_loads: a table call with a tip-wrench history
+  bool bnd = false;                    // kr_simulate_batch_boundary: a table call with a base and tip-wrench history
 };
 template <typename T>
 SimPlan plan_simulate(const kr_handle* h, const PlanQuery& q);
@@ -350,6 +351,7 @@ struct SimSrc {
   const kr_mlp_bank* bank = nullptr;
   const int32_t* net_idx = nullptr;  // device copy of the caller's index array
   const void* loads = nullptr;       // kr_simulate_batch_loads: [B][T][6], element type of the call
+  const void* bnd = nullptr;         // kr_simulate_batch_boundary: [B][T][KR_BND], element type of the call
 };
 template <typename T>
 int launch_step(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);            // kr_sim_*.hip
@@ -376,6 +378,8 @@ int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk
                     const SimArgs<T>& a, const LaunchAt& at);                                    // kr_bank_*.hip
 template <typename T>
 int launch_load_sim(kr_handle* h, const kr_param_table* t, const T* loads, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_load_*.hip
+template <typename T>
+int launch_bnd_sim(kr_handle* h, const kr_param_table* t, const T* bnd, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bnd_*.hip
 int ensure_resume(kr_handle* h, int64_t B);
 int ensure_hist_ws(kr_handle* h, size_t bytes);
 
@@ -390,6 +394,7 @@ inline int launch_sim(kr_handle* h, const SimPlan& p, const SimSrc& src, SimArgs
     if (int rc = ensure_hist_ws(h, p.hist_ws_bytes)) return rc;
     a.hist_ws = static_cast<T*>(h->hist_ws);
   }
+  if (src.bnd) return launch_bnd_sim<T>(h, src.table, static_cast<const T*>(src.bnd), p, a, at);
   if (src.loads) return launch_load_sim<T>(h, src.table, static_cast<const T*>(src.loads), p, a, at);
   if (src.bank) return launch_bank_sim<T>(h, src.table, src.bank, src.net_idx, p, a, at);
   if (src.table) return launch_tab_sim<T>(h, src.table, p, a, at);

@@ -1641,6 +1641,9 @@ constexpr int MS_NPL = 2;  // grid points per lane held in registers by the pers
 // PSRC = RodTableLoads<T> (kr_load_impl.hpp): the tip wrench of step t is loads[rod][t] - six lanes put it where the
 // cold block keeps F_tip / M_tip before the step's first sweep (every reader of the wrench - the sweeps, the retry from
 // the warm start, the damped fallback - reads that block), once per step and outside the sweeps.
+// PSRC = RodTableBnd<T> (kr_bnd_impl.hpp): the same with the whole boundary, bnd[rod][t] = p0 h0 q0 w0 F_tip M_tip, in
+// the block's first 19 slots.  The base slots are read by ms_pred_guess (row 0 of Xs, before every solve of the step) and
+// by the damped fallback, both after the step's store; no sweep reads them from the block.
 template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1, typename PSRC = RodConst<T>, typename MSRC = MlpDev<T>>
 __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC Pa, const SimArgs<T> A, const MSRC Ma) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1713,13 +1716,18 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
   T tens[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) tens[k] = ctl[t0 * 4 + k];
-  constexpr bool LOADS = rod_src_has_loads<T, PSRC>::value;
-  const T* wrench = nullptr;  // loads only: [T_steps][6] of this rod
-  T wnext = T(0);             // ... lanes 0..5: the wrench of the coming step, requested one step ahead like the tensions
+  // the cold slots a step rewrites: [W0, W0 + WN) - the wrench (loads), the whole boundary (bnd) or none
+  using WSRC = rod_src_step_slots<T, PSRC>;
+  constexpr int W0 = WSRC::first, WN = WSRC::count;
+  constexpr bool LOADS = WN > 0;
+  static_assert(!LOADS || (W0 + WN == CD_TDIRS && (W0 == CD_FTIP || W0 == CD_P0)), "the per-step slots end with F_tip, M_tip");
+  const T* wrench = nullptr;  // loads only: [T_steps][WN] of this rod
+  T wnext = T(0);             // ... lanes 0..WN-1: the values of the coming step, requested one step ahead like the tensions
+  bool base_bad = false;      // bnd only: a base value of this or an earlier step was not finite
   if constexpr (LOADS) {
-    wrench = Pa.loads + rod * A.T_steps * 6;
+    wrench = WSRC::hist(Pa) + rod * A.T_steps * WN;
     if constexpr (!NN) {
-      if (lane < 6) wnext = wrench[t0 * 6 + lane];
+      if (lane < WN) wnext = wrench[t0 * WN + lane];
     }
   }
   wave_sync();
@@ -1747,7 +1755,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
     //  under the history records, instead of a step ahead - against sweeps of ~300 k cycles the wait does not show)
     T wcur = wnext;
     if constexpr (LOADS && NN) {
-      if (lane < 6) wcur = wrench[t * 6 + lane];
+      if (lane < WN) wcur = wrench[t * WN + lane];
     }
     // ---- history records from c12 (newest) and regP (the one before) ----------
 #pragma unroll
@@ -1773,11 +1781,26 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
       for (int k = 0; k < 4; ++k) tens[k] = ctl[(t + 1) * 4 + k];
     }
     if constexpr (LOADS) {  // (the fences of the start values below stand between this store and the first sweep)
-      if (lane < 6) {
-        L.cold[CD_FTIP + lane] = wcur;  // F_tip (3) and M_tip (3) are adjacent
+      if (lane < WN) {
+        L.cold[W0 + lane] = wcur;  // F_tip (3) and M_tip (3) are adjacent
         if constexpr (!NN) {
-          if (t + 1 < A.T_steps) wnext = wrench[(t + 1) * 6 + lane];
+          if (t + 1 < A.T_steps) wnext = wrench[(t + 1) * WN + lane];
         }
+      }
+      // (the base slots are read back by other lanes in ms_pred_guess, before any fence of the start values)
+      if constexpr (W0 < CD_FTIP) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // A base value that is not finite must show in the status.  h0, q0, w0 do by themselves; p0 would not: no
+        // equation reads p, so a NaN there fails the Newton update of the p rows and is then "solved" by the damped
+        // fallback, whose six unknowns do not see it - status 0 over positions that are NaN.  From such a step on the
+        // rod reports KR_ST_NONFINITE (knode_rod.h, "failed steps"); the overlapped kernel hands such a rod over here.
+        // (the test reads the exponent bits: a class compare of a double would be the one fp64 instruction the loop has
+        //  more than its loads twin's - tools/bnd_asm_compare.py)
+        bool inf_or_nan;
+        if constexpr (sizeof(T) == 8) inf_or_nan = (~__double2hiint((double)wcur) & 0x7ff00000) == 0;
+        else inf_or_nan = (~__float_as_int((float)wcur) & 0x7f800000) == 0;
+        base_bad = base_bad || __builtin_amdgcn_ballot_w64(lane < CD_FTIP && inf_or_nan) != 0;
       }
     }
     const int64_t inx = A.ring ? (t + 1) % 3 : t + 1;
@@ -1808,6 +1831,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
       const int it_plain = it;  // `iters` reports the plain and the damped phase together (knode_rod.h)
       status = ss_newton_damped<T, DIAG, SCHEME, HS, true, NN>(Pc, M, L, R, lane, C, S, it);
       it += it_plain;
+    }
+    if constexpr (W0 < CD_FTIP) {
+      if (base_bad && status == KR_ST_CONVERGED) status = KR_ST_NONFINITE;
     }
     if (lane == 0 && A.status) A.status[rod * A.T_steps + t] = status;
     ms_pred_update<T>(Q, order, status, A.predictor, lane, L.Xs, stamps);

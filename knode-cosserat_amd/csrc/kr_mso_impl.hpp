@@ -222,6 +222,10 @@ struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 
 // the part of the record area this kernel leaves unused (it keeps 12 of a record's HS slots, the odd tile).  Every read
 // of the wrench names the step it belongs to (cold_of), so a rejected verification, the rebuild, a plain step and a chord
 // update find their step's values whatever sweep they run in; a set is written once per step, at the hand-over.
+// PSRC = RodTableBnd<T> (kr_bnd_impl.hpp): the same with the whole boundary of step t, bnd[rod][t] = p0 h0 q0 w0 F_tip
+// M_tip: two sets of 19 slots, set 0 the cold block's first 19.  The base slots are read by ms_pred_guess only (row 0 of
+// the step's unknowns), which takes cold_of(its step); the areas Xs / XsB swap roles without a copy, so the step under
+// verification keeps the row 0 it was given.
 template <typename T, bool DIAG, int HS, int OCC = 1, typename PSRC = RodConst<T>>
 __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC Pa, const SimArgs<T> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -290,17 +294,28 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     }
     wave_sync();
   };
-  constexpr bool LOADS = rod_src_has_loads<T, PSRC>::value;
-  static_assert(!LOADS || HS >= 18, "the second wrench set lives behind the odd tile in the record area");
-  // the cold block as step t sees it: L.cold itself, or (loads, odd t) moved so that CD_FTIP .. + 5 fall on the second set
-  // (offset arithmetic like lead_of; only the six wrench slots may be read through it)
-  const ptrdiff_t wr_d = LOADS ? (L.hist + (size_t)N * 12) - (L.cold + CD_FTIP) : 0;
+  // the cold slots a step rewrites: [W0, W0 + WN) - the wrench (loads), the whole boundary (bnd) or none
+  using WSRC = rod_src_step_slots<T, PSRC>;
+  constexpr int W0 = WSRC::first, WN = WSRC::count;
+  constexpr bool LOADS = WN > 0;
+  static_assert(!LOADS || (W0 + WN == CD_TDIRS && (W0 == CD_FTIP || W0 == CD_P0)), "the per-step slots end with F_tip, M_tip");
+  // the second set lives behind the odd tile in the record area: N (HS - 12) free slots, and the planner serves
+  // N >= 2 MS_P + 1 (one_wave_range) - 54 (fp64) or 72 (fp32) slots for the 6 or 19 of a set
+  static_assert(!LOADS || (HS >= 18 && (2 * MS_P + 1) * (HS - 12) >= WN), "the second set lives behind the odd tile in the record area");
+  // the cold block as step t sees it: L.cold itself, or (loads, odd t) moved so that W0 .. W0 + WN - 1 fall on the second
+  // set (offset arithmetic like lead_of; only those slots may be read through it)
+  const ptrdiff_t wr_d = LOADS ? (L.hist + (size_t)N * 12) - (L.cold + W0) : 0;
   auto cold_of = [&](int t) -> const T* {
     if constexpr (LOADS) return L.cold + (ptrdiff_t)(t & 1) * wr_d;
     else return L.cold;
   };
-  const T* wrench = nullptr;  // loads only: [T_steps][6] of this rod
-  if constexpr (LOADS) wrench = Pa.loads + rod * A.T_steps * 6;
+  // where ms_pred_guess finds the base state of step t (row 0 of the unknowns): the step's set when a step rewrites it
+  auto base_of = [&](int t) -> const T* {
+    if constexpr (LOADS && W0 < CD_FTIP) return L.cold + (ptrdiff_t)(t & 1) * wr_d;
+    else return L.cold;
+  };
+  const T* wrench = nullptr;  // loads only: [T_steps][WN] of this rod
+  if constexpr (LOADS) wrench = WSRC::hist(Pa) + rod * A.T_steps * WN;
   const T* ctl = A.ctl + rod * A.T_steps * 4;
   auto load_fc = [&](int t) -> V3<T> {  // rhoA g + tendon force of step t (cosserat_ode.py:151,195)
     V3<T> tf{T(0), T(0), T(0)};
@@ -365,12 +380,13 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   // the hand-over of a step and the sweep that follows)
   V3<T> fcA = load_fc(0), fcB = fcA;
   V3<T> fcN = load_fc(T_steps > 1 ? 1 : 0);
-  T wN = T(0);  // loads, lanes 0..5: the wrench of step tA + 1, requested like fcN
+  T wN = T(0);  // loads, lanes 0..WN-1: the values of step tA + 1, requested like fcN
   if constexpr (LOADS) {
-    if (lane < 6) {
-      L.cold[CD_FTIP + lane] = wrench[lane];  // step 0 (set 0; the fences of the start values below come before any read)
-      wN = wrench[(size_t)(T_steps > 1 ? 1 : 0) * 6 + lane];
+    if (lane < WN) {
+      L.cold[W0 + lane] = wrench[lane];  // step 0 (set 0; the fences of the start values below come before any read)
+      wN = wrench[(size_t)(T_steps > 1 ? 1 : 0) * WN + lane];
     }
+    if constexpr (W0 < CD_FTIP) wave_sync_lds();  // (the base slots are read back by other lanes in ms_pred_guess)
   }
   // av = hk_a + hk_b v_h, au = hk_c u_h (diagonal material matrices): kept in registers so that forming a history
   // record inside a sweep does not go back to the parameter table
@@ -383,7 +399,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     hk_c[c] = -L.cold[CD_KBTI + 4 * c] * L.cold[CD_BBT + 4 * c];
   }
 
-  ms_pred_guess<T>(Q, order, lane, L.cold, Xs);
+  ms_pred_guess<T>(Q, order, lane, base_of(0), Xs);
   wave_sync_lds();
   if (order <= 0 && lane < 6) Xs[0 * MS_YP + 7 + lane] = Gguess;  // caller's guess (knode.py:67,89)
   wave_sync_lds();
@@ -898,7 +914,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         fcN = fcA;
         fcA = fcB;
         if constexpr (LOADS) {  // (set tA & 1 still holds this step's wrench; the next hand-over writes the other set again)
-          if (lane < 6) wN = wrench[(size_t)(tA + 1 < T_steps ? tA + 1 : tA) * 6 + lane];
+          if (lane < WN) wN = wrench[(size_t)(tA + 1 < T_steps ? tA + 1 : tA) * WN + lane];
         }
         order = orderB;
         it = itB;
@@ -1077,7 +1093,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       if (order > 0 && !retried) {
         retried = true;
         order = 0;
-        ms_pred_guess<T>(Q, 0, ln, L.cold, Xs);
+        ms_pred_guess<T>(Q, 0, ln, base_of(tA), Xs);
         wave_sync_lds();
         if (ln < 6) Xs[0 * MS_YP + 7 + ln] = Gguess;
         wave_sync_lds();
@@ -1116,13 +1132,14 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         if constexpr (LOADS) {
           // the step handed over above keeps set (tA - 1) & 1; the set written here last served step tA - 2, accepted
           // before this hand-over (the fences of the start values below come before any read)
-          if (lane < 6) {
-            L.cold[CD_FTIP + wr_d * (tA & 1) + lane] = wN;
-            wN = wrench[(size_t)(tA + 1 < T_steps ? tA + 1 : tA) * 6 + lane];
+          if (lane < WN) {
+            L.cold[W0 + wr_d * (tA & 1) + lane] = wN;
+            wN = wrench[(size_t)(tA + 1 < T_steps ? tA + 1 : tA) * WN + lane];
           }
+          if constexpr (W0 < CD_FTIP) wave_sync_lds();  // (the base slots are read back by other lanes in ms_pred_guess)
         }
         order = Q.next_order;
-        ms_pred_guess<T>(Q, order, lane, L.cold, Xs);
+        ms_pred_guess<T>(Q, order, lane, base_of(tA), Xs);
         wave_sync_lds();
         if (order <= 0 && lane < 6) Xs[0 * MS_YP + 7 + lane] = XsB[0 * MS_YP + 7 + lane];  // warm start: the G just found
         wave_sync_lds();

@@ -142,15 +142,17 @@ SimPlan plan_one_wave(const kr_handle* h, SimPlan p, const PlanQuery& q, int N, 
   return p;
 }
 
-// kr_simulate_batch_table / _bank / _loads (a table call whose tip wrench varies in time: the same plan, the loads
-// instantiations of the same kernels): the one-wavefront persistent kernels only, and a refusal (never the handle's own
+// kr_simulate_batch_table / _bank / _loads / _boundary (a table call whose tip wrench, or whose base state and tip
+// wrench, vary in time: the same plan, the loads or boundary instantiations of the same kernels): the one-wavefront persistent kernels only, and a refusal (never the handle's own
 // parameters or network) for everything they do not serve
 template <typename T>
 SimPlan plan_table(const kr_handle* h, const PlanQuery& q) {
   const bool bank = q.source == KR_SRC_BANK;
-  const char* const word = bank ? "bank" : q.loads ? "loads" : "table";
+  const char* const word = bank ? "bank" : q.bnd ? "boundary" : q.loads ? "loads" : "table";
   char what[128];
   auto refuse = [&](const char* w) {
+    if (q.bnd)
+      return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_boundary: %s (not served with per-step boundary data; nothing falls back to a frozen base or wrench)", w);
     if (q.loads)
       return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_loads: %s (not served with per-step tip loads; nothing falls back to a frozen wrench)", w);
     return bank ? refused(KR_E_UNSUPPORTED, "kr_simulate_batch_bank: %s (not served with a network bank; nothing falls back to the handle's MLP)", w)

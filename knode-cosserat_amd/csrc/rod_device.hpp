@@ -80,10 +80,30 @@ template <typename T>
 struct RodTableLoads : RodTable<T> {
   const T* loads;
 };
-template <typename T, typename PSRC>
-struct rod_src_has_loads { static constexpr bool value = false; };
+// A table plus a boundary history (kr_simulate_batch_boundary, kr_bnd_impl.hpp): bnd[B][T_steps][19] = p0 (3), h0 (4),
+// q0 (3), w0 (3), F_tip (3), M_tip (3) of rod b while it solves step t - the base state and the tip wrench, in the order
+// of the LDS cold block's first 19 slots - in place of those values of the rod's row.
 template <typename T>
-struct rod_src_has_loads<T, RodTableLoads<T>> { static constexpr bool value = true; };
+struct RodTableBnd : RodTable<T> {
+  const T* bnd;
+};
+// Which slots of the cold block (kr_ms_impl.hpp, CD_*) a step rewrites from a history that rides in the parameter source:
+// [first, first + count), read from hist(P)[rod][t][count].  count = 0: none, the block is filled once per launch.
+template <typename T, typename PSRC>
+struct rod_src_step_slots {
+  static constexpr int first = 0, count = 0;
+  static __device__ __forceinline__ const T* hist(const PSRC&) { return nullptr; }
+};
+template <typename T>
+struct rod_src_step_slots<T, RodTableLoads<T>> {
+  static constexpr int first = 13, count = 6;  // CD_FTIP, F_tip and M_tip
+  static __device__ __forceinline__ const T* hist(const RodTableLoads<T>& P) { return P.loads; }
+};
+template <typename T>
+struct rod_src_step_slots<T, RodTableBnd<T>> {
+  static constexpr int first = 0, count = 19;  // CD_P0 .. CD_MTIP + 3: the whole boundary
+  static __device__ __forceinline__ const T* hist(const RodTableBnd<T>& P) { return P.bnd; }
+};
 // What a persistent kernel takes as its first argument: the launch-uniform RodConst<T> by value (every rod alike), or a
 // RodTable<T>.  rod_src_row yields the constants of one rod for the kernel's arithmetic: the kernel argument itself,
 // or - table - a local copy of the rod's row, read ONCE, unconditionally, where the kernel starts: scalar loads (the

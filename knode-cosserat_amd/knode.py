@@ -185,6 +185,54 @@ def _tip_loads(tip_loads, B, T, check_finite=True):
     return np.ascontiguousarray(L)
 
 
+def _base_motion(base_motion, B, T, check_finite=True):
+    """``base[B, T, 13]`` (float64, contiguous) of ``simulate_batch(..., base_motion=...)`` from ``[B, T, 13]`` or
+    ``[T, 13]`` (one history for all rods), columns ``p0 (3) h0 (4) q0 (3) w0 (3)``; host-side validation only (no device
+    call)."""
+    try:
+        M = np.asarray(base_motion, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise kn.KrError("simulate_batch: base_motion must be a numeric array [B, T, 13] or [T, 13]") from None
+    if M.ndim == 2:
+        if M.shape != (T, 13):
+            raise kn.KrError(f"simulate_batch: base_motion must be [T, 13] = [{T}, 13] (p0, h0, q0, w0 per step); got {M.shape}")
+        M = np.broadcast_to(M[None], (B, T, 13))
+    elif M.ndim == 3:
+        if M.shape[0] != B:
+            raise kn.KrError(f"simulate_batch: base_motion holds {M.shape[0]} rods, ctl {B}")
+        if M.shape[1:] != (T, 13):
+            raise kn.KrError(f"simulate_batch: base_motion must be [B, T, 13] = [{B}, {T}, 13] (p0, h0, q0, w0 per step); got {M.shape}")
+    else:
+        raise kn.KrError(f"simulate_batch: base_motion must be [B, T, 13] or [T, 13]; got shape {M.shape}")
+    # (check_finite=False: a base value that is not finite is ordinary input to the library, knode_rod.h "failed steps";
+    #  h0 is used as given - not normalised, as in the reference - so only the quaternion that is no rotation at all is
+    #  refused here)
+    if check_finite:
+        if not np.isfinite(M).all():
+            b, t, _ = np.argwhere(~np.isfinite(M))[0]
+            raise kn.KrError(f"simulate_batch: base_motion is not finite at rod {b}, step {t}")
+        zero = ~M[:, :, 3:7].any(axis=2)
+        if zero.any():
+            b, t = np.argwhere(zero)[0]
+            raise kn.KrError(f"simulate_batch: base_motion has a zero quaternion h0 at rod {b}, step {t}")
+    return np.ascontiguousarray(M)
+
+
+def _boundary(base, loads, rows):
+    """``bnd[B, T, KR_BND]`` of a boundary call: the base history, then the wrench history or - without one - each rod's
+    own ``F_tip`` / ``M_tip`` (``rows``: the KrParams of the rods) on every step."""
+    B, T = base.shape[0], base.shape[1]
+    bnd = np.empty((B, T, kn.KR_BND), dtype=np.float64)
+    bnd[:, :, :13] = base
+    if loads is not None:
+        bnd[:, :, 13:] = loads
+    else:
+        for b, p in enumerate(rows):
+            bnd[b, :, 13:16] = np.asarray(p.F_tip[:], dtype=np.float64)
+            bnd[b, :, 16:19] = np.asarray(p.M_tip[:], dtype=np.float64)
+    return bnd
+
+
 def _score_reference(robot, score, B, T, tip_only):
     """``(reference[R, Tr, >=7, N], point)`` of ``simulate_batch(..., score=...)``, R = 1 or B; host-side validation only
     (no device call)."""
@@ -216,7 +264,7 @@ def _score_reference(robot, score, B, T, tip_only):
 
 
 def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
-                   robots=None, per_robot_nn=False, score=None, tip_loads=None, check_finite=True):
+                   robots=None, per_robot_nn=False, score=None, tip_loads=None, check_finite=True, base_motion=None):
     """B rods, each with its own tension history.
 
     robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
@@ -247,15 +295,31 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     assigned before that solve.  The values replace the robot's own wrench; with ``robots=`` row b keeps everything else.
     Composes with ``score`` and ``tip_only``; not served with ``per_robot_nn``.
 
-    check_finite: True (default) refuses ``tip_loads`` that are not finite before anything touches the device; False hands
-    them to the library, for which they are ordinary input (domain randomisation, a diverging row of a sweep).
+    base_motion: a base that moves in time, [B, T, 13] or [T, 13] (shared by all rods), columns ``p0 (3) h0 (4) q0 (3)
+    w0 (3)``: rod b solves step t with that base state - the reference with ``robot.p0 / h0 / q0 / w0`` assigned before
+    that solve (a platform, a carriage, the wrist of an arm).  The values replace the robot's own; ``h0`` is not
+    normalised; record 0 of state t + 1 holds them exactly.  The caller supplies consistent ``q0`` / ``w0``.  Composes
+    with ``robots``, ``tip_loads`` (without it every rod keeps its own ``F_tip`` / ``M_tip``), ``score`` and ``tip_only``;
+    not served with ``per_robot_nn``.
+
+    check_finite: True (default) refuses ``tip_loads`` / ``base_motion`` that are not finite (and a zero ``h0``) before
+    anything touches the device; False hands them to the library, for which they are ordinary input (domain randomisation,
+    a diverging row of a sweep).
 
     Failed steps (knode_rod.h): a rod whose inputs stop being finite at step t0 reports ``status`` 2 at t0; the call returns
     normally and every other rod's outputs are bit for bit those of the batch without the failure.  Where the value enters
     the sweeps (a NaN tension or rod parameter) the rod's states, tips, ``dtw`` and ``mse`` are NaN from there on and every
     later step reports a nonzero status.  A NaN tip wrench (``tip_loads``, ``F_tip`` / ``M_tip``) enters the tip condition
-    only: states and scores stay finite and later steps may report 0 again - ``status`` 2 at t0 is the only mark."""
-    loads = None
+    only: states and scores stay finite and later steps may report 0 again - ``status`` 2 at t0 is the only mark.  A NaN
+    base value (``base_motion``) enters the sweeps like a NaN tension."""
+    loads = base = None
+    if base_motion is not None:  # (validated on the host before anything touches the device)
+        if per_robot_nn:
+            raise kn.KrError("simulate_batch: base_motion with per_robot_nn=True is not served (per-step boundary data has no network-bank form)")
+        ctl_shape = np.asarray(ctl).shape
+        if len(ctl_shape) != 3:
+            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+        base = _base_motion(base_motion, int(ctl_shape[0]), int(ctl_shape[1]), check_finite)
     if tip_loads is not None:  # (validated on the host before anything touches the device)
         if per_robot_nn:
             raise kn.KrError("simulate_batch: tip_loads with per_robot_nn=True is not served (per-step tip loads have no network-bank form)")
@@ -275,6 +339,9 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         rows = _robots_rows(robot, robots, int(np.asarray(ctl).shape[0]))
     elif loads is not None:  # only the loads vary: a table of identical rows
         rows = _robots_rows(robot, [robot] * loads.shape[0], loads.shape[0])
+    elif base is not None:  # only the base varies
+        rows = _robots_rows(robot, [robot] * base.shape[0], base.shape[0])
+    bnd = _boundary(base, loads, rows) if base is not None else None  # (tip_loads alone stays a loads call)
     if per_robot_nn:
         if robots is None:
             raise kn.KrError("simulate_batch: per_robot_nn needs robots=[...]")
@@ -293,10 +360,11 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     G = torch.zeros((B, 6), dtype=tdt, device=dev)  # knode.py:67
     tip = torch.empty((B, T, 3), dtype=tdt, device=dev)
     status = torch.zeros((B, T), dtype=torch.int32, device=dev)
-    loads_t = torch.as_tensor(loads, device=dev).to(tdt).contiguous() if loads is not None else None
+    loads_t = torch.as_tensor(loads, device=dev).to(tdt).contiguous() if loads is not None and bnd is None else None
+    bnd_t = torch.as_tensor(bnd, device=dev).to(tdt).contiguous() if bnd is not None else None
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
                scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
-               table=table, bank=bank, net_of_rod=net_of_rod, loads=loads_t)
+               table=table, bank=bank, net_of_rod=net_of_rod, loads=loads_t, bnd=bnd_t)
     if score is not None:  # queued behind the run; the copies below wait for both
         Tr = score_ref.shape[1]
         ref_states = h.pack_poses(score_ref, tdt)  # [Tr, 1 or B, N, KR_SLOTS], packed once

@@ -25,6 +25,7 @@ ACT_NONE, ACT_TANH, ACT_SOFTPLUS, ACT_RELU, ACT_ELU = range(5)
 ST_CONVERGED, ST_MAXIT, ST_NONFINITE = 0, 1, 2
 KR_MAX_LAYERS = 8
 KR_DTW_MAX_LEN = 4096
+KR_BND = 19  # p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) per rod and step (kr_simulate_batch_boundary)
 KR_E_ARG, KR_E_UNSUPPORTED = -1, -4
 
 # reference row (0..24 of [y; z]) -> packed slot, see knode_rod.h
@@ -103,6 +104,8 @@ _PROTOS = {
     "kr_simulate_batch_table": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int, _vp]),
     "kr_simulate_batch_loads": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int,
                                        _vp]),
+    "kr_simulate_batch_boundary": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int,
+                                          _vp]),
     "kr_mlp_bank_check": (_int, [C.POINTER(KrParams), _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kr_mlp_bank_create": (_int, [_vp, _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _int, _vp,
                                   C.POINTER(_vp)]),
@@ -551,8 +554,23 @@ class Handle:
         check(self.lib.kr_set_option(self._h, name.encode(), int(value)))
 
     def simulate(self, ctl, states, G, ring=False, tip=None, status=None, scheme=KR_EULER, tol=0.0, maxit=0,
-                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None, loads=None):
+                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None, loads=None, bnd=None):
         B, T = ctl.shape[0], ctl.shape[1]
+        if bnd is not None:  # rod b, step t: bnd[b, t] = p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) in place of its row's
+            if bank is not None or net_of_rod is not None:
+                raise KrError("bnd= together with bank=: per-step boundary data is not served with a network bank")
+            if loads is not None:
+                raise KrError("bnd= together with loads=: the last six columns of bnd are the tip wrench")
+            if table is None:
+                raise KrError("a boundary call needs table= (a table of identical rows when only the boundary varies)")
+            if B != table.B:
+                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
+            if tuple(bnd.shape) != (B, T, KR_BND) or bnd.dtype != ctl.dtype or not bnd.is_contiguous():
+                raise KrError(f"bnd must be a contiguous [{B}, {T}, {KR_BND}] tensor of {ctl.dtype}; got {tuple(bnd.shape)} {bnd.dtype}")
+            check(self.lib.kr_simulate_batch_boundary(self._h, table._t, T, scheme, _ptr(ctl), _ptr(bnd), _ptr(states),
+                                                      int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
+                                                      int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+            return
         if loads is not None:  # rod b, step t: tip wrench loads[b, t] = F_tip (3), M_tip (3) in place of its row's
             if bank is not None or net_of_rod is not None:
                 raise KrError("loads= together with bank=: per-step tip loads are not served with a network bank")
