@@ -302,7 +302,7 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
  * which makes a second call continue a run exactly (it may point into the ring).
  * When the multiple-shooting kernel applies (see kr_set_option) all T steps run
  * in ONE launch: every wavefront keeps its rod's history in LDS / registers.
- * FAILED STEPS (this call and its table / bank / loads / boundary forms).  Values that are not finite are ordinary input: the call
+ * FAILED STEPS (this call and its table / bank / loads / boundary / key-point forms).  Values that are not finite are ordinary input: the call
  * returns KR_OK and every entry of status[B][T] is written.  A rod whose inputs stop being finite at step t0 (a NaN
  * tension or tip load of that step; a NaN parameter of its table row: t0 = 0) reports 0 before t0 and KR_ST_NONFINITE at
  * t0, whichever kernel family runs the call; a finite input that overflows the arithmetic reports a nonzero status at
@@ -318,6 +318,9 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
  * kr_simulate_batch_boundary: a non-finite base value (p0, h0, q0, w0 of bnd[b][t0]) enters the sweeps - the rod reports
  * 0 before t0, KR_ST_NONFINITE at t0 and nonzero afterwards; a non-finite wrench value of bnd[b][t0] behaves as
  * documented for loads; every other rod is bit for bit the clean call.
+ * kr_simulate_batch_keypoints: kp follows the states it copies.  Every kp[t][b][k] is written for every rod and step; a
+ * rod that fails at t0 has, in kp[0 .. t0 - 1], the clean run's records bit for bit, and from t0 on what its states hold
+ * (NaN where the bad value enters the sweeps); every other rod's records are bit for bit those of the clean call.
  * Every OTHER rod's status, tips, G and states are bit for bit those of the call without the bad value, in every kernel
  * family; on a ring its last three states are complete.  Nothing of a failed step stays behind in the handle's scratch,
  * the history workspace or (keep_predictor = 0) the predictor images; with keep_predictor = 1 the failing rod's own
@@ -469,6 +472,36 @@ int kr_simulate_batch_loads(kr_handle* h, const kr_param_table* t, int64_t T, in
 int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl,
                                const void* bnd, void* states, int ring, void* G, void* tip, double tol, int maxit,
                                int32_t* status, int use_nn, const void* state_prev_init, int dtype, void* stream);
+
+/* ---- key-point records: states at chosen grid points from a tip-only run -- */
+/* A simulate call returns the full history (states[T + 1][B][N][KR_SLOTS]: 22.9 MB per step at B = 1024, N = 100, fp64)
+ * or, on a 3-slot ring, the tip positions and the last three states; interior steps of a ring run store only the twelve
+ * leading slots of each record.  What is computed from a trajectory - the metrics below (kr_dtw_batch,
+ * kr_pose_mse_points_batch), the reference's key points ([3, 5, 7, 9], [2, 6, 9], markers [1, 3, 6, 9]), a tip
+ * orientation - needs the states at a few grid points for every step.
+ *
+ * kr_simulate_batch_boundary with one more output, kp[T][B][K][KR_SLOTS]: kp[t][b][k] is the complete record, pad zeros
+ * included, of grid point idx[k] of the state step t writes - what a full-history call leaves in states[t + 1][b][idx[k]],
+ * bit for bit, on a ring as with the full history.  Element type = dtype; kp must be 16-byte aligned.
+ * idx_host: K grid points on the HOST, 1 <= K <= KR_KEYPOINTS_MAX, strictly increasing, each in [0, N) (the kernels find
+ * the place of a marked point by counting the marked points below it).  Anything else: KR_E_ARG with a message that names
+ * the first bad entry, decided on the host before anything is copied or launched; no output buffer is touched.
+ * kr_keypoints_check applies the same rule without a handle (host arithmetic only, like kr_param_table_check).
+ * t, bnd and kp are required (KR_E_ARG without one); a caller with a fixed boundary repeats the row's p0 h0 q0 w0 F_tip
+ * M_tip on every step, as advised above.  tip, status, G, states (ring or full), keep_predictor and state_prev_init mean
+ * what they mean for the boundary call; a call cut into pieces slices kp like tip (kp is time-major: a piece of n steps
+ * from step t0 writes kp + t0 * B * K * KR_SLOTS).  A sweep that is later rejected has written its key points and the
+ * sweep that replaces it overwrites them, like the tip: nothing of a rejected sweep stays in kp.
+ * Served and refused: exactly as kr_simulate_batch_boundary, with messages that name this call; no output buffer of a
+ * refused call is touched.  Afterwards last_sim_path = 2, last_waves_per_rod = 1, last_overlap as for the table call.
+ * NO key-point form: a network bank, several wavefronts per rod, N > 128, RK4, one launch per step.
+ * Failed steps: see FAILED STEPS at kr_simulate_batch. */
+#define KR_KEYPOINTS_MAX 16
+int kr_keypoints_check(int N, int K, const int32_t* idx_host);
+int kr_simulate_batch_keypoints(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl,
+                                const void* bnd, int K, const int32_t* idx_host, void* kp,
+                                void* states, int ring, void* G, void* tip, double tol, int maxit, int32_t* status,
+                                int use_nn, const void* state_prev_init, int dtype, void* stream);
 
 /* ---- KNODE one-step-ahead training path -------------------------------- */
 /* CosseratRodTorch.parallelGetNextSegmentEuler (cosserat_ode_torch.py:401-437)
@@ -653,8 +686,8 @@ int kr_estimate_state(kr_handle* h, int64_t T, const double* data, const double*
  * (physics_multitrain.py:213-222, physics_train.py:136-167), as device kernels that read the packed states where a
  * simulate call left them: two doubles per rod come back instead of a trajectory.
  * All metric arithmetic is fp64 whatever `dtype`, which is only the element type of the inputs; outputs are double.
- * Both calls use none of the handle's scratch; kr_pose_mse_batch takes N from the handle, kr_dtw_batch reads no
- * parameter at all.
+ * The calls use none of the handle's scratch; kr_pose_mse_batch takes N from the handle, kr_pose_mse_points_batch
+ * and kr_dtw_batch read no parameter at all.
  * FastDTW (what the reference calls) is NOT built on the device: it needs the warp path traced back on every level of
  * its pyramid, its parity with the third-party package is unpinned in this project anyway (krod_eval.py), and the
  * exact distance below is the quantity it approximates (and a lower bound of it). */
@@ -665,7 +698,8 @@ int kr_estimate_state(kr_handle* h, int64_t T, const double* data, const double*
  * without FastDTW's coarse-path restriction).  Sample i of rod b of sequence a is the 3 consecutive elements at
  * a + b*a_rod_stride + i*a_step_stride (strides in ELEMENTS, >= 0; rod stride 0 = one sequence shared by all rods).
  * This reads simulate's tip[B][T][3] (rod T*3, step 3) and equally one grid point of a full state history
- * states[T+1][B][N][KR_SLOTS] (pointer to slot 12 of that point in states[0]; rod N*KR_SLOTS, step B*N*KR_SLOTS).
+ * states[T+1][B][N][KR_SLOTS] (pointer to slot 12 of that point in states[0]; rod N*KR_SLOTS, step B*N*KR_SLOTS),
+ * or one key point of kp[T][B][K][KR_SLOTS] (pointer to slot 12 of kp[0][0][k]; rod K*KR_SLOTS, step B*K*KR_SLOTS).
  * dist[B].
  * The recurrence is cost = (|dx| + |dy|) + |dz|, D = cost + min(min(up, left), diag) in exactly this order: the
  * result is bit-identical to krod_eval.dtw_distance on the same (upcast) samples.  A NaN sample is not propagated the
@@ -690,6 +724,11 @@ int kr_dtw_batch(kr_handle* h, int64_t B,
  * The sums are formed in a fixed order without atomics: a call is reproducible bit for bit. */
 int kr_pose_mse_batch(kr_handle* h, int64_t B, int64_t T, const void* states, const void* ref_states,
                       int64_t ref_B, double* mse, double* parts, int dtype, void* stream);
+/* The same with the number of points per rod as an argument instead of the handle's N: records[T][B][P][KR_SLOTS],
+ * ref_records[T][ref_B][P][KR_SLOTS] - the kp of kr_simulate_batch_keypoints (P = K) against a reference gathered at the
+ * same points.  With P = N it returns bit for bit what kr_pose_mse_batch returns. */
+int kr_pose_mse_points_batch(kr_handle* h, int64_t B, int64_t T, int64_t P, const void* records, const void* ref_records,
+                             int64_t ref_B, double* mse, double* parts, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -250,6 +250,7 @@ static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, int64_t T_s
   q.bank = src.bank;
   q.loads = src.loads != nullptr;
   q.bnd = src.bnd != nullptr;
+  q.kp = src.kp.kp != nullptr;
   q.prev_init = prev_init; q.states = states; q.slot_elems = (int64_t)slot;
   const SimPlan plan = plan_simulate<T>(h, q);
   if (plan.rc) return refuse_plan(plan);
@@ -1140,6 +1141,67 @@ int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T,
   SimSrc src;
   src.table = t;
   src.bnd = bnd;
+  return dtype == KR_F32
+             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                    state_prev_init, s)
+             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
+                                     state_prev_init, s);
+}
+
+// the rule of kr_keypoints_check; `lo` / `hi` receive the mask of the marked grid points (bit j = grid point j)
+static int keypoints_mask(const char* who, int N, int K, const int32_t* idx, unsigned long long& lo, unsigned long long& hi) {
+  lo = hi = 0;
+  const std::string w = std::string(who) + ": ";
+  if (K < 1 || K > KR_KEYPOINTS_MAX) {
+    set_error(w + "K = " + std::to_string(K) + ", a call takes 1 <= K <= " + std::to_string(KR_KEYPOINTS_MAX) + " key points");
+    return KR_E_ARG;
+  }
+  if (!idx) { set_error(w + "null pointer argument: idx"); return KR_E_ARG; }
+  if (N < 1 || N > 128) { set_error(w + "N = " + std::to_string(N) + ", key points are served for N <= 128"); return KR_E_ARG; }
+  for (int k = 0; k < K; ++k) {
+    const long long j = idx[k];
+    if (j < 0 || j >= N) {
+      set_error(w + "idx[" + std::to_string(k) + "] = " + std::to_string(j) + " lies outside [0, N) = [0, " + std::to_string(N) + ")");
+      return KR_E_ARG;
+    }
+    if (k > 0 && j <= idx[k - 1]) {
+      set_error(w + "idx[" + std::to_string(k) + "] = " + std::to_string(j) + " does not exceed idx[" + std::to_string(k - 1) + "] = " +
+                std::to_string((long long)idx[k - 1]) + " (the key points must be strictly increasing)");
+      return KR_E_ARG;
+    }
+    (j < 64 ? lo : hi) |= 1ull << (j & 63);
+  }
+  return KR_OK;
+}
+
+int kr_keypoints_check(int N, int K, const int32_t* idx_host) {
+  unsigned long long lo, hi;
+  return keypoints_mask("kr_keypoints_check", N, K, idx_host, lo, hi);
+}
+
+// kr_simulate_batch_boundary that also writes kp[T][B][K][KR_SLOTS], the records of the K marked grid points of every step
+int kr_simulate_batch_keypoints(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, const void* bnd,
+                                int K, const int32_t* idx_host, void* kp, void* states, int ring, void* G, void* tip, double tol,
+                                int maxit, int32_t* status, int use_nn, const void* state_prev_init, int dtype, void* stream) {
+  static const char* const NAME = "kr_simulate_batch_keypoints";
+  KR_CHECK_H(h);
+  if (!t || !bnd || !kp) {
+    set_error(std::string(NAME) + ": null pointer argument: " + (!t ? "t" : !bnd ? "bnd" : "kp") +
+              " (a caller with a fixed boundary repeats the row's values)");
+    return KR_E_ARG;
+  }
+  SimSrc src;
+  if (int rc = keypoints_mask(NAME, t->N, K, idx_host, src.kp.mask_lo, src.kp.mask_hi)) return rc;
+  if ((uintptr_t)kp & 15) { set_error(std::string(NAME) + ": kp must be 16-byte aligned"); return KR_E_ARG; }
+  KR_BATCH_PROLOGUE(t->B);
+  if (int rc = tab_matches(h, t)) return rc;
+  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
+  if (T == 0) return KR_OK;
+  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  src.table = t;
+  src.bnd = bnd;
+  src.kp.kp = kp;
+  src.kp.K = K;
   return dtype == KR_F32
              ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
                                     state_prev_init, s)

@@ -303,6 +303,7 @@ struct PlanQuery {
   int64_t slot_elems = 0;
   bool loads = false;                  // kr_simulate_batch_loads: a table call with a tip-wrench history
   bool bnd = false;                    // kr_simulate_batch_boundary: a table call with a base and tip-wrench history
+  bool kp = false;                     // kr_simulate_batch_keypoints: a boundary call that also writes key-point records
 };
 template <typename T>
 SimPlan plan_simulate(const kr_handle* h, const PlanQuery& q);
@@ -344,6 +345,13 @@ inline int launch(hipStream_t s, void (*kern)(P...), dim3 grid, dim3 block, size
   return launch(LaunchAt{s, false}, kern, grid, block, smem, args...);
 }
 
+// kr_simulate_batch_keypoints: kp[T][B][K][KR_SLOTS] of the call's element type and the marked grid points, bit j of
+// (mask_lo, mask_hi) = grid point j (kp == nullptr: no key points)
+struct KpDst {
+  void* kp = nullptr;
+  int K = 0;
+  unsigned long long mask_lo = 0, mask_hi = 0;
+};
 // The launchers: each maps a plan to the template instantiation it names and launches it, in the unit that holds the
 // kernel.
 struct SimSrc {
@@ -352,6 +360,7 @@ struct SimSrc {
   const int32_t* net_idx = nullptr;  // device copy of the caller's index array
   const void* loads = nullptr;       // kr_simulate_batch_loads: [B][T][6], element type of the call
   const void* bnd = nullptr;         // kr_simulate_batch_boundary: [B][T][KR_BND], element type of the call
+  KpDst kp;                          // kr_simulate_batch_keypoints (with bnd): where the key-point records go
 };
 template <typename T>
 int launch_step(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);            // kr_sim_*.hip
@@ -380,6 +389,9 @@ template <typename T>
 int launch_load_sim(kr_handle* h, const kr_param_table* t, const T* loads, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_load_*.hip
 template <typename T>
 int launch_bnd_sim(kr_handle* h, const kr_param_table* t, const T* bnd, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bnd_*.hip
+template <typename T>
+int launch_kp_sim(kr_handle* h, const kr_param_table* t, const T* bnd, const KpDst& kd, const SimPlan& p, const SimArgs<T>& a,
+                  const LaunchAt& at);  // kr_kp_*.hip
 int ensure_resume(kr_handle* h, int64_t B);
 int ensure_hist_ws(kr_handle* h, size_t bytes);
 
@@ -394,6 +406,7 @@ inline int launch_sim(kr_handle* h, const SimPlan& p, const SimSrc& src, SimArgs
     if (int rc = ensure_hist_ws(h, p.hist_ws_bytes)) return rc;
     a.hist_ws = static_cast<T*>(h->hist_ws);
   }
+  if (src.bnd && src.kp.kp) return launch_kp_sim<T>(h, src.table, static_cast<const T*>(src.bnd), src.kp, p, a, at);
   if (src.bnd) return launch_bnd_sim<T>(h, src.table, static_cast<const T*>(src.bnd), p, a, at);
   if (src.loads) return launch_load_sim<T>(h, src.table, static_cast<const T*>(src.loads), p, a, at);
   if (src.bank) return launch_bank_sim<T>(h, src.table, src.bank, src.net_idx, p, a, at);

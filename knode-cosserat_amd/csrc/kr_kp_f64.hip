@@ -1,0 +1,6 @@
+// double instantiation of the persistent kernels with per-step boundary data and key-point records (kr_kp_impl.hpp)
+#define KR_MS_NO_INST
+#include "kr_kp_impl.hpp"
+namespace kr {
+template int launch_kp_sim<double>(kr_handle*, const kr_param_table*, const double*, const KpDst&, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
+}

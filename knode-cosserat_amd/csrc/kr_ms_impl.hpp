@@ -333,6 +333,19 @@ struct MsSolveArgs {
   // such sweeps in a row the next one is a full one again.
   bool bo_allowed = false;
 };
+// The same for the key-point kernels (kr_kp_impl.hpp): where every sweep that streams a record into out_rod also puts the
+// records of the marked grid points of this step, [K][KR_SLOTS], and the wavefront-uniform mask of the marked points
+// (store_keypoint, kr_sim_impl.hpp).  A type of its own: the solves below (ms_newton, ss_newton_damped) deduce it from
+// their argument and are compiled for it apart; every other kernel keeps MsSolveArgs<T> and the code it had.
+template <typename T>
+struct MsSolveArgsKp : MsSolveArgs<T> {
+  T* kp = nullptr;
+  unsigned long long kp_lo = 0, kp_hi = 0;
+};
+template <typename SA>
+struct ms_solve_has_kp { static constexpr bool value = false; };
+template <typename T>
+struct ms_solve_has_kp<MsSolveArgsKp<T>> { static constexpr bool value = true; };
 
 // Scaled maximum norm of the residual of a sweep - the interface jumps E_g - Y_{g+1} (19 rows each) and the tip
 // condition - from the end states of the unperturbed lanes in Es: one component per lane, 3 x 19 + 6 = 63 lanes.
@@ -356,10 +369,10 @@ __device__ __forceinline__ float ms_residual_norm(const T* Es, const T* Xs, cons
 // Newton iteration on (G, Y_1..Y_{P-1}) for one rod = one wavefront.  On entry L.hist holds the
 // history records and L.Xs the initial guess (visible to all lanes).  Returns the status; `it`
 // = sweeps used.  On exit L.Xs holds the accepted unknowns.
-template <typename T, bool DIAG, int SCHEME, int HS, bool PERSIST, bool NN>
+// (SA, deduced from S: MsSolveArgs<T>, or MsSolveArgsKp<T> with key-point records)
+template <typename T, bool DIAG, int SCHEME, int HS, bool PERSIST, bool NN, typename SA>
 __device__ __forceinline__ int ms_newton(const RodConst<T>& Pc, const MlpDev<T>& M, const MsLds<T>& L, const MsRole& R,
-                                         int lane, const SweepCtx<T, HS>& C, MsSolveArgs<T>& S, int& it,
-                                         MsStamps& stamps) {
+                                            int lane, const SweepCtx<T, HS>& C, SA& S, int& it, MsStamps& stamps) {
   const int N = Pc.N;
 #ifdef KR_MS_STAMPS
   unsigned long long tq;
@@ -465,6 +478,7 @@ __device__ __forceinline__ int ms_newton(const RodConst<T>& Pc, const MlpDev<T>&
           T rec[KR_SLOTS];
           record_from(y, v, u, rec);
           if (S.out_rod) store_record(S.out_rod + (size_t)j * KR_SLOTS, rec);
+          if constexpr (ms_solve_has_kp<SA>::value) store_keypoint(S.kp, S.kp_lo, S.kp_hi, j, rec);
           if constexpr (PERSIST) {
             T lead[12];
 #pragma unroll
@@ -527,6 +541,7 @@ __device__ __forceinline__ int ms_newton(const RodConst<T>& Pc, const MlpDev<T>&
       T rec[KR_SLOTS];
       record_from(y, S.vlast, S.ulast, rec);
       if (S.out_rod) store_record(S.out_rod + (size_t)(N - 1) * KR_SLOTS, rec);
+      if constexpr (ms_solve_has_kp<SA>::value) store_keypoint(S.kp, S.kp_lo, S.kp_hi, N - 1, rec);
       if constexpr (PERSIST) {
         T lead[12];
 #pragma unroll
@@ -999,10 +1014,9 @@ __device__ __forceinline__ int ms_newton(const RodConst<T>& Pc, const MlpDev<T>&
 // every sweep; the sweep whose full Newton update is below the tolerance is the accepted one.  58 lanes idle along
 // the N - 1 dependent grid points: this path is for robustness, not speed.  Leaves L.Xs consistent with the result.
 // ---------------------------------------------------------------------------
-template <typename T, bool DIAG, int SCHEME, int HS, bool PERSIST, bool NN>
+template <typename T, bool DIAG, int SCHEME, int HS, bool PERSIST, bool NN, typename SA>
 __device__ __forceinline__ int ss_newton_damped(const RodConst<T>& Pc, const MlpDev<T>& M, const MsLds<T>& L,
-                                                const MsRole& R, int lane, const SweepCtx<T, HS>& C, MsSolveArgs<T>& S,
-                                                int& it) {
+                                                   const MsRole& R, int lane, const SweepCtx<T, HS>& C, SA& S, int& it) {
   const int N = Pc.N;
   const int col = lane < 7 ? lane : 0;  // lanes 7.. duplicate the unperturbed column and store nothing
   T G[6], Gold[6], d[6];
@@ -1043,6 +1057,7 @@ __device__ __forceinline__ int ss_newton_damped(const RodConst<T>& Pc, const Mlp
         T rec[KR_SLOTS];
         record_from(y, v, u, rec);
         if (S.out_rod) store_record(S.out_rod + (size_t)j * KR_SLOTS, rec);
+        if constexpr (ms_solve_has_kp<SA>::value) store_keypoint(S.kp, S.kp_lo, S.kp_hi, j, rec);
         if constexpr (PERSIST) {
           T lead[12];
 #pragma unroll
@@ -1085,6 +1100,7 @@ __device__ __forceinline__ int ss_newton_damped(const RodConst<T>& Pc, const Mlp
       T rec[KR_SLOTS];
       record_from(y, S.vlast, S.ulast, rec);
       if (S.out_rod) store_record(S.out_rod + (size_t)(N - 1) * KR_SLOTS, rec);
+      if constexpr (ms_solve_has_kp<SA>::value) store_keypoint(S.kp, S.kp_lo, S.kp_hi, N - 1, rec);
       if constexpr (PERSIST) {
         T lead[12];
 #pragma unroll
@@ -1644,6 +1660,10 @@ constexpr int MS_NPL = 2;  // grid points per lane held in registers by the pers
 // PSRC = RodTableBnd<T> (kr_bnd_impl.hpp): the same with the whole boundary, bnd[rod][t] = p0 h0 q0 w0 F_tip M_tip, in
 // the block's first 19 slots.  The base slots are read by ms_pred_guess (row 0 of Xs, before every solve of the step) and
 // by the damped fallback, both after the step's store; no sweep reads them from the block.
+// PSRC = RodTableBndKp<T> (kr_kp_impl.hpp): the boundary kernel that also writes kp[t][rod][k], the complete record of
+// the k-th marked grid point of the state step t writes, at every site that streams that record into the state - the
+// storing sweeps of ms_newton (MLP off and on), their last grid point, the damped fallback - so a sweep that replaces
+// a rejected one overwrites its key points as it overwrites its records and its tip.
 template <typename T, bool DIAG, int SCHEME, int HS, bool NN, int OCC = 1, typename PSRC = RodConst<T>, typename MSRC = MlpDev<T>>
 __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC Pa, const SimArgs<T> A, const MSRC Ma) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1697,7 +1717,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
   double* img = A.pred_io ? A.pred_io + (size_t)rod * MS_PRED_ROWS * WAVE : nullptr;
   if (img && A.pred_load && !resumed) ms_pred_load<T>(Q, img, lane);
   else ms_pred_init<T>(Q, lane, R, s0, sp, resumed || A.prev_init != nullptr, A.predictor);
-  MsSolveArgs<T> S;
+  // key-point records (PSRC = RodTableBndKp<T>): every record a solve streams into the state goes to kp too if marked
+  using KPSRC = rod_src_keypoints<T, PSRC>;
+  std::conditional_t<KPSRC::value, MsSolveArgsKp<T>, MsSolveArgs<T>> S;
   {
     const T* cl = s0 + (size_t)(N - 1) * KR_SLOTS;
     S.vlast = {cl[SL_V], cl[SL_V + 1], cl[SL_V + 2]};
@@ -1716,6 +1738,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
   T tens[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) tens[k] = ctl[t0 * 4 + k];
+  if constexpr (KPSRC::value) { S.kp_lo = KPSRC::lo(Pa); S.kp_hi = KPSRC::hi(Pa); }
   // the cold slots a step rewrites: [W0, W0 + WN) - the wrench (loads), the whole boundary (bnd) or none
   using WSRC = rod_src_step_slots<T, PSRC>;
   constexpr int W0 = WSRC::first, WN = WSRC::count;
@@ -1806,6 +1829,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void ms_sim_kernel(const PSRC P
     const int64_t inx = A.ring ? (t + 1) % 3 : t + 1;
     S.out_rod = A.states + inx * A.slot_elems + rod * rod_elems;
     S.tip = A.tip ? A.tip + (rod * A.T_steps + t) * 3 : nullptr;
+    if constexpr (KPSRC::value) S.kp = KPSRC::at(Pa, t, A.B, rod);  // (the take-over launch: from resume[rod] on, like the states)
     // ---- initial guess and solve ---------------------------------------------------
     int order = Q.next_order;
     int status, it;

@@ -226,6 +226,11 @@ struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 
 // M_tip: two sets of 19 slots, set 0 the cold block's first 19.  The base slots are read by ms_pred_guess only (row 0 of
 // the step's unknowns), which takes cold_of(its step); the areas Xs / XsB swap roles without a copy, so the step under
 // verification keeps the row 0 it was given.
+// PSRC = RodTableBndKp<T> (kr_kp_impl.hpp): the boundary kernel that also writes kp[tB][rod][k], the complete record of
+// the k-th marked grid point, wherever a verifying lane holds the record of a marked point: in every trip (complete,
+// lean and predicated alike - a lean step stores nothing else there) and, for the last grid point, in the verdict's
+// block beside the tip.  A rejected sweep has written its key points; the sweep that verifies the step again, or the
+// take-over launch from resume[rod] on, overwrites them - the tip's rule.
 template <typename T, bool DIAG, int HS, int OCC = 1, typename PSRC = RodConst<T>>
 __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC Pa, const SimArgs<T> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -245,6 +250,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   const int a_residual_test = own_sgpr(A.residual_test), a_predictor = own_sgpr(A.predictor);
   const T hc1 = own_sgpr(A.hc1), hc2 = own_sgpr(A.hc2);
   const int T_steps = own_sgpr((int)A.T_steps);  // (step indices are 32-bit: the host refuses a call of 2^31 steps or more)
+  // key-point records (PSRC = RodTableBndKp<T>): pointer, K and the mask of the marked grid points are kernel arguments
+  using KPSRC = rod_src_keypoints<T, PSRC>;
+  constexpr bool KP = KPSRC::value;
+  const unsigned long long kp_lo = KPSRC::lo(Pa), kp_hi = KPSRC::hi(Pa);
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * mso_lds_elems<T, HS>(N), N, true, false);
   T* const Es = L.Es;
   T* const XB = L.XB;
@@ -265,6 +274,14 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   const int ib = isB ? lane - MSO_B0 : 0;
   const int s_l = isB ? ms_interval_start(ib, R.sbase, R.srem) : R.s_i;
   const int len_l = isB ? R.sbase + (ib < R.srem ? 1 : 0) : R.len_i;
+  // (key points) the interval a verifying lane walks, one grid point per trip: bit kk of kp_marks = grid point s_l + kk is
+  // marked (an interval has at most 32 grid points at N <= 128), kp_rank0 = the marked points below s_l
+  unsigned kp_marks = 0;
+  int kp_rank0 = 0;
+  if constexpr (KP) {
+    kp_marks = keypoint_window(kp_lo, kp_hi, s_l);
+    kp_rank0 = keypoint_rank(kp_lo, kp_hi, s_l);
+  }
   ms_cold_fill<T>(rod_src_mem<T>(Pa, rod), L.cold, lane);
   wave_sync();
 
@@ -435,6 +452,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     const bool act = isB ? merged : (isA && runA);
     const int trips = R.lmax + ((merged && runA) ? MSO_LAG : 0);
     T* const out_rod = slot_ptr(rsA);  // state tB + 1 (used by the verifying lanes only)
+    T* const kp_out = KPSRC::at(Pa, tB, A.B, rod);  // ... and its key-point records, [K][KR_SLOTS] (key-point kernels only)
     // grid point this lane evaluates in trip k (clamped to its interval: lanes outside their range keep evaluating
     // their first / last point and do not advance)
     auto point_of = [&](int k) -> int {
@@ -572,6 +590,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           } else {
             if (!(lean && k >= R.sbase)) store_record(out_rod + (size_t)j * KR_SLOTS, rec);  // (verifying lanes: kk = k)
           }
+          // a marked grid point: the complete record, lean step or not (with the record's other stores, in front of the
+          // tile's: no read of the next trip waits behind it)
+          //  (a live verifying lane is at grid point j = s_l + kk, 0 <= kk < len_l <= 32)
+          if constexpr (KP) store_keypoint_window(kp_out, kp_marks, kp_rank0, kk, rec);
           lds_store_vec<T, 12>(lead_w + eo, lead);
         }
         // history record of the next trip.  A forward-difference lane reads the leading slots a verifying lane wrote
@@ -760,6 +782,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           // (a lean ring step: the leading slots go out with the tile once the step is accepted, and slots 12.. of this
           //  record have no reader - rebuild and the take-over kernel read q w v u here, full records at interval starts)
           if (!lean) store_record(out_rod + (size_t)(N - 1) * KR_SLOTS, rec);
+          if constexpr (KP) store_keypoint(kp_out, kp_lo, kp_hi, N - 1, rec);
           T lead[12];
 #pragma unroll
           for (int c = 0; c < 12; ++c) lead[c] = rec[c];

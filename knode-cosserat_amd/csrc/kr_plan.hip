@@ -142,15 +142,17 @@ SimPlan plan_one_wave(const kr_handle* h, SimPlan p, const PlanQuery& q, int N, 
   return p;
 }
 
-// kr_simulate_batch_table / _bank / _loads / _boundary (a table call whose tip wrench, or whose base state and tip
-// wrench, vary in time: the same plan, the loads or boundary instantiations of the same kernels): the one-wavefront persistent kernels only, and a refusal (never the handle's own
+// kr_simulate_batch_table / _bank / _loads / _boundary / _keypoints (a table call whose tip wrench, or whose base state and tip
+// wrench, vary in time, the latter also with key-point records: the same plan, the loads, boundary or key-point instantiations of the same kernels): the one-wavefront persistent kernels only, and a refusal (never the handle's own
 // parameters or network) for everything they do not serve
 template <typename T>
 SimPlan plan_table(const kr_handle* h, const PlanQuery& q) {
   const bool bank = q.source == KR_SRC_BANK;
-  const char* const word = bank ? "bank" : q.bnd ? "boundary" : q.loads ? "loads" : "table";
+  const char* const word = bank ? "bank" : q.kp ? "key-point" : q.bnd ? "boundary" : q.loads ? "loads" : "table";
   char what[128];
   auto refuse = [&](const char* w) {
+    if (q.kp)
+      return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_keypoints: %s (not served with key-point records; nothing falls back to a call without them)", w);
     if (q.bnd)
       return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_boundary: %s (not served with per-step boundary data; nothing falls back to a frozen base or wrench)", w);
     if (q.loads)

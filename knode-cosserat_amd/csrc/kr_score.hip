@@ -229,20 +229,22 @@ extern "C" int kr_dtw_batch(kr_handle* h, int64_t B, const void* a, int64_t Ta, 
                                               (int)Tb, b_rod_stride, b_step_stride, dist, s);
 }
 
-extern "C" int kr_pose_mse_batch(kr_handle* h, int64_t B, int64_t T, const void* states, const void* ref_states, int64_t ref_B,
-                                 double* mse, double* parts, int dtype, void* stream) {
+// kr_pose_mse_batch (P = the handle's N) and kr_pose_mse_points_batch (P given): one kernel, P records per rod and step
+static int pose_mse_impl(const std::string& who, kr_handle* h, int64_t B, int64_t T, int64_t P, const void* states, const void* ref_states,
+                         int64_t ref_B, double* mse, double* parts, int dtype, void* stream) {
   KR_SCORE_ARG(!h, "null handle");
-  KR_SCORE_ARG(!states || !ref_states || !mse, "kr_pose_mse_batch: null pointer argument");
+  KR_SCORE_ARG(!states || !ref_states || !mse, who + ": null pointer argument");
   KR_SCORE_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
-  KR_SCORE_ARG(B < 1, "kr_pose_mse_batch: B < 1");
-  KR_SCORE_ARG(T < 1, "kr_pose_mse_batch: T < 1");
-  KR_SCORE_ARG(ref_B != 1 && ref_B != B, "kr_pose_mse_batch: ref_B must be 1 or B");
-  KR_SCORE_ARG(((uintptr_t)states | (uintptr_t)ref_states) & 15, "kr_pose_mse_batch: states and ref_states must be 16-byte aligned");
+  KR_SCORE_ARG(B < 1, who + ": B < 1");
+  KR_SCORE_ARG(T < 1, who + ": T < 1");
+  KR_SCORE_ARG(P < 1 || P > 0x7FFFFFFFll, who + ": P must be >= 1 (and below 2^31)");
+  KR_SCORE_ARG(ref_B != 1 && ref_B != B, who + ": ref_B must be 1 or B");
+  KR_SCORE_ARG(((uintptr_t)states | (uintptr_t)ref_states) & 15, who + ": states and ref_states must be 16-byte aligned");
   if (B > 0x7FFFFFFFll) {
-    set_error("kr_pose_mse_batch: at most 2^31 - 1 rods");
+    set_error(who + ": at most 2^31 - 1 rods");
     return KR_E_UNSUPPORTED;
   }
-  const int N = h->params.N;
+  const int N = (int)P;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = order_stream(h, s)) return rc;
   if (dtype == KR_F32)
@@ -253,4 +255,15 @@ extern "C" int kr_pose_mse_batch(kr_handle* h, int64_t B, int64_t T, const void*
                        (const double*)ref_states, ref_B, mse, parts);
   KR_HIP(hipGetLastError());
   return KR_OK;
+}
+
+extern "C" int kr_pose_mse_batch(kr_handle* h, int64_t B, int64_t T, const void* states, const void* ref_states, int64_t ref_B,
+                                 double* mse, double* parts, int dtype, void* stream) {
+  KR_SCORE_ARG(!h, "null handle");
+  return pose_mse_impl("kr_pose_mse_batch", h, B, T, h->params.N, states, ref_states, ref_B, mse, parts, dtype, stream);
+}
+
+extern "C" int kr_pose_mse_points_batch(kr_handle* h, int64_t B, int64_t T, int64_t P, const void* records, const void* ref_records,
+                                        int64_t ref_B, double* mse, double* parts, int dtype, void* stream) {
+  return pose_mse_impl("kr_pose_mse_points_batch", h, B, T, P, records, ref_records, ref_B, mse, parts, dtype, stream);
 }

@@ -91,6 +91,35 @@ __device__ __forceinline__ void store_vec(T* dst, const T (&v)[NV]) {
   }
 }
 
+// Key-point records (rod_device.hpp, RodTableBndKp): the record of grid point j goes to kp[rank] if j is marked, rank =
+// the number of marked points below j.  kp = the records of this rod and step, [K][KR_SLOTS]; (lo, hi) the 128-bit mask,
+// wavefront-uniform; 0 <= j < 128.  Integer arithmetic on registers only; the store is the one thing under the mark.
+template <typename T>
+__device__ __forceinline__ void store_keypoint(T* kp, unsigned long long lo, unsigned long long hi, int j, const T (&rec)[KR_SLOTS]) {
+  const bool up = j >= 64;
+  const unsigned long long w = up ? hi : lo;
+  const int b = j & 63;
+  const int rank = __popcll(w & ~(~0ull << b)) + (up ? __popcll(lo) : 0);
+  T* const dst = kp + (size_t)rank * KR_SLOTS;
+  if ((w >> b) & 1ull) store_record(dst, rec);
+}
+
+// The same for a lane that walks an interval of at most 32 grid points from s on, one per trip (the verifying lanes of
+// mso_sim_kernel): the window of the mask (bit i = grid point s + i) and the rank of s are formed once, a trip then
+// needs a bit test, a masked population count and one multiply-add for the address.
+__device__ __forceinline__ unsigned keypoint_window(unsigned long long lo, unsigned long long hi, int s) {
+  return (unsigned)(s >= 64 ? hi >> (s - 64) : (lo >> s) | ((hi << 1) << (63 - s)));
+}
+__device__ __forceinline__ int keypoint_rank(unsigned long long lo, unsigned long long hi, int s) {  // marked points below s
+  return s >= 64 ? __popcll(lo) + __popcll(hi & ~(~0ull << (s - 64))) : __popcll(lo & ~(~0ull << s));
+}
+template <typename T>
+__device__ __forceinline__ void store_keypoint_window(T* kp, unsigned marks, int rank0, int i, const T (&rec)[KR_SLOTS]) {
+  const int rank = rank0 + __popc(marks & ~(~0u << i));  // 0 <= i < 32
+  T* const dst = kp + (size_t)rank * KR_SLOTS;
+  if ((marks >> i) & 1u) store_record(dst, rec);
+}
+
 template <typename T, int HS>
 __device__ __forceinline__ void load_hist_vec(const T* src, T (&hv)[HS]) {
   if constexpr (HS % Vec16<T>::n == 0) {

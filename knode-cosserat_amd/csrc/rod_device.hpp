@@ -104,6 +104,39 @@ struct rod_src_step_slots<T, RodTableBnd<T>> {
   static constexpr int first = 0, count = 19;  // CD_P0 .. CD_MTIP + 3: the whole boundary
   static __device__ __forceinline__ const T* hist(const RodTableBnd<T>& P) { return P.bnd; }
 };
+// The boundary source plus key-point records (kr_simulate_batch_keypoints, kr_kp_impl.hpp): kp[T_steps][B][K][KR_SLOTS]
+// receives, for every step t, the complete record of the K marked grid points of the state that step writes.  The point
+// set is a 128-bit mask (N <= 128 in every kernel that takes a table): bit j of (lo, hi) marks grid point j, and the
+// rank of a marked point - its index k in kp - is the number of marked points below it.  Pointer, K and mask are kernel
+// arguments of the key-point instantiations alone and wavefront-uniform: testing a grid point reads no memory.
+template <typename T>
+struct RodTableBndKp : RodTableBnd<T> {
+  T* kp;
+  int K;
+  unsigned long long mask_lo, mask_hi;
+};
+template <typename T>
+struct rod_src_step_slots<T, RodTableBndKp<T>> {
+  static constexpr int first = 0, count = 19;  // the boundary one
+  static __device__ __forceinline__ const T* hist(const RodTableBndKp<T>& P) { return P.bnd; }
+};
+// Whether a parameter source carries key-point records, and where rod `rod` of a batch of B finds those of step t
+template <typename T, typename PSRC>
+struct rod_src_keypoints {
+  static constexpr bool value = false;
+  static __device__ __forceinline__ T* at(const PSRC&, int64_t, int64_t, int64_t) { return nullptr; }
+  static __device__ __forceinline__ unsigned long long lo(const PSRC&) { return 0; }
+  static __device__ __forceinline__ unsigned long long hi(const PSRC&) { return 0; }
+};
+template <typename T>
+struct rod_src_keypoints<T, RodTableBndKp<T>> {
+  static constexpr bool value = true;
+  static __device__ __forceinline__ T* at(const RodTableBndKp<T>& P, int64_t t, int64_t B, int64_t rod) {
+    return P.kp + ((t * B + rod) * P.K) * 28;  // (KR_SLOTS; the records of one rod and step are contiguous)
+  }
+  static __device__ __forceinline__ unsigned long long lo(const RodTableBndKp<T>& P) { return P.mask_lo; }
+  static __device__ __forceinline__ unsigned long long hi(const RodTableBndKp<T>& P) { return P.mask_hi; }
+};
 // What a persistent kernel takes as its first argument: the launch-uniform RodConst<T> by value (every rod alike), or a
 // RodTable<T>.  rod_src_row yields the constants of one rod for the kernel's arithmetic: the kernel argument itself,
 // or - table - a local copy of the rod's row, read ONCE, unconditionally, where the kernel starts: scalar loads (the

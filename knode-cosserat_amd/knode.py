@@ -233,6 +233,43 @@ def _boundary(base, loads, rows):
     return bnd
 
 
+def _key_points(key_points, N):
+    """The grid points of ``simulate_batch(..., key_points=[...])`` as the library wants them: int32, sorted, without
+    duplicates, each in [0, N) (a negative index counts from the tip); host-side validation only (no library call)."""
+    try:
+        arr = np.asarray(key_points)
+        if arr.size and (arr.dtype == bool or not np.issubdtype(arr.dtype, np.integer)):
+            raise TypeError
+        pts = [int(p) for p in arr.reshape(-1)] if arr.ndim <= 1 else None
+    except (TypeError, ValueError):
+        pts = None
+    if pts is None:
+        raise kn.KrError("simulate_batch: key_points must be a list of integer grid points")
+    for p in pts:
+        if not -N <= p < N:
+            raise kn.KrError(f"simulate_batch: key point {p} outside the rod's {N} grid points")
+    idx = sorted({p % N for p in pts})
+    if not 1 <= len(idx) <= kn.KR_KEYPOINTS_MAX:
+        raise kn.KrError(f"simulate_batch: {len(idx)} key points; a call takes 1 .. {kn.KR_KEYPOINTS_MAX}")
+    return np.asarray(idx, dtype=np.int32)
+
+
+def _base_of_rows(rows, T):
+    """``base[B, T, 13]`` of a call without ``base_motion``: each rod's own ``p0 h0 q0 w0`` on every step."""
+    base = np.empty((len(rows), T, 13), dtype=np.float64)
+    for b, p in enumerate(rows):
+        base[b, :] = np.concatenate([np.asarray(p.p0[:], dtype=np.float64), np.asarray(p.h0[:], dtype=np.float64),
+                                     np.asarray(p.q0[:], dtype=np.float64), np.asarray(p.w0[:], dtype=np.float64)])
+    return base
+
+
+def _kp_rows(records):
+    """Packed key-point records ``[T + 1, B, K, KR_SLOTS]`` (q w v u p h n m, entry 0 = the initial state) as the result's
+    ``kp``: ``[B, T + 1, 25, K]`` in the reference's row order (p h n m q w v u), i.e. ``traj[:, :, :, key_points]``."""
+    r = np.asarray(records).transpose(1, 0, 3, 2)  # [B, T + 1, KR_SLOTS, K]
+    return np.ascontiguousarray(np.concatenate([r[:, :, 12:25], r[:, :, 0:12]], axis=2))
+
+
 def _score_reference(robot, score, B, T, tip_only):
     """``(reference[R, Tr, >=7, N], point)`` of ``simulate_batch(..., score=...)``, R = 1 or B; host-side validation only
     (no device call)."""
@@ -264,7 +301,8 @@ def _score_reference(robot, score, B, T, tip_only):
 
 
 def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, tol=0.0, maxit=0, tip_only=False,
-                   robots=None, per_robot_nn=False, score=None, tip_loads=None, check_finite=True, base_motion=None):
+                   robots=None, per_robot_nn=False, score=None, tip_loads=None, check_finite=True, base_motion=None,
+                   key_points=None):
     """B rods, each with its own tension history.
 
     robots: None = B copies of ``robot``; otherwise a sequence of B ``CosseratRod`` objects, each prepared the
@@ -302,6 +340,16 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     with ``robots``, ``tip_loads`` (without it every rod keeps its own ``F_tip`` / ``M_tip``), ``score`` and ``tip_only``;
     not served with ``per_robot_nn``.
 
+    key_points: a list of 1 .. 16 grid points (a negative index counts from the tip; sorted and de-duplicated here): the
+    result gains ``kp`` float[B, T+1, 25, K], the states at those points in the reference's row order, entry 0 the initial
+    state - ``traj[:, :, :, key_points]`` wherever both exist - and ``key_points`` int32[K], the order used.  With
+    ``tip_only=True`` this is the way to the states at a few points of a long run of a large batch: the full history is
+    never stored.  Composes with ``robots``, ``tip_loads``, ``base_motion`` (without them the boundary is each rod's own, on
+    every step) and ``tip_only``; not served with ``per_robot_nn``.  With ``key_points``, ``score`` is accepted with
+    ``tip_only=True``: ``dtw`` is the DTW of the path of ``score["point"]``, which must then be a key point, and
+    ``mse_kp`` the pose MSE over the K key points against the reference at those points (``mse``, the all-points quantity,
+    is there only when the full history is).
+
     check_finite: True (default) refuses ``tip_loads`` / ``base_motion`` that are not finite (and a zero ``h0``) before
     anything touches the device; False hands them to the library, for which they are ordinary input (domain randomisation,
     a diverging row of a sweep).
@@ -312,7 +360,14 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     later step reports a nonzero status.  A NaN tip wrench (``tip_loads``, ``F_tip`` / ``M_tip``) enters the tip condition
     only: states and scores stay finite and later steps may report 0 again - ``status`` 2 at t0 is the only mark.  A NaN
     base value (``base_motion``) enters the sweeps like a NaN tension."""
-    loads = base = None
+    loads = base = kp_idx = None
+    if key_points is not None:  # (validated on the host before anything touches the device)
+        if per_robot_nn:
+            raise kn.KrError("simulate_batch: key_points with per_robot_nn=True is not served (key-point records have no network-bank form)")
+        ctl_shape = np.asarray(ctl).shape
+        if len(ctl_shape) != 3:
+            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+        kp_idx = _key_points(key_points, int(robot.N))
     if base_motion is not None:  # (validated on the host before anything touches the device)
         if per_robot_nn:
             raise kn.KrError("simulate_batch: base_motion with per_robot_nn=True is not served (per-step boundary data has no network-bank form)")
@@ -331,7 +386,10 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         ctl_shape = np.asarray(ctl).shape
         if len(ctl_shape) != 3:
             raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
-        score_ref, score_point = _score_reference(robot, score, int(ctl_shape[0]), int(ctl_shape[1]), tip_only)
+        score_ref, score_point = _score_reference(robot, score, int(ctl_shape[0]), int(ctl_shape[1]), tip_only and kp_idx is None)
+        if tip_only and score_point not in kp_idx.tolist():
+            raise kn.KrError(f"simulate_batch: score point {score_point} is not one of the key points {kp_idx.tolist()} "
+                             "(tip_only=True keeps the states at the key points only)")
     rows = None
     networks = net_of_rod = None
     if robots is not None:  # (validated on the host before anything touches the device)
@@ -341,6 +399,11 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         rows = _robots_rows(robot, [robot] * loads.shape[0], loads.shape[0])
     elif base is not None:  # only the base varies
         rows = _robots_rows(robot, [robot] * base.shape[0], base.shape[0])
+    elif kp_idx is not None:  # nothing varies: a table of identical rows
+        n_rods = int(np.asarray(ctl).shape[0])
+        rows = _robots_rows(robot, [robot] * n_rods, n_rods)
+    if kp_idx is not None and base is None:  # a key-point call is a boundary call: each rod's own base on every step
+        base = _base_of_rows(rows, int(np.asarray(ctl).shape[1]))
     bnd = _boundary(base, loads, rows) if base is not None else None  # (tip_loads alone stays a loads call)
     if per_robot_nn:
         if robots is None:
@@ -362,15 +425,27 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     status = torch.zeros((B, T), dtype=torch.int32, device=dev)
     loads_t = torch.as_tensor(loads, device=dev).to(tdt).contiguous() if loads is not None and bnd is None else None
     bnd_t = torch.as_tensor(bnd, device=dev).to(tdt).contiguous() if bnd is not None else None
+    kp_all = None
+    if kp_idx is not None:  # [T + 1, B, K, KR_SLOTS]: entry 0 from the initial state (a ring overwrites its slot), the rest by the run
+        kp_all = torch.empty((T + 1, B, len(kp_idx), kn.KR_SLOTS), dtype=tdt, device=dev)
+        kp_all[0] = states[0][:, torch.as_tensor(kp_idx.astype(np.int64), device=dev)]
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
                scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
-               table=table, bank=bank, net_of_rod=net_of_rod, loads=loads_t, bnd=bnd_t)
+               table=table, bank=bank, net_of_rod=net_of_rod, loads=loads_t, bnd=bnd_t,
+               **({"key_points": kp_idx, "kp": kp_all[1:]} if kp_idx is not None else {}))
     if score is not None:  # queued behind the run; the copies below wait for both
         Tr = score_ref.shape[1]
         ref_states = h.pack_poses(score_ref, tdt)  # [Tr, 1 or B, N, KR_SLOTS], packed once
         ref_path = ref_states[:, :, score_point, 12:15].permute(1, 0, 2)
-        score_dtw = h.dtw(states[:Tr, :, score_point, 12:15].permute(1, 0, 2), ref_path[0] if ref_path.shape[0] == 1 else ref_path)
-        score_mse, _ = h.pose_mse(states[:Tr], ref_states)
+        if tip_only:  # the path of the score point from the key-point records (the ring holds three states)
+            path = kp_all[:Tr, :, kp_idx.tolist().index(score_point), 12:15].permute(1, 0, 2)
+        else:
+            path = states[:Tr, :, score_point, 12:15].permute(1, 0, 2)
+        score_dtw = h.dtw(path, ref_path[0] if ref_path.shape[0] == 1 else ref_path)
+        score_mse = None if tip_only else h.pose_mse(states[:Tr], ref_states)[0]
+        if kp_idx is not None:
+            ref_kp = ref_states[:, :, torch.as_tensor(kp_idx.astype(np.int64), device=dev)].contiguous()
+            score_mse_kp, _ = h.pose_mse_points(kp_all[:Tr], ref_kp)
     out = {"tip": tip.cpu().numpy(), "status": status.cpu().numpy(), "G": G.cpu().numpy()}  # (.cpu() waits for the run)
     if table is not None:
         table.close()
@@ -380,7 +455,13 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         bank.close()
     if score is not None:
         out["dtw"] = score_dtw.cpu().numpy()
-        out["mse"] = score_mse.cpu().numpy()
+        if score_mse is not None:
+            out["mse"] = score_mse.cpu().numpy()
+        if kp_idx is not None:
+            out["mse_kp"] = score_mse_kp.cpu().numpy()
+    if kp_idx is not None:
+        out["kp"] = _kp_rows(kp_all.cpu().numpy())
+        out["key_points"] = kp_idx.copy()
     if not tip_only and return_states:
         N = h.N
         traj = torch.empty((B, T + 1, 25, N), dtype=tdt, device=dev)

@@ -26,6 +26,7 @@ ST_CONVERGED, ST_MAXIT, ST_NONFINITE = 0, 1, 2
 KR_MAX_LAYERS = 8
 KR_DTW_MAX_LEN = 4096
 KR_BND = 19  # p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) per rod and step (kr_simulate_batch_boundary)
+KR_KEYPOINTS_MAX = 16  # key points per call (kr_simulate_batch_keypoints)
 KR_E_ARG, KR_E_UNSUPPORTED = -1, -4
 
 # reference row (0..24 of [y; z]) -> packed slot, see knode_rod.h
@@ -106,6 +107,9 @@ _PROTOS = {
                                        _vp]),
     "kr_simulate_batch_boundary": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _int, _vp, _int,
                                           _vp]),
+    "kr_keypoints_check": (_int, [_int, _int, C.POINTER(C.c_int32)]),
+    "kr_simulate_batch_keypoints": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _int, C.POINTER(C.c_int32), _vp, _vp, _int, _vp, _vp,
+                                           C.c_double, _int, _vp, _int, _vp, _int, _vp]),
     "kr_mlp_bank_check": (_int, [C.POINTER(KrParams), _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kr_mlp_bank_create": (_int, [_vp, _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _int, _vp,
                                   C.POINTER(_vp)]),
@@ -141,6 +145,7 @@ _PROTOS = {
     "kr_estimate_state": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "kr_dtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp]),
     "kr_pose_mse_batch": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
+    "kr_pose_mse_points_batch": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -554,8 +559,32 @@ class Handle:
         check(self.lib.kr_set_option(self._h, name.encode(), int(value)))
 
     def simulate(self, ctl, states, G, ring=False, tip=None, status=None, scheme=KR_EULER, tol=0.0, maxit=0,
-                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None, loads=None, bnd=None):
+                 use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None, loads=None, bnd=None, key_points=None,
+                 kp=None):
         B, T = ctl.shape[0], ctl.shape[1]
+        if key_points is not None or kp is not None:
+            # kp[t, b, k] receives the complete record of grid point key_points[k] of the state step t writes
+            if bank is not None or net_of_rod is not None:
+                raise KrError("key_points= together with bank=: key-point records are not served with a network bank")
+            if loads is not None:
+                raise KrError("key_points= together with loads=: a key-point call takes bnd (its last six columns are the tip wrench)")
+            if table is None or bnd is None:
+                raise KrError("a key-point call needs table= and bnd= (a caller with a fixed boundary repeats the rows' values)")
+            if key_points is None or kp is None:
+                raise KrError("a key-point call needs key_points= and kp= together")
+            if B != table.B:
+                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
+            if tuple(bnd.shape) != (B, T, KR_BND) or bnd.dtype != ctl.dtype or not bnd.is_contiguous():
+                raise KrError(f"bnd must be a contiguous [{B}, {T}, {KR_BND}] tensor of {ctl.dtype}; got {tuple(bnd.shape)} {bnd.dtype}")
+            idx = np.ascontiguousarray(np.asarray(key_points).reshape(-1), dtype=np.int32)
+            K = int(idx.size)
+            if tuple(kp.shape) != (T, B, K, KR_SLOTS) or kp.dtype != ctl.dtype or not kp.is_contiguous():
+                raise KrError(f"kp must be a contiguous [{T}, {B}, {K}, {KR_SLOTS}] tensor of {ctl.dtype}; got {tuple(kp.shape)} {kp.dtype}")
+            check(self.lib.kr_simulate_batch_keypoints(self._h, table._t, T, scheme, _ptr(ctl), _ptr(bnd), K,
+                                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(kp), _ptr(states),
+                                                       int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
+                                                       int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+            return
         if bnd is not None:  # rod b, step t: bnd[b, t] = p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) in place of its row's
             if bank is not None or net_of_rod is not None:
                 raise KrError("bnd= together with bank=: per-step boundary data is not served with a network bank")
@@ -643,6 +672,26 @@ class Handle:
         parts = torch.empty((B, 2), dtype=torch.float64, device=states.device)
         check(self.lib.kr_pose_mse_batch(self._h, B, T, _ptr(states), _ptr(ref_states), ref_states.shape[1], _ptr(mse),
                                          _ptr(parts), dtype_code(states.dtype), _stream()))
+        return mse, parts
+
+    def pose_mse_points(self, records, ref_records):
+        """``pose_mse`` over P records per rod and step instead of the handle's N grid points: ``records`` ``[T, B, P, KR_SLOTS]``
+        (the ``kp`` of a key-point call) against ``ref_records`` ``[T, B or 1, P, KR_SLOTS]``, both contiguous.  Returns
+        ``(mse[B], parts[B, 2])``, float64 on the device."""
+        import torch
+        if records.dim() != 4 or ref_records.dim() != 4 or records.shape[3] != KR_SLOTS or \
+                ref_records.shape[2:] != records.shape[2:] or ref_records.shape[0] != records.shape[0]:
+            raise KrError(f"pose_mse_points: records {tuple(records.shape)} / ref_records {tuple(ref_records.shape)}: expected "
+                          f"[T, B, P, {KR_SLOTS}] and [T, B or 1, P, {KR_SLOTS}]")
+        if records.dtype != ref_records.dtype:
+            raise KrError(f"pose_mse_points: records are {records.dtype}, ref_records {ref_records.dtype}")
+        if not records.is_contiguous() or not ref_records.is_contiguous():
+            raise KrError("pose_mse_points: records and ref_records must be contiguous")
+        T, B, P = records.shape[0], records.shape[1], records.shape[2]
+        mse = torch.empty((B,), dtype=torch.float64, device=records.device)
+        parts = torch.empty((B, 2), dtype=torch.float64, device=records.device)
+        check(self.lib.kr_pose_mse_points_batch(self._h, B, T, P, _ptr(records), _ptr(ref_records), ref_records.shape[1], _ptr(mse),
+                                                _ptr(parts), dtype_code(records.dtype), _stream()))
         return mse, parts
 
     def pack_poses(self, traj, dtype):
