@@ -237,22 +237,29 @@ static int step_impl(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a,
   return KR_OK;
 }
 
-// kr_simulate_batch, _table (src.table) and _bank (src.bank too): one path
+// What the six simulate entry points take alike (knode_rod.h: kr_simulate_batch)
+struct SimCall {
+  int64_t T_steps;
+  int scheme;
+  const void* ctl;
+  void* states;
+  int ring;
+  void *G, *tip;
+  double tol;
+  int maxit;
+  int32_t* status;
+  int use_nn;
+  const void* prev_init;
+  int dtype;
+  void* stream;
+};
+
+// every simulate entry point: one path, the rods' source in `src`
 template <typename T>
-static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, int64_t T_steps, int scheme, const void* ctl, void* states,
-                         int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
-                         const void* prev_init, hipStream_t s) {
+static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, const SimCall& c, hipStream_t s) {
   const size_t slot = (size_t)B * h->params.N * KR_SLOTS;
-  T* base = (T*)states;
-  PlanQuery q{B, T_steps, scheme, use_nn};
-  q.source = src.bank ? KR_SRC_BANK : src.table ? KR_SRC_TABLE : KR_SRC_HANDLE;
-  if (src.table) q.N = src.table->N;
-  q.bank = src.bank;
-  q.loads = src.loads != nullptr;
-  q.bnd = src.bnd != nullptr;
-  q.kp = src.kp.kp != nullptr;
-  q.prev_init = prev_init; q.states = states; q.slot_elems = (int64_t)slot;
-  const SimPlan plan = plan_simulate<T>(h, q);
+  T* base = (T*)c.states;
+  const SimPlan plan = plan_simulate<T>(h, plan_query(src, B, c.T_steps, c.scheme, c.use_nn, c.prev_init, c.states, (int64_t)slot));
   if (plan.rc) return refuse_plan(plan);
   const PredImage im = plan_pred_image(h, plan, B);
   double* pred = nullptr;
@@ -262,10 +269,10 @@ static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, int64_t T_s
   }
   if (plan.path == 2) {
     // one launch for all steps
-    auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, G, ctl, 4, tol, maxit);
+    auto a0 = make_args<T>(h, B, nullptr, nullptr, nullptr, c.G, c.ctl, 4, c.tol, c.maxit);
     SimArgs<T> sa{};
-    sa.B = B; sa.T_steps = T_steps; sa.states = base; sa.slot_elems = (int64_t)slot; sa.ring = ring;
-    sa.prev_init = (const T*)prev_init; sa.ctl = (const T*)ctl; sa.G = (T*)G; sa.tip = (T*)tip; sa.status = status;
+    sa.B = B; sa.T_steps = c.T_steps; sa.states = base; sa.slot_elems = (int64_t)slot; sa.ring = c.ring;
+    sa.prev_init = (const T*)c.prev_init; sa.ctl = (const T*)c.ctl; sa.G = (T*)c.G; sa.tip = (T*)c.tip; sa.status = c.status;
     sa.tol = a0.tol; sa.tolA = a0.tolA; sa.fd_eps = a0.fd_eps; sa.hc1 = a0.hc1; sa.hc2 = a0.hc2;
     sa.maxit = a0.maxit; sa.predictor = h->predictor; sa.residual_test = h->residual_test; sa.nn_lowp = h->nn_lowp_first; sa.nn_base_only = h->nn_base_only_store;
     sa.dbg = static_cast<unsigned long long*>(h->dbg);
@@ -275,23 +282,23 @@ static int simulate_impl(kr_handle* h, const SimSrc& src, int64_t B, int64_t T_s
     return KR_OK;
   }
   // one launch per step
-  for (int64_t t = 0; t < T_steps; ++t) {
+  for (int64_t t = 0; t < c.T_steps; ++t) {
     // knode.py:65-66,76-77: before the first step y_prev = y (unless the caller hands over the state before)
-    const int64_t ic = ring ? t % 3 : t;
-    const int64_t in = ring ? (t + 1) % 3 : t + 1;
-    const T* pprev = t == 0 ? (prev_init ? (const T*)prev_init : base + ic * slot)
-                            : base + (ring ? (t + 2) % 3 : t - 1) * slot;
-    auto a = make_args<T>(h, B, pprev, base + ic * slot, base + in * slot, G, (const T*)ctl + t * 4,
-                          T_steps * 4, tol, maxit);
+    const int64_t ic = c.ring ? t % 3 : t;
+    const int64_t in = c.ring ? (t + 1) % 3 : t + 1;
+    const T* pprev = t == 0 ? (c.prev_init ? (const T*)c.prev_init : base + ic * slot)
+                            : base + (c.ring ? (t + 2) % 3 : t - 1) * slot;
+    auto a = make_args<T>(h, B, pprev, base + ic * slot, base + in * slot, c.G, (const T*)c.ctl + t * 4,
+                          c.T_steps * 4, c.tol, c.maxit);
     // time extrapolation of the initial guess from the states already computed (order <= h->predictor)
-    int order = t == 0 ? (prev_init ? 1 : 0) : (t == 1 ? (prev_init ? 2 : 1) : 2);
+    int order = t == 0 ? (c.prev_init ? 1 : 0) : (t == 1 ? (c.prev_init ? 2 : 1) : 2);
     if (order > h->predictor) order = h->predictor;  // (orders 3..5: persistent kernel only)
-    if (order == 2) a.prev2 = t == 1 ? (const T*)prev_init : base + (ring ? (t + 1) % 3 : t - 2) * slot;
+    if (order == 2) a.prev2 = t == 1 ? (const T*)c.prev_init : base + (c.ring ? (t + 1) % 3 : t - 2) * slot;
     a.pred_order = order;
-    a.pred = pred; a.pred_reset = t == 0 && !im.load; a.pred_has_prev = prev_init != nullptr; a.pred_limit = h->predictor;
-    if (tip) { a.tip = (T*)tip + t * 3; a.tip_stride = T_steps * 3; }
-    if (status) { a.status = status + t; a.st_stride = T_steps; }
-    if (h->dbg) { a.iters = static_cast<int32_t*>(h->dbg) + t; a.st_stride = T_steps; }  // diagnostics: sweeps per rod and step, [B][T] int32
+    a.pred = pred; a.pred_reset = t == 0 && !im.load; a.pred_has_prev = c.prev_init != nullptr; a.pred_limit = h->predictor;
+    if (c.tip) { a.tip = (T*)c.tip + t * 3; a.tip_stride = c.T_steps * 3; }
+    if (c.status) { a.status = c.status + t; a.st_stride = c.T_steps; }
+    if (h->dbg) { a.iters = static_cast<int32_t*>(h->dbg) + t; a.st_stride = c.T_steps; }  // diagnostics: sweeps per rod and step, [B][T] int32
     if (int rc = launch_step<T>(h, plan, a, s)) return rc;
   }
   note_sim_plan(h, plan, im, B);  // (T_steps > 0 here)
@@ -1087,22 +1094,36 @@ int kr_state_init_straight_table(kr_handle* h, const kr_param_table* t, void* st
                          : launch_tab_init_straight<double>(h, t, (double*)state, s);
 }
 
+// The dtype dispatch of every simulate entry point, and in front of it what all but the bank's check alike once their own
+// checks are done (kr_simulate_batch_bank checks T and the pointers before it touches the stream: it calls the dispatch)
+static int simulate_dispatch(kr_handle* h, const SimSrc& src, int64_t B, const SimCall& c, hipStream_t s) {
+  return c.dtype == KR_F32 ? simulate_impl<float>(h, src, B, c, s) : simulate_impl<double>(h, src, B, c, s);
+}
+static int simulate_call(kr_handle* h, const SimSrc& src, int64_t B, const SimCall& c) {
+  const int dtype = c.dtype;
+  void* const stream = c.stream;
+  KR_BATCH_PROLOGUE(B);
+  if (src.table)
+    if (int rc = tab_matches(h, src.table)) return rc;
+  if (c.T_steps < 0) { set_error("T < 0"); return KR_E_ARG; }
+  if (c.T_steps == 0) return KR_OK;
+  const void *ctl = c.ctl, *states = c.states, *G = c.G;
+  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  return simulate_dispatch(h, src, B, c, s);
+}
+// a table-family source of `kind`
+static SimSrc make_src(int kind, const kr_param_table* t, const void* hist = nullptr) {
+  SimSrc src;
+  src.kind = kind; src.table = t; src.hist = hist;
+  return src;
+}
+
 int kr_simulate_batch_table(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl, void* states,
                             int ring, void* G, void* tip, double tol, int maxit, int32_t* status, int use_nn,
                             const void* state_prev_init, int dtype, void* stream) {
   KR_CHECK_PTR(t);
-  KR_BATCH_PROLOGUE(t->B);
-  if (int rc = tab_matches(h, t)) return rc;
-  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
-  if (T == 0) return KR_OK;
-  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
-  SimSrc src;
-  src.table = t;
-  return dtype == KR_F32
-             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                    state_prev_init, s)
-             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                     state_prev_init, s);
+  return simulate_call(h, make_src(KR_SRC_TABLE, t), t->B,
+                       SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn, state_prev_init, dtype, stream});
 }
 
 // kr_simulate_batch_table with a tip wrench per rod and step.  (The kernels it plans are resolved and given their LDS
@@ -1112,19 +1133,8 @@ int kr_simulate_batch_loads(kr_handle* h, const kr_param_table* t, int64_t T, in
                             const void* state_prev_init, int dtype, void* stream) {
   KR_CHECK_PTR(t);
   KR_CHECK_PTR(loads);
-  KR_BATCH_PROLOGUE(t->B);
-  if (int rc = tab_matches(h, t)) return rc;
-  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
-  if (T == 0) return KR_OK;
-  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
-  SimSrc src;
-  src.table = t;
-  src.loads = loads;
-  return dtype == KR_F32
-             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                    state_prev_init, s)
-             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                     state_prev_init, s);
+  return simulate_call(h, make_src(KR_SRC_LOADS, t, loads), t->B,
+                       SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn, state_prev_init, dtype, stream});
 }
 
 // kr_simulate_batch_loads with the base state of every rod and step beside its wrench: bnd[B][T][KR_BND]
@@ -1133,19 +1143,8 @@ int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T,
                                const void* state_prev_init, int dtype, void* stream) {
   KR_CHECK_PTR(t);
   KR_CHECK_PTR(bnd);
-  KR_BATCH_PROLOGUE(t->B);
-  if (int rc = tab_matches(h, t)) return rc;
-  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
-  if (T == 0) return KR_OK;
-  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
-  SimSrc src;
-  src.table = t;
-  src.bnd = bnd;
-  return dtype == KR_F32
-             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                    state_prev_init, s)
-             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                     state_prev_init, s);
+  return simulate_call(h, make_src(KR_SRC_BOUNDARY, t, bnd), t->B,
+                       SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn, state_prev_init, dtype, stream});
 }
 
 // the rule of kr_keypoints_check; `lo` / `hi` receive the mask of the marked grid points (bit j = grid point j)
@@ -1190,23 +1189,12 @@ int kr_simulate_batch_keypoints(kr_handle* h, const kr_param_table* t, int64_t T
               " (a caller with a fixed boundary repeats the row's values)");
     return KR_E_ARG;
   }
-  SimSrc src;
-  if (int rc = keypoints_mask(NAME, t->N, K, idx_host, src.kp.mask_lo, src.kp.mask_hi)) return rc;
-  if ((uintptr_t)kp & 15) { set_error(std::string(NAME) + ": kp must be 16-byte aligned"); return KR_E_ARG; }
-  KR_BATCH_PROLOGUE(t->B);
-  if (int rc = tab_matches(h, t)) return rc;
-  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
-  if (T == 0) return KR_OK;
-  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
-  src.table = t;
-  src.bnd = bnd;
+  SimSrc src = make_src(KR_SRC_KEYPOINTS, t, bnd);
   src.kp.kp = kp;
   src.kp.K = K;
-  return dtype == KR_F32
-             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                    state_prev_init, s)
-             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                     state_prev_init, s);
+  if (int rc = keypoints_mask(NAME, t->N, K, idx_host, src.kp.mask_lo, src.kp.mask_hi)) return rc;
+  if ((uintptr_t)kp & 15) { set_error(std::string(NAME) + ": kp must be 16-byte aligned"); return KR_E_ARG; }
+  return simulate_call(h, src, t->B, SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn, state_prev_init, dtype, stream});
 }
 
 // ---- per-rod networks: banks ----------------------------------------------------------------------------------------
@@ -1360,11 +1348,9 @@ int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_b
   // this call returns
   KR_HIP(hipMemcpyAsync(h->net_idx_buf, net_of_rod_host, sizeof(int32_t) * (size_t)t->B, hipMemcpyHostToDevice, s));
   KR_HIP(hipStreamSynchronize(s));
-  SimSrc src;
-  src.table = t; src.bank = bank; src.net_idx = static_cast<const int32_t*>(h->net_idx_buf);
-  return dtype == KR_F32
-             ? simulate_impl<float>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, 1, state_prev_init, s)
-             : simulate_impl<double>(h, src, t->B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, 1, state_prev_init, s);
+  SimSrc src = make_src(KR_SRC_BANK, t);
+  src.bank = bank; src.net_idx = static_cast<const int32_t*>(h->net_idx_buf);
+  return simulate_dispatch(h, src, t->B, SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, 1, state_prev_init, dtype, stream}, s);
 }
 
 // the one-time host work of the first kr_simulate_batch (Euler, MLP off) of this batch size, ahead of time: the kernels
@@ -1391,15 +1377,7 @@ int kr_simulate_prepare(kr_handle* h, int64_t B, int dtype) {
 int kr_simulate_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, void* states, int ring, void* G,
                       void* tip, double tol, int maxit, int32_t* status, int use_nn, const void* state_prev_init,
                       int dtype, void* stream) {
-  KR_BATCH_PROLOGUE(B);
-  if (T < 0) { set_error("T < 0"); return KR_E_ARG; }
-  if (T == 0) return KR_OK;
-  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
-  return dtype == KR_F32
-             ? simulate_impl<float>(h, SimSrc{}, B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                    state_prev_init, s)
-             : simulate_impl<double>(h, SimSrc{}, B, T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn,
-                                     state_prev_init, s);
+  return simulate_call(h, SimSrc{}, B, SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, use_nn, state_prev_init, dtype, stream});
 }
 
 }  // extern "C"

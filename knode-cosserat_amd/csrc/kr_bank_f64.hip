@@ -2,5 +2,5 @@
 #define KR_MS_NO_INST
 #include "kr_bank_impl.hpp"
 namespace kr {
-template int launch_bank_sim<double>(kr_handle*, const kr_param_table*, const kr_mlp_bank*, const int32_t*, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
+template int launch_bank_sim<double>(kr_handle*, const SimSrc&, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
 }

@@ -21,11 +21,12 @@
 
 namespace kr {
 
+// (the MLP-on arm of launch_one_wave_src with the bank for a network: its own launch, so that this unit holds that one
+// kernel and not the MLP-off table kernels of kr_tab_*)
 template <typename T>
-int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, const int32_t* net_idx, const SimPlan& p,
-                    const SimArgs<T>& a, const LaunchAt& at) {
-  const RodTable<T> tab{(const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t), t->N};
-  const MlpBank<T> bank{bank_net0<T>(bk), (const KR_CONSTANT_AS int32_t*)net_idx, (unsigned long long)bk->stride};
+int launch_bank_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  const auto tab = table_src<T, RodTable<T>>(src.table);
+  const MlpBank<T> bank{bank_net0<T>(src.bank), (const KR_CONSTANT_AS int32_t*)src.net_idx, (unsigned long long)src.bank->stride};
   return launch(at, ms_sim_kernel<T, true, KR_EULER, hs_phys<T>(), true, 1, RodTable<T>, MlpBank<T>>, dim3((unsigned)((a.B + MS_WPB - 1) / MS_WPB)),
                 dim3(WAVE * MS_WPB), p.smem[0], tab, a, bank);
 }

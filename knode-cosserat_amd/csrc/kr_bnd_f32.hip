@@ -2,5 +2,5 @@
 #define KR_MS_NO_INST
 #include "kr_bnd_impl.hpp"
 namespace kr {
-template int launch_bnd_sim<float>(kr_handle*, const kr_param_table*, const float*, const SimPlan&, const SimArgs<float>&, const LaunchAt&);
+template int launch_bnd_sim<float>(kr_handle*, const SimSrc&, const SimPlan&, const SimArgs<float>&, const LaunchAt&);
 }

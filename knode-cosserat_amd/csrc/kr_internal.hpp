@@ -276,7 +276,37 @@ enum SimFamily {
   KR_FAM_MSW_NN_SIM,  // ... with the MLP on (kr_mswn_*.hip)
   KR_FAM_MSWO         // ... with overlapped steps (kr_mswo_impl.hpp)
 };
-enum SimSource { KR_SRC_HANDLE, KR_SRC_TABLE, KR_SRC_BANK };  // where a rod's constants / network come from
+// Where a rod's constants, its per-step data and its network come from: one kind per simulate entry point.  Every kind
+// but the first is a table call (SimSrc::table) served by the one-wavefront persistent kernels only (plan_table).
+enum SimKind { KR_SRC_HANDLE, KR_SRC_TABLE, KR_SRC_LOADS, KR_SRC_BOUNDARY, KR_SRC_KEYPOINTS, KR_SRC_BANK };
+// ... and how a kind is spoken of: its entry point, the word for it in a refusal, and the end of the refusal sentence
+struct SimKindText {
+  const char *api, *word, *tail;
+};
+constexpr SimKindText kSimKindText[] = {
+    {"kr_simulate_batch", "", ""},
+    {"kr_simulate_batch_table", "table", "not served with a parameter table; nothing falls back to the handle's parameters"},
+    {"kr_simulate_batch_loads", "loads", "not served with per-step tip loads; nothing falls back to a frozen wrench"},
+    {"kr_simulate_batch_boundary", "boundary", "not served with per-step boundary data; nothing falls back to a frozen base or wrench"},
+    {"kr_simulate_batch_keypoints", "key-point", "not served with key-point records; nothing falls back to a call without them"},
+    {"kr_simulate_batch_bank", "bank", "not served with a network bank; nothing falls back to the handle's MLP"},
+};
+// kr_simulate_batch_keypoints: kp[T][B][K][KR_SLOTS] of the call's element type and the marked grid points, bit j of
+// (mask_lo, mask_hi) = grid point j
+struct KpDst {
+  void* kp = nullptr;
+  int K = 0;
+  unsigned long long mask_lo = 0, mask_hi = 0;
+};
+// The source of one call: what its kind needs, nothing else set
+struct SimSrc {
+  int kind = KR_SRC_HANDLE;
+  const kr_param_table* table = nullptr;  // every kind but KR_SRC_HANDLE
+  const void* hist = nullptr;             // KR_SRC_LOADS: loads[B][T][6]; KR_SRC_BOUNDARY / _KEYPOINTS: bnd[B][T][KR_BND]; element type of the call
+  KpDst kp;                               // KR_SRC_KEYPOINTS: where the key-point records go
+  const kr_mlp_bank* bank = nullptr;      // KR_SRC_BANK
+  const int32_t* net_idx = nullptr;       // ... and the device copy of the caller's index array
+};
 struct SimPlan {
   int rc = KR_OK;     // KR_OK, or what a refused call returns (`why` says why)
   int path = 0;       // what last_sim_path reports: 0 / 1 one launch per step (single / multiple shooting), 2 persistent
@@ -294,17 +324,21 @@ struct SimPlan {
 struct PlanQuery {
   int64_t B, T_steps;
   int scheme, use_nn;
-  int source = KR_SRC_HANDLE;
+  int source = KR_SRC_HANDLE;          // SimSrc::kind
   int N = 0;                           // table calls: the table's
   const kr_mlp_bank* bank = nullptr;   // bank calls
   // the aliasing rule of KR_FAM_MSWO with its tiles in HBM
   const void* prev_init = nullptr;
   const void* states = nullptr;
   int64_t slot_elems = 0;
-  bool loads = false;                  // kr_simulate_batch_loads: a table call with a tip-wrench history
-  bool bnd = false;                    // kr_simulate_batch_boundary: a table call with a base and tip-wrench history
-  bool kp = false;                     // kr_simulate_batch_keypoints: a boundary call that also writes key-point records
 };
+// the query of a simulate call on `src` (simulate_impl, kr_api.hip)
+inline PlanQuery plan_query(const SimSrc& src, int64_t B, int64_t T_steps, int scheme, int use_nn, const void* prev_init = nullptr,
+                            const void* states = nullptr, int64_t slot_elems = 0) {
+  PlanQuery q{B, T_steps, scheme, use_nn, src.kind, src.table ? src.table->N : 0, src.bank};
+  q.prev_init = prev_init; q.states = states; q.slot_elems = slot_elems;
+  return q;
+}
 template <typename T>
 SimPlan plan_simulate(const kr_handle* h, const PlanQuery& q);
 // kr_step_batch, kr_residual_* (mode 1) and the steps of a kr_simulate_batch that takes one launch per step
@@ -345,23 +379,8 @@ inline int launch(hipStream_t s, void (*kern)(P...), dim3 grid, dim3 block, size
   return launch(LaunchAt{s, false}, kern, grid, block, smem, args...);
 }
 
-// kr_simulate_batch_keypoints: kp[T][B][K][KR_SLOTS] of the call's element type and the marked grid points, bit j of
-// (mask_lo, mask_hi) = grid point j (kp == nullptr: no key points)
-struct KpDst {
-  void* kp = nullptr;
-  int K = 0;
-  unsigned long long mask_lo = 0, mask_hi = 0;
-};
 // The launchers: each maps a plan to the template instantiation it names and launches it, in the unit that holds the
 // kernel.
-struct SimSrc {
-  const kr_param_table* table = nullptr;
-  const kr_mlp_bank* bank = nullptr;
-  const int32_t* net_idx = nullptr;  // device copy of the caller's index array
-  const void* loads = nullptr;       // kr_simulate_batch_loads: [B][T][6], element type of the call
-  const void* bnd = nullptr;         // kr_simulate_batch_boundary: [B][T][KR_BND], element type of the call
-  KpDst kp;                          // kr_simulate_batch_keypoints (with bnd): where the key-point records go
-};
 template <typename T>
 int launch_step(kr_handle* h, const SimPlan& p, const StepArgs<T>& a, hipStream_t s);            // kr_sim_*.hip
 template <typename T>
@@ -379,19 +398,18 @@ int launch_mso_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const La
 template <typename T>
 int launch_mswo_sim(kr_handle* h, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);    // kr_mswo_*.hip
 template <typename T>
-int launch_tab_sim(kr_handle* h, const kr_param_table* t, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_tab_*.hip
+int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s);   // kr_tab_*.hip
+// the table kinds, one signature: each fills its kernels' source struct from `src` (launch_one_wave_src, kr_tab_impl.hpp)
 template <typename T>
-int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hipStream_t s);
+int launch_tab_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_tab_*.hip
 template <typename T>
-int launch_bank_sim(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bk, const int32_t* net_idx, const SimPlan& p,
-                    const SimArgs<T>& a, const LaunchAt& at);                                    // kr_bank_*.hip
+int launch_load_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_load_*.hip
 template <typename T>
-int launch_load_sim(kr_handle* h, const kr_param_table* t, const T* loads, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_load_*.hip
+int launch_bnd_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bnd_*.hip
 template <typename T>
-int launch_bnd_sim(kr_handle* h, const kr_param_table* t, const T* bnd, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bnd_*.hip
+int launch_kp_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_kp_*.hip
 template <typename T>
-int launch_kp_sim(kr_handle* h, const kr_param_table* t, const T* bnd, const KpDst& kd, const SimPlan& p, const SimArgs<T>& a,
-                  const LaunchAt& at);  // kr_kp_*.hip
+int launch_bank_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bank_*.hip
 int ensure_resume(kr_handle* h, int64_t B);
 int ensure_hist_ws(kr_handle* h, size_t bytes);
 
@@ -406,11 +424,14 @@ inline int launch_sim(kr_handle* h, const SimPlan& p, const SimSrc& src, SimArgs
     if (int rc = ensure_hist_ws(h, p.hist_ws_bytes)) return rc;
     a.hist_ws = static_cast<T*>(h->hist_ws);
   }
-  if (src.bnd && src.kp.kp) return launch_kp_sim<T>(h, src.table, static_cast<const T*>(src.bnd), src.kp, p, a, at);
-  if (src.bnd) return launch_bnd_sim<T>(h, src.table, static_cast<const T*>(src.bnd), p, a, at);
-  if (src.loads) return launch_load_sim<T>(h, src.table, static_cast<const T*>(src.loads), p, a, at);
-  if (src.bank) return launch_bank_sim<T>(h, src.table, src.bank, src.net_idx, p, a, at);
-  if (src.table) return launch_tab_sim<T>(h, src.table, p, a, at);
+  switch (src.kind) {
+    case KR_SRC_TABLE: return launch_tab_sim<T>(h, src, p, a, at);
+    case KR_SRC_LOADS: return launch_load_sim<T>(h, src, p, a, at);
+    case KR_SRC_BOUNDARY: return launch_bnd_sim<T>(h, src, p, a, at);
+    case KR_SRC_KEYPOINTS: return launch_kp_sim<T>(h, src, p, a, at);
+    case KR_SRC_BANK: return launch_bank_sim<T>(h, src, p, a, at);
+    default: break;  // (KR_SRC_HANDLE: by family)
+  }
   switch (p.family) {
     case KR_FAM_MSO:
       if (int rc = launch_mso_sim<T>(h, p, a, at)) return rc;

@@ -32,25 +32,16 @@ namespace kr {
 
 // launch_bnd_sim with the key-point records
 template <typename T>
-int launch_kp_sim(kr_handle* h, const kr_param_table* t, const T* bnd, const KpDst& kd, const SimPlan& p, const SimArgs<T>& a,
-                  const LaunchAt& at) {
-  constexpr int HS = hs_phys<T>();
+int launch_kp_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
   static_assert(rod_src_step_slots<T, RodTableBndKp<T>>::count == KR_BND, "knode_rod.h: KR_BND values per rod and step");
   static_assert(KR_SLOTS == 28, "rod_src_keypoints: the records of kp are KR_SLOTS wide");
-  RodTableBndKp<T> tab;
-  tab.rows = (const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t);
-  tab.N = t->N;
-  tab.bnd = bnd;
-  tab.kp = static_cast<T*>(kd.kp);
-  tab.K = kd.K;
-  tab.mask_lo = kd.mask_lo;
-  tab.mask_hi = kd.mask_hi;
-  const dim3 grid((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), block(WAVE * MS_WPB);
-  if (p.nn) return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, true, 1, RodTableBndKp<T>>, grid, block, p.smem[0], tab, a, mlpdev<T>(h));
-  if (p.family == KR_FAM_MSO)
-    if (int rc = launch_mso_inst<T, 1>(tab, p, a, at)) return rc;
-  return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, false, 1, RodTableBndKp<T>>, grid, block, p.smem[p.family == KR_FAM_MSO ? 1 : 0], tab, a,
-                mlpdev<T>(h));
+  auto tab = table_src<T, RodTableBndKp<T>>(src.table);
+  tab.bnd = static_cast<const T*>(src.hist);
+  tab.kp = static_cast<T*>(src.kp.kp);
+  tab.K = src.kp.K;
+  tab.mask_lo = src.kp.mask_lo;
+  tab.mask_hi = src.kp.mask_hi;
+  return launch_one_wave_src<T>(h, tab, p, a, at);
 }
 
 }  // namespace kr

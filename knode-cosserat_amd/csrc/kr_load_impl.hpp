@@ -25,18 +25,10 @@ namespace kr {
 
 // launch_tab_sim with the wrench history
 template <typename T>
-int launch_load_sim(kr_handle* h, const kr_param_table* t, const T* loads, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
-  constexpr int HS = hs_phys<T>();
-  RodTableLoads<T> tab;
-  tab.rows = (const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t);
-  tab.N = t->N;
-  tab.loads = loads;
-  const dim3 grid((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), block(WAVE * MS_WPB);
-  if (p.nn) return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, true, 1, RodTableLoads<T>>, grid, block, p.smem[0], tab, a, mlpdev<T>(h));
-  if (p.family == KR_FAM_MSO)
-    if (int rc = launch_mso_inst<T, 1>(tab, p, a, at)) return rc;
-  return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, false, 1, RodTableLoads<T>>, grid, block, p.smem[p.family == KR_FAM_MSO ? 1 : 0], tab, a,
-                mlpdev<T>(h));
+int launch_load_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  auto tab = table_src<T, RodTableLoads<T>>(src.table);
+  tab.loads = static_cast<const T*>(src.hist);
+  return launch_one_wave_src<T>(h, tab, p, a, at);
 }
 
 }  // namespace kr

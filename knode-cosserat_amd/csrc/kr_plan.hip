@@ -148,18 +148,10 @@ SimPlan plan_one_wave(const kr_handle* h, SimPlan p, const PlanQuery& q, int N, 
 template <typename T>
 SimPlan plan_table(const kr_handle* h, const PlanQuery& q) {
   const bool bank = q.source == KR_SRC_BANK;
-  const char* const word = bank ? "bank" : q.kp ? "key-point" : q.bnd ? "boundary" : q.loads ? "loads" : "table";
+  const SimKindText& text = kSimKindText[q.source];
+  const char* const word = text.word;
   char what[128];
-  auto refuse = [&](const char* w) {
-    if (q.kp)
-      return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_keypoints: %s (not served with key-point records; nothing falls back to a call without them)", w);
-    if (q.bnd)
-      return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_boundary: %s (not served with per-step boundary data; nothing falls back to a frozen base or wrench)", w);
-    if (q.loads)
-      return refused(KR_E_UNSUPPORTED, "kr_simulate_batch_loads: %s (not served with per-step tip loads; nothing falls back to a frozen wrench)", w);
-    return bank ? refused(KR_E_UNSUPPORTED, "kr_simulate_batch_bank: %s (not served with a network bank; nothing falls back to the handle's MLP)", w)
-                : refused(KR_E_UNSUPPORTED, "kr_simulate_batch_table: %s (not served with a parameter table; nothing falls back to the handle's parameters)", w);
-  };
+  auto refuse = [&](const char* w) { return refused(KR_E_UNSUPPORTED, "%s: %s (%s)", text.api, w, text.tail); };
   if (q.scheme != KR_EULER) return refuse("only Euler sweeps (scheme = KR_EULER)");
   if (!one_wave_range(q.N)) {
     std::snprintf(what, sizeof what, "N = %d, the one-wavefront persistent %s 9 <= N <= 128", q.N, bank ? "kernel serves" : "kernels serve");

@@ -2,6 +2,6 @@
 #define KR_MS_NO_INST
 #include "kr_tab_impl.hpp"
 namespace kr {
-template int launch_tab_sim<double>(kr_handle*, const kr_param_table*, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
+template int launch_tab_sim<double>(kr_handle*, const SimSrc&, const SimPlan&, const SimArgs<double>&, const LaunchAt&);
 template int launch_tab_init_straight<double>(kr_handle*, const kr_param_table*, double*, hipStream_t);
 }

@@ -43,18 +43,33 @@ int launch_tab_init_straight(kr_handle* h, const kr_param_table* t, T* state, hi
   return launch(s, init_straight_tab_kernel<T>, dim3(grid_for(t->B * t->N)), dim3(256), 0, t->N, t->L, t->B, state);
 }
 
-// KR_FAM_MSO: two launches, as with the handle's constants - the overlapped kernel, then the take-over launch for what
-// it left behind (a.resume); KR_FAM_MS_SIM: the one-wavefront persistent kernel alone
-template <typename T>
-int launch_tab_sim(kr_handle* h, const kr_param_table* t, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+// A plan of plan_table carried out on the kernels of one parameter source PSRC (RodTable<T> or a struct derived from it):
+// the MLP-on persistent kernel; or - KR_FAM_MSO - two launches, as with the handle's constants: the overlapped kernel, then
+// the take-over launch for what it left behind (a.resume); or - KR_FAM_MS_SIM - the one-wavefront persistent kernel alone.
+// The unit that calls it holds these three instantiations.
+template <typename T, typename PSRC>
+int launch_one_wave_src(kr_handle* h, const PSRC& tab, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
   constexpr int HS = hs_phys<T>();
-  const RodTable<T> tab{(const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t), t->N};
   const dim3 grid((unsigned)((a.B + MS_WPB - 1) / MS_WPB)), block(WAVE * MS_WPB);
-  if (p.nn) return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, true, 1, RodTable<T>>, grid, block, p.smem[0], tab, a, mlpdev<T>(h));
+  if (p.nn) return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, true, 1, PSRC>, grid, block, p.smem[0], tab, a, mlpdev<T>(h));
   if (p.family == KR_FAM_MSO)
     if (int rc = launch_mso_inst<T, 1>(tab, p, a, at)) return rc;
-  return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, false, 1, RodTable<T>>, grid, block, p.smem[p.family == KR_FAM_MSO ? 1 : 0], tab, a,
+  return launch(at, ms_sim_kernel<T, true, KR_EULER, HS, false, 1, PSRC>, grid, block, p.smem[p.family == KR_FAM_MSO ? 1 : 0], tab, a,
                 mlpdev<T>(h));
+}
+
+// the table part of every source struct
+template <typename T, typename PSRC>
+PSRC table_src(const kr_param_table* t) {
+  PSRC tab{};
+  tab.rows = (const KR_CONSTANT_AS RodConst<T>*)table_rows<T>(t);
+  tab.N = t->N;
+  return tab;
+}
+
+template <typename T>
+int launch_tab_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at) {
+  return launch_one_wave_src<T>(h, table_src<T, RodTable<T>>(src.table), p, a, at);
 }
 
 }  // namespace kr

@@ -361,31 +361,23 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     only: states and scores stay finite and later steps may report 0 again - ``status`` 2 at t0 is the only mark.  A NaN
     base value (``base_motion``) enters the sweeps like a NaN tension."""
     loads = base = kp_idx = None
-    if key_points is not None:  # (validated on the host before anything touches the device)
-        if per_robot_nn:
-            raise kn.KrError("simulate_batch: key_points with per_robot_nn=True is not served (key-point records have no network-bank form)")
+    # (everything below is validated on the host before anything touches the device)
+    per_step = (("key_points", key_points, "key-point records have"), ("base_motion", base_motion, "per-step boundary data has"),
+                ("tip_loads", tip_loads, "per-step tip loads have"))
+    for name, value, what in per_step:
+        if value is not None and per_robot_nn:
+            raise kn.KrError(f"simulate_batch: {name} with per_robot_nn=True is not served ({what} no network-bank form)")
+    if score is not None or any(value is not None for _, value, _ in per_step):
         ctl_shape = np.asarray(ctl).shape
         if len(ctl_shape) != 3:
             raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+    if key_points is not None:
         kp_idx = _key_points(key_points, int(robot.N))
-    if base_motion is not None:  # (validated on the host before anything touches the device)
-        if per_robot_nn:
-            raise kn.KrError("simulate_batch: base_motion with per_robot_nn=True is not served (per-step boundary data has no network-bank form)")
-        ctl_shape = np.asarray(ctl).shape
-        if len(ctl_shape) != 3:
-            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+    if base_motion is not None:
         base = _base_motion(base_motion, int(ctl_shape[0]), int(ctl_shape[1]), check_finite)
-    if tip_loads is not None:  # (validated on the host before anything touches the device)
-        if per_robot_nn:
-            raise kn.KrError("simulate_batch: tip_loads with per_robot_nn=True is not served (per-step tip loads have no network-bank form)")
-        ctl_shape = np.asarray(ctl).shape
-        if len(ctl_shape) != 3:
-            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+    if tip_loads is not None:
         loads = _tip_loads(tip_loads, int(ctl_shape[0]), int(ctl_shape[1]), check_finite)
-    if score is not None:  # (validated on the host before anything touches the device)
-        ctl_shape = np.asarray(ctl).shape
-        if len(ctl_shape) != 3:
-            raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+    if score is not None:
         score_ref, score_point = _score_reference(robot, score, int(ctl_shape[0]), int(ctl_shape[1]), tip_only and kp_idx is None)
         if tip_only and score_point not in kp_idx.tolist():
             raise kn.KrError(f"simulate_batch: score point {score_point} is not one of the key points {kp_idx.tolist()} "

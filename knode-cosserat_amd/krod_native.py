@@ -379,6 +379,20 @@ class MlpBank:
             pass
 
 
+# Handle.simulate, per kind of call: what it says beside bank= / net_of_rod=, beside loads=, and when what it needs is missing
+_SIM_RULES = {
+    "keypoints": ("key_points= together with bank=: key-point records are not served with a network bank",
+                  "key_points= together with loads=: a key-point call takes bnd (its last six columns are the tip wrench)",
+                  "a key-point call needs table= and bnd= (a caller with a fixed boundary repeats the rows' values)"),
+    "boundary": ("bnd= together with bank=: per-step boundary data is not served with a network bank",
+                 "bnd= together with loads=: the last six columns of bnd are the tip wrench",
+                 "a boundary call needs table= (a table of identical rows when only the boundary varies)"),
+    "loads": ("loads= together with bank=: per-step tip loads are not served with a network bank", None,
+              "a loads call needs table= (a table of identical rows when only the loads vary)"),
+    "bank": (None, None, "a bank call needs table=, bank= and net_of_rod= together"),
+}
+
+
 class Handle:
     """Owns one kr_handle (one device, one parameter set)."""
 
@@ -562,79 +576,52 @@ class Handle:
                  use_nn=False, prev_init=None, table=None, bank=None, net_of_rod=None, loads=None, bnd=None, key_points=None,
                  kp=None):
         B, T = ctl.shape[0], ctl.shape[1]
-        if key_points is not None or kp is not None:
+        banked = bank is not None or net_of_rod is not None
+        kind = ("keypoints" if key_points is not None or kp is not None else "boundary" if bnd is not None else
+                "loads" if loads is not None else "bank" if banked else "table" if table is not None else "handle")
+        # the exclusion rules and the shared checks, in the order a caller with two mistakes hears of them
+        no_bank, no_loads, needs = _SIM_RULES.get(kind, (None, None, None))
+        if no_bank and banked:
+            raise KrError(no_bank)
+        if no_loads and loads is not None:
+            raise KrError(no_loads)
+        if needs and (table is None or (kind == "keypoints" and bnd is None) or (kind == "bank" and (bank is None or net_of_rod is None))):
+            raise KrError(needs)
+        if kind == "keypoints" and (key_points is None or kp is None):
+            raise KrError("a key-point call needs key_points= and kp= together")
+        if table is not None and B != table.B:
+            raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
+        # rod b, step t: loads[b, t] = F_tip (3), M_tip (3), or bnd[b, t] = p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3),
+        # in place of its row's
+        name, hist, width = ("loads", loads, 6) if kind == "loads" else ("bnd", bnd, KR_BND)
+        if kind in ("keypoints", "boundary", "loads") and (tuple(hist.shape) != (B, T, width) or hist.dtype != ctl.dtype or not hist.is_contiguous()):
+            raise KrError(f"{name} must be a contiguous [{B}, {T}, {width}] tensor of {ctl.dtype}; got {tuple(hist.shape)} {hist.dtype}")
+        if kind in ("keypoints", "bank"):
+            idx = np.ascontiguousarray(np.asarray(key_points if kind == "keypoints" else net_of_rod).reshape(-1), dtype=np.int32)
+            idx_p, K = idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size)
+        if kind == "keypoints" and (tuple(kp.shape) != (T, B, K, KR_SLOTS) or kp.dtype != ctl.dtype or not kp.is_contiguous()):
             # kp[t, b, k] receives the complete record of grid point key_points[k] of the state step t writes
-            if bank is not None or net_of_rod is not None:
-                raise KrError("key_points= together with bank=: key-point records are not served with a network bank")
-            if loads is not None:
-                raise KrError("key_points= together with loads=: a key-point call takes bnd (its last six columns are the tip wrench)")
-            if table is None or bnd is None:
-                raise KrError("a key-point call needs table= and bnd= (a caller with a fixed boundary repeats the rows' values)")
-            if key_points is None or kp is None:
-                raise KrError("a key-point call needs key_points= and kp= together")
-            if B != table.B:
-                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
-            if tuple(bnd.shape) != (B, T, KR_BND) or bnd.dtype != ctl.dtype or not bnd.is_contiguous():
-                raise KrError(f"bnd must be a contiguous [{B}, {T}, {KR_BND}] tensor of {ctl.dtype}; got {tuple(bnd.shape)} {bnd.dtype}")
-            idx = np.ascontiguousarray(np.asarray(key_points).reshape(-1), dtype=np.int32)
-            K = int(idx.size)
-            if tuple(kp.shape) != (T, B, K, KR_SLOTS) or kp.dtype != ctl.dtype or not kp.is_contiguous():
-                raise KrError(f"kp must be a contiguous [{T}, {B}, {K}, {KR_SLOTS}] tensor of {ctl.dtype}; got {tuple(kp.shape)} {kp.dtype}")
-            check(self.lib.kr_simulate_batch_keypoints(self._h, table._t, T, scheme, _ptr(ctl), _ptr(bnd), K,
-                                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(kp), _ptr(states),
-                                                       int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
-                                                       int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
-            return
-        if bnd is not None:  # rod b, step t: bnd[b, t] = p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) in place of its row's
-            if bank is not None or net_of_rod is not None:
-                raise KrError("bnd= together with bank=: per-step boundary data is not served with a network bank")
-            if loads is not None:
-                raise KrError("bnd= together with loads=: the last six columns of bnd are the tip wrench")
-            if table is None:
-                raise KrError("a boundary call needs table= (a table of identical rows when only the boundary varies)")
-            if B != table.B:
-                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
-            if tuple(bnd.shape) != (B, T, KR_BND) or bnd.dtype != ctl.dtype or not bnd.is_contiguous():
-                raise KrError(f"bnd must be a contiguous [{B}, {T}, {KR_BND}] tensor of {ctl.dtype}; got {tuple(bnd.shape)} {bnd.dtype}")
-            check(self.lib.kr_simulate_batch_boundary(self._h, table._t, T, scheme, _ptr(ctl), _ptr(bnd), _ptr(states),
-                                                      int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
-                                                      int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
-            return
-        if loads is not None:  # rod b, step t: tip wrench loads[b, t] = F_tip (3), M_tip (3) in place of its row's
-            if bank is not None or net_of_rod is not None:
-                raise KrError("loads= together with bank=: per-step tip loads are not served with a network bank")
-            if table is None:
-                raise KrError("a loads call needs table= (a table of identical rows when only the loads vary)")
-            if B != table.B:
-                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
-            if tuple(loads.shape) != (B, T, 6) or loads.dtype != ctl.dtype or not loads.is_contiguous():
-                raise KrError(f"loads must be a contiguous [{B}, {T}, 6] tensor of {ctl.dtype}; got {tuple(loads.shape)} {loads.dtype}")
-            check(self.lib.kr_simulate_batch_loads(self._h, table._t, T, scheme, _ptr(ctl), _ptr(loads), _ptr(states),
-                                                   int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
-                                                   int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
-            return
-        if bank is not None or net_of_rod is not None:  # rod b: row b of the table, network net_of_rod[b] of the bank
-            if bank is None or net_of_rod is None or table is None:
-                raise KrError("a bank call needs table=, bank= and net_of_rod= together")
-            if B != table.B:
-                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
-            idx = np.ascontiguousarray(np.asarray(net_of_rod).reshape(-1), dtype=np.int32)
-            if idx.size != B:
-                raise KrError(f"ctl holds {B} rods, net_of_rod {idx.size}")
-            check(self.lib.kr_simulate_batch_bank(self._h, table._t, bank._b, idx.ctypes.data_as(C.POINTER(C.c_int32)), T, scheme,
-                                                  _ptr(ctl), _ptr(states), int(bool(ring)), _ptr(G), _ptr(tip), float(tol),
-                                                  int(maxit), _ptr(status), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
-            return
-        if table is not None:  # rod b takes row b of the table instead of the handle's parameters
-            if B != table.B:
-                raise KrError(f"ctl holds {B} rods, the parameter table {table.B}")
-            check(self.lib.kr_simulate_batch_table(self._h, table._t, T, scheme, _ptr(ctl), _ptr(states), int(bool(ring)),
-                                                   _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status),
-                                                   int(bool(use_nn)), _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
-            return
-        check(self.lib.kr_simulate_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), int(bool(ring)), _ptr(G),
-                                         _ptr(tip), float(tol), int(maxit), _ptr(status), int(bool(use_nn)),
-                                         _ptr(prev_init), dtype_code(ctl.dtype), _stream()))
+            raise KrError(f"kp must be a contiguous [{T}, {B}, {K}, {KR_SLOTS}] tensor of {ctl.dtype}; got {tuple(kp.shape)} {kp.dtype}")
+        if kind == "bank" and K != B:  # rod b: row b of the table, network net_of_rod[b] of the bank
+            raise KrError(f"ctl holds {B} rods, net_of_rod {K}")
+        # one argument list per kind around what all share
+        lib, h, nn = self.lib, self._h, int(bool(use_nn))
+        head = (T, scheme, _ptr(ctl))
+        mid = (_ptr(states), int(bool(ring)), _ptr(G), _ptr(tip), float(tol), int(maxit), _ptr(status))
+        end = (_ptr(prev_init), dtype_code(ctl.dtype), _stream())
+        if kind == "handle":
+            rc = lib.kr_simulate_batch(h, B, *head, *mid, nn, *end)
+        elif kind == "table":  # rod b takes row b of the table instead of the handle's parameters
+            rc = lib.kr_simulate_batch_table(h, table._t, *head, *mid, nn, *end)
+        elif kind == "loads":
+            rc = lib.kr_simulate_batch_loads(h, table._t, *head, _ptr(loads), *mid, nn, *end)
+        elif kind == "boundary":
+            rc = lib.kr_simulate_batch_boundary(h, table._t, *head, _ptr(bnd), *mid, nn, *end)
+        elif kind == "keypoints":
+            rc = lib.kr_simulate_batch_keypoints(h, table._t, *head, _ptr(bnd), K, idx_p, _ptr(kp), *mid, nn, *end)
+        else:  # (a bank's networks are on: no use_nn)
+            rc = lib.kr_simulate_batch_bank(h, table._t, bank._b, idx_p, *head, *mid, *end)
+        check(rc)
 
     # -- evaluation metrics ------------------------------------------------------
     def dtw(self, a, b, out=None):

@@ -2,7 +2,7 @@
 // (tests/test_base_motion_cpu.py).
 //
 // A stand-alone host program, compiled host-only like select_probe.hip: it runs the library's planner (plan_simulate,
-// kr_plan.hip) on a matrix of table queries, once with PlanQuery::loads and once with PlanQuery::bnd, and prints one
+// kr_plan.hip) on a matrix of table queries, once for a loads source and once for a boundary source (SimSrc::kind), and prints one
 // line per query and form: "<label> | loads|bnd | rc path family W occ nn overlap smem0 smem1 | why".  The test
 // compares the two forms field by field; a refusal's text must name its own call.
 #define KR_MS_NO_INST
@@ -46,12 +46,12 @@ static void run(const char* dt, int N, long long B, int scheme, int net, const O
     else if (on == "ms_mode") h.ms_mode = o.val;
     else if (on == "ms_batch_limit") h.ms_batch_limit = o.val;
     else if (on == "lds_limit") h.lds_limit = o.val;
-    kr::PlanQuery q{B, 2, scheme, net != 0};
-    q.source = kr::KR_SRC_TABLE;
-    q.N = N;
-    q.loads = form == 0;
-    q.bnd = form == 1;
-    const kr::SimPlan p = kr::plan_simulate<T>(&h, q);
+    kr_param_table t;
+    t.N = N;
+    kr::SimSrc src;
+    src.kind = form ? kr::KR_SRC_BOUNDARY : kr::KR_SRC_LOADS;
+    src.table = &t;
+    const kr::SimPlan p = kr::plan_simulate<T>(&h, kr::plan_query(src, B, 2, scheme, net != 0));
     std::printf("%s,%d,%lld,%c,n%d,%s=%d | %s | %d %d %d %d %d %d %d %zu %zu | %s\n", dt, N, B, scheme == KR_EULER ? 'E' : 'R', net,
                 o.name ? o.name : "none", o.val, form ? "bnd" : "loads", p.rc, p.path, (int)p.family, p.W, p.occ, (int)p.nn, (int)p.overlap,
                 p.smem[0], p.smem[1], p.why);

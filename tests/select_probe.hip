@@ -9,8 +9,14 @@
 // the launcher interfaces this planner replaced.  The predictor-image members (pred_io / pred_load, pred / pred_reset)
 // are the probe's own constants in those lines; what a simulate call puts there is plan_pred_image's decision, which the
 // "pred" lines at the end print for test_select_cpu.py to compare with the rule of the parent's simulate_impl.
+// The "src" lines drive the five table-family sources (table, bank, loads, boundary, key points) through launch_sim and
+// also print the source struct as the kernel received it, read back from the launch's own arguments: every field the
+// launcher fills is a distinct sentinel, so a dropped or swapped one shows (tests/golden/selection_parent_sources.txt.gz).
 #define KR_MS_NO_INST
 #include "kr_bank_impl.hpp"
+#include "kr_load_impl.hpp"
+#include "kr_bnd_impl.hpp"
+#include "kr_kp_impl.hpp"
 #include "kr_mswo_impl.hpp"
 #include "kr_mswn_impl.hpp"
 #include "kr_msn_impl.hpp"
@@ -40,6 +46,7 @@ static std::string g_expect;                 // scalar members of the SimArgs / 
 static const void* g_attr_kern = nullptr;    // kernel of the last hipFuncGetAttributes (prepare entries)
 static dim3 g_grid, g_block;
 static size_t g_smem;
+static bool g_print_src = false;             // "src" lines: every launch also prints its source struct
 
 static std::string kernel_name(const void* func) {
   Dl_info info;
@@ -111,6 +118,27 @@ static std::string step_flags(const kr::StepArgs<T>& a) {
   return s;
 }
 
+// The parameter source (first kernel argument) and, for a bank kernel, the network source (third) as the launch passed them
+template <typename T>
+static std::string src_fields(const std::string& n, void** args) {
+  char b[320];
+  const auto* t = static_cast<const kr::RodTable<T>*>(args[0]);
+  int at = std::snprintf(b, sizeof b, " src{rows=%p N=%d", (const void*)t->rows, t->N);
+  if (n.find("RodTableBndKp<") != std::string::npos) {
+    const auto* k = static_cast<const kr::RodTableBndKp<T>*>(args[0]);
+    at += std::snprintf(b + at, sizeof b - at, " bnd=%p kp=%p K=%d lo=%llx hi=%llx", (const void*)k->bnd, (const void*)k->kp, k->K, k->mask_lo, k->mask_hi);
+  } else if (n.find("RodTableBnd<") != std::string::npos) {
+    at += std::snprintf(b + at, sizeof b - at, " bnd=%p", (const void*)static_cast<const kr::RodTableBnd<T>*>(args[0])->bnd);
+  } else if (n.find("RodTableLoads<") != std::string::npos) {
+    at += std::snprintf(b + at, sizeof b - at, " loads=%p", (const void*)static_cast<const kr::RodTableLoads<T>*>(args[0])->loads);
+  }
+  if (n.find("MlpBank<") != std::string::npos) {
+    const auto* k = static_cast<const kr::MlpBank<T>*>(args[2]);
+    at += std::snprintf(b + at, sizeof b - at, " idx=%p stride=%llu layers=%d", (const void*)k->net_of_rod, k->stride, k->n_layers);
+  }
+  return std::string(b) + "}";
+}
+
 extern "C" {
 hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t smem, hipStream_t) {
   g_grid = grid; g_block = block; g_smem = smem;
@@ -132,6 +160,7 @@ hipError_t hipLaunchKernel(const void* func, dim3 grid, dim3 block, void** args,
     s += f64 ? step_flags(*static_cast<kr::StepArgs<double>*>(args[1])) : step_flags(*static_cast<kr::StepArgs<float>*>(args[1]));
   else
     s += "-";
+  if (g_print_src) s += f64 ? src_fields<double>(n, args) : src_fields<float>(n, args);
   g_launches.push_back(s);
   return hipSuccess;
 }
@@ -149,8 +178,8 @@ void __hipUnregisterFatBinary(void**) {}
 }
 
 // ---- the matrix ----
-enum Entry { E_SIM, E_STEP, E_RESID, E_TAB, E_BANK, E_PREP };
-static const char* const kEntryName[] = {"sim", "step", "resid", "tab", "bank", "prep"};
+enum Entry { E_SIM, E_STEP, E_RESID, E_TAB, E_BANK, E_PREP, E_LOADS, E_BND, E_KP };
+static const char* const kEntryName[] = {"sim", "step", "resid", "tab", "bank", "prep", "loads", "bnd", "kp"};
 // network: 0 none; 1 served three-layer (mfma_ok, jvp_ok); 2 mfma_ok without jvp_ok; 3 neither; 4 nn_input_history = 1;
 // 5 use_nn with no network set.  Bank entries: the bank's network 0 has the flags of kind 1 / 2 / 3
 struct Case {
@@ -165,6 +194,15 @@ struct Case {
 
 static void* const kDummy = reinterpret_cast<void*>(0x10000);   // a non-null "device" pointer nobody dereferences
 static unsigned char* const kStates = reinterpret_cast<unsigned char*>(0x40000000);
+// the fields of a table-family source, each its own sentinel
+static void* const kRowsF = reinterpret_cast<void*>(0x11000);
+static void* const kRowsD = reinterpret_cast<void*>(0x12000);
+static void* const kLoads = reinterpret_cast<void*>(0x20000);
+static void* const kBnd = reinterpret_cast<void*>(0x30000);
+static void* const kKp = reinterpret_cast<void*>(0x50000);
+static void* const kNetIdx = reinterpret_cast<void*>(0x60000);
+constexpr int kKpK = 3;
+constexpr unsigned long long kKpLo = 0x0000000100000005ull, kKpHi = 0x8000000000000002ull;
 constexpr int64_t kSteps = 2;
 
 static void set_option(kr_handle& h, const char* opt, int val) {
@@ -240,7 +278,7 @@ static kr::StepArgs<T> step_args(const kr_handle& h, const Case& c, int mode) {
 
 static std::string label(const Case& c) {
   char b[160];
-  std::snprintf(b, sizeof b, "%s,%d,%lld,%c,d%d,n%d,%s", c.f64 ? "f64" : "f32", c.N, (long long)c.B,
+  std::snprintf(b, sizeof b, "%s%s,%d,%lld,%c,d%d,n%d,%s", g_print_src ? "src " : "", c.f64 ? "f64" : "f32", c.N, (long long)c.B,
                 c.scheme == KR_EULER ? 'E' : 'R', c.diag, c.net, kEntryName[c.entry]);
   std::string s = b;
   if (c.opt) s += std::string(",") + c.opt + "=" + std::to_string(c.val);
@@ -259,6 +297,10 @@ static void print_line(const Case& c, int rc, int path, int overlap, int W) {
 
 static void run_case(const Case& c);  // (the interfaces under test)
 static void run_pred_matrix();
+struct Opt { const char* name; int val; };
+// the option values a table-family call refuses or runs under (section 4 of run_matrix and the "src" lines)
+static const Opt kTableOpts[] = {{nullptr, 0}, {"ms_mode", 0}, {"ms_mode", 1}, {"persistent", 0}, {"ms_batch_limit", 128}, {"waves_per_rod", 1},
+                                 {"waves_per_rod", 2}, {"waves_per_rod", 4}, {"overlap", 0}, {"lds_limit", 65536}, {"mfma_mlp", 0}};
 
 static long run_matrix() {
   long n = 0;
@@ -282,7 +324,6 @@ static long run_matrix() {
               for (int entry : {E_SIM, E_STEP, E_RESID})
                 run(Case{f64 != 0, N, B, scheme, diag, net, entry, nullptr, 0, 0});
   // 2. one option at a time away from its default
-  struct Opt { const char* name; int val; };
   const Opt opts[] = {{"overlap", 0}, {"msw_overlap", 0}, {"waves_per_rod", 1}, {"waves_per_rod", 2}, {"waves_per_rod", 4},
                       {"persistent", 0}, {"ms_mode", 0}, {"ms_mode", 1}, {"ms_batch_limit", 128}, {"lds_limit", 65536}};
   for (int f64 = 0; f64 < 2; ++f64)
@@ -302,13 +343,11 @@ static long run_matrix() {
       for (int prev : {1, 2})
         run(Case{f64 != 0, N, 512, KR_EULER, 1, 0, E_SIM, nullptr, 0, prev});
   // 4. table and bank entries, with the option values and the scheme they refuse
-  const Opt topts[] = {{nullptr, 0}, {"ms_mode", 0}, {"ms_mode", 1}, {"persistent", 0}, {"ms_batch_limit", 128}, {"waves_per_rod", 1},
-                       {"waves_per_rod", 2}, {"waves_per_rod", 4}, {"overlap", 0}, {"lds_limit", 65536}, {"mfma_mlp", 0}};
   for (int f64 = 0; f64 < 2; ++f64)
     for (int N : {8, 9, 100, 128, 129})
       for (int64_t B : {(int64_t)8, (int64_t)2048})
         for (int scheme : schemes)
-          for (const Opt& o : topts) {
+          for (const Opt& o : kTableOpts) {
             for (int net = 0; net < 6; ++net) run(Case{f64 != 0, N, B, scheme, 1, net, E_TAB, o.name, o.val, 0});
             for (int net = 1; net < 4; ++net) run(Case{f64 != 0, N, B, scheme, 1, net, E_BANK, o.name, o.val, 0});
           }
@@ -319,9 +358,30 @@ static long run_matrix() {
   return n;
 }
 
+// the matrix of section 4 for all five table-family sources, every line with the source struct the kernel received
+static long run_src_matrix() {
+  long n = 0;
+  g_print_src = true;
+  for (int f64 = 0; f64 < 2; ++f64)
+    for (int N : {8, 9, 100, 128, 129})
+      for (int64_t B : {(int64_t)8, (int64_t)2048})
+        for (int scheme : {KR_EULER, KR_RK4})
+          for (const Opt& o : kTableOpts)
+            for (int entry : {E_TAB, E_BANK, E_LOADS, E_BND, E_KP})
+              for (int net = entry == E_BANK ? 1 : 0; net < (entry == E_BANK ? 4 : 6); ++net, ++n) {
+                g_launches.clear();
+                kr::g_err.clear();
+                g_attr_kern = nullptr;
+                run_case(Case{f64 != 0, N, B, scheme, 1, net, entry, o.name, o.val, 0});
+              }
+  g_print_src = false;
+  return n;
+}
+
 int main() {
   const long n = run_matrix();
   std::printf("# %ld cases\n", n);
+  std::printf("# %ld source cases\n", run_src_matrix());
   run_pred_matrix();
   return 0;
 }
@@ -347,20 +407,23 @@ static void run_typed(const Case& c) {
   } else {
     kr_param_table t;
     t.B = c.B; t.N = c.N;
-    t.rows_f = static_cast<kr::RodConst<float>*>(kDummy); t.rows_d = static_cast<kr::RodConst<double>*>(kDummy);
+    t.rows_f = static_cast<kr::RodConst<float>*>(kRowsF); t.rows_d = static_cast<kr::RodConst<double>*>(kRowsD);
     kr_mlp_bank bk;
     bk.K = 3; bk.stride = 256;
     set_net(bk.mf, c.net); set_net(bk.md, c.net);
     kr::SimSrc src;
-    if (c.entry == E_TAB || c.entry == E_BANK) src.table = &t;
-    if (c.entry == E_BANK) { src.bank = &bk; src.net_idx = static_cast<const int32_t*>(kDummy); }
+    switch (c.entry) {
+      case E_TAB: src.kind = kr::KR_SRC_TABLE; break;
+      case E_BANK: src.kind = kr::KR_SRC_BANK; src.bank = &bk; src.net_idx = static_cast<const int32_t*>(kNetIdx); break;
+      case E_LOADS: src.kind = kr::KR_SRC_LOADS; src.hist = kLoads; break;
+      case E_BND: src.kind = kr::KR_SRC_BOUNDARY; src.hist = kBnd; break;
+      case E_KP: src.kind = kr::KR_SRC_KEYPOINTS; src.hist = kBnd; src.kp = kr::KpDst{kKp, kKpK, kKpLo, kKpHi}; break;
+      default: break;  // (the handle's own rod)
+    }
+    if (src.kind != kr::KR_SRC_HANDLE) src.table = &t;
     auto sa = sim_args<T>(h, c);
     g_expect = sim_scalars(sa);
-    kr::PlanQuery q{c.B, kSteps, c.scheme, use_nn};
-    q.source = src.bank ? kr::KR_SRC_BANK : src.table ? kr::KR_SRC_TABLE : kr::KR_SRC_HANDLE;
-    q.N = c.N; q.bank = src.bank;
-    q.prev_init = sa.prev_init; q.states = sa.states; q.slot_elems = sa.slot_elems;
-    p = kr::plan_simulate<T>(&h, q);
+    p = kr::plan_simulate<T>(&h, kr::plan_query(src, c.B, kSteps, c.scheme, use_nn, sa.prev_init, sa.states, sa.slot_elems));
     if (!p.rc && p.path == 2) {
       rc = kr::launch_sim<T>(&h, p, src, sa, kr::LaunchAt{nullptr, c.entry == E_PREP});
     } else if (!p.rc) {  // step 0 of the per-step loop
@@ -384,7 +447,6 @@ static void run_case(const Case& c) {
 static void run_pred_matrix() {
   struct NB { int N; int64_t B; };
   const NB nbs[] = {{100, 256}, {100, 1024}, {400, 1024}, {8, 8}, {8, 100000}};  // (the last: more than 1 GB of images)
-  struct Opt { const char* name; int val; };
   const Opt opts[] = {{nullptr, 0}, {"ms_mode", 0}, {"ms_mode", 1}, {"ms_batch_limit", 128}};
   for (const NB& nb : nbs)
     for (int net : {0, 1})

@@ -340,3 +340,223 @@ def test_refusals(torch_cuda, monkeypatch):
     # a long rod: the several-wavefront kernels have no table form
     long_rod = make_robot(None, 400)
     assert "N" in refused(lambda: long_rod._native().param_table([long_rod._params()] * 2), kn.KR_E_UNSUPPORTED)
+
+
+# ---------------------------------------------------------------------------
+# 8. argument errors of the five C entry points of the table family: the (rc, kr_last_error()) pair of each, and which of
+#    two mistakes a caller hears of first.  Nothing is launched.
+# ---------------------------------------------------------------------------
+ARG_ENTRIES = ("table", "loads", "boundary", "keypoints", "bank")
+BAD = "bad"  # (a value the case replaces by something wrong of its kind; see arg_error_call)
+
+
+def arg_error_cases():
+    """[(label, entry, overrides)]: one argument wrong, then the pairs whose outcome depends on the order of the checks."""
+    cases = []
+    for e in ARG_ENTRIES:
+        add = lambda label, **over: cases.append((f"{e}: {label}", e, over))
+        add("null table", t=None)
+        for p in ("ctl", "states", "G"):
+            add(f"null {p}", **{p: None})
+        add("T < 0", T=-1)
+        add("table of another N", t="other_N")
+        add("table of another del_t", t="other_del_t")
+        add("null table, T < 0", t=None, T=-1)
+        add("table of another N, T < 0", t="other_N", T=-1)
+        add("table of another N, T = 0", t="other_N", T=0)
+        add("T < 0, null ctl", T=-1, ctl=None)
+        add("T = 0, null ctl", T=0, ctl=None)
+        add("null ctl, null states, null G", ctl=None, states=None, G=None)
+        add("null states, null G", states=None, G=None)
+        if e in ("loads", "boundary", "keypoints"):
+            add("null history", hist=None)
+            add("null table, null history", t=None, hist=None)
+            add("null history, T < 0", hist=None, T=-1)
+            add("null history, table of another N", hist=None, t="other_N")
+        if e == "keypoints":
+            add("null kp", kp=None)
+            add("misaligned kp", kp=BAD)
+            add("point out of range", idx=[3, 5, 10])
+            add("points not increasing", idx=[3, 7, 5])
+            add("no points", idx=[])
+            add("null kp, point out of range", kp=None, idx=[3, 5, 10])
+            add("misaligned kp, point out of range", kp=BAD, idx=[3, 5, 10])
+            add("point out of range, T < 0", idx=[3, 5, 10], T=-1)
+            add("misaligned kp, table of another N", kp=BAD, t="other_N")
+            add("misaligned kp, T < 0", kp=BAD, T=-1)
+            add("point of the other table's range, table of another N", idx=[3, 5, 20], t="other_N")
+        if e == "bank":
+            add("null bank", bank=None)
+            add("null index array", nets=None)
+            add("index out of range", nets=[0, 1, 2, 0, 1, 0])
+            add("negative index", nets=[0, -1, 0, 0, 0, 0])
+            add("null table, null bank", t=None, bank=None)
+            add("index out of range, T < 0", nets=[0, 1, 2, 0, 1, 0], T=-1)
+            add("index out of range, T = 0", nets=[0, 1, 2, 0, 1, 0], T=0)
+            add("table of another N, index out of range", t="other_N", nets=[0, 1, 2, 0, 1, 0])
+            add("index out of range, null ctl", nets=[0, 1, 2, 0, 1, 0], ctl=None)
+    return cases
+
+
+def arg_error_pairs(torch):
+    """{label: (rc, message or None)} of arg_error_cases() on B = 6, N = 10, T = 2, fp64; None where rc = 0."""
+    import ctypes as C
+
+    import cosserat_oracle as orc
+    import krod_native as kn
+    B, N, T, dt = 6, 10, 2, torch.float64
+    r = make_robot(None, N)
+    h = r._native()
+    slow = make_robot(None, N)
+    slow.del_t = 2 * slow.del_t
+    slow.compute_intermediate_terms()
+    ctl = torch.full((B, T, 4), 5.0, dtype=dt, device=DEV)
+    hist = {"table": None, "bank": None, "loads": torch.zeros((B, T, 6), dtype=dt, device=DEV)}
+    hist["boundary"] = hist["keypoints"] = torch.zeros((B, T, kn.KR_BND), dtype=dt, device=DEV)
+    kp = torch.zeros((T, B, 3, kn.KR_SLOTS), dtype=dt, device=DEV)
+    st = h.new_state(B, dt, n_slots=T + 1)
+    G = torch.zeros((B, 6), dtype=dt, device=DEV)
+    net = orc.make_mlp([28, 64, 64, 25], "elu", seed=15)
+    out = {}
+    with h.param_table([r._params()] * B) as tab, make_robot(None, 23)._native().param_table([make_robot(None, 23)._params()] * B) as tab23, \
+            slow._native().param_table([slow._params()] * B) as tab_slow, h.mlp_bank([(net.weights, net.biases, net.acts)] * 2) as bank:
+        h.init_straight(st[0], table=tab)
+        before = st.clone()
+        ptr = lambda x: None if x is None else x if isinstance(x, int) else C.c_void_p(x.data_ptr())
+        for label, entry, over in arg_error_cases():
+            a = dict(t=tab._t, T=T, ctl=ctl, hist=hist[entry], idx=[3, 5, 7], kp=kp, states=st, G=G, bank=bank._b, nets=[0, 1, 0, 1, 0, 1])
+            a.update(over)
+            if isinstance(a["t"], str):
+                a["t"] = {"other_N": tab23._t, "other_del_t": tab_slow._t}[a["t"]]
+            if a["kp"] is BAD:
+                a["kp"] = kp.data_ptr() + 8
+            ints = lambda v: None if v is None else (C.c_int32 * max(len(v), 1))(*v)
+            own = {"table": (), "bank": (), "loads": (ptr(a["hist"]),), "boundary": (ptr(a["hist"]),),
+                   "keypoints": (ptr(a["hist"]), len(a["idx"]), ints(a["idx"]), ptr(a["kp"]))}[entry]
+            mid = (ptr(a["states"]), 0, ptr(a["G"]), None, 0.0, 0, None)
+            end = (None, kn.dtype_code(dt), None)
+            if entry == "bank":
+                rc = h.lib.kr_simulate_batch_bank(h._h, a["t"], a["bank"], ints(a["nets"]), a["T"], kn.KR_EULER, ptr(a["ctl"]), *mid, *end)
+            else:
+                fn = getattr(h.lib, "kr_simulate_batch_" + entry)
+                rc = fn(h._h, a["t"], a["T"], kn.KR_EULER, ptr(a["ctl"]), *own, *mid, 0, *end)
+            out[label] = (rc, h.lib.kr_last_error().decode() if rc else None)
+        torch.cuda.synchronize()
+        assert torch.equal(st, before) and bool((G == 0).all()) and bool((kp == 0).all())  # nothing ran
+    return out
+
+
+# recorded with this list on the build of the commit before the six entry points shared one call body
+ARG_ERROR_PAIRS = {
+    'table: null table': (-1, 'null pointer argument: t'),
+    'table: null ctl': (-1, 'null pointer argument: ctl'),
+    'table: null states': (-1, 'null pointer argument: states'),
+    'table: null G': (-1, 'null pointer argument: G'),
+    'table: T < 0': (-1, 'T < 0'),
+    'table: table of another N': (-1, "parameter table: N of the table differs from the handle's"),
+    'table: table of another del_t': (-1, "parameter table: del_t of the table differs from the handle's"),
+    'table: null table, T < 0': (-1, 'null pointer argument: t'),
+    'table: table of another N, T < 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'table: table of another N, T = 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'table: T < 0, null ctl': (-1, 'T < 0'),
+    'table: T = 0, null ctl': (0, None),
+    'table: null ctl, null states, null G': (-1, 'null pointer argument: ctl'),
+    'table: null states, null G': (-1, 'null pointer argument: states'),
+    'loads: null table': (-1, 'null pointer argument: t'),
+    'loads: null ctl': (-1, 'null pointer argument: ctl'),
+    'loads: null states': (-1, 'null pointer argument: states'),
+    'loads: null G': (-1, 'null pointer argument: G'),
+    'loads: T < 0': (-1, 'T < 0'),
+    'loads: table of another N': (-1, "parameter table: N of the table differs from the handle's"),
+    'loads: table of another del_t': (-1, "parameter table: del_t of the table differs from the handle's"),
+    'loads: null table, T < 0': (-1, 'null pointer argument: t'),
+    'loads: table of another N, T < 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'loads: table of another N, T = 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'loads: T < 0, null ctl': (-1, 'T < 0'),
+    'loads: T = 0, null ctl': (0, None),
+    'loads: null ctl, null states, null G': (-1, 'null pointer argument: ctl'),
+    'loads: null states, null G': (-1, 'null pointer argument: states'),
+    'loads: null history': (-1, 'null pointer argument: loads'),
+    'loads: null table, null history': (-1, 'null pointer argument: t'),
+    'loads: null history, T < 0': (-1, 'null pointer argument: loads'),
+    'loads: null history, table of another N': (-1, 'null pointer argument: loads'),
+    'boundary: null table': (-1, 'null pointer argument: t'),
+    'boundary: null ctl': (-1, 'null pointer argument: ctl'),
+    'boundary: null states': (-1, 'null pointer argument: states'),
+    'boundary: null G': (-1, 'null pointer argument: G'),
+    'boundary: T < 0': (-1, 'T < 0'),
+    'boundary: table of another N': (-1, "parameter table: N of the table differs from the handle's"),
+    'boundary: table of another del_t': (-1, "parameter table: del_t of the table differs from the handle's"),
+    'boundary: null table, T < 0': (-1, 'null pointer argument: t'),
+    'boundary: table of another N, T < 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'boundary: table of another N, T = 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'boundary: T < 0, null ctl': (-1, 'T < 0'),
+    'boundary: T = 0, null ctl': (0, None),
+    'boundary: null ctl, null states, null G': (-1, 'null pointer argument: ctl'),
+    'boundary: null states, null G': (-1, 'null pointer argument: states'),
+    'boundary: null history': (-1, 'null pointer argument: bnd'),
+    'boundary: null table, null history': (-1, 'null pointer argument: t'),
+    'boundary: null history, T < 0': (-1, 'null pointer argument: bnd'),
+    'boundary: null history, table of another N': (-1, 'null pointer argument: bnd'),
+    'keypoints: null table': (-1, "kr_simulate_batch_keypoints: null pointer argument: t (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: null ctl': (-1, 'null pointer argument: ctl'),
+    'keypoints: null states': (-1, 'null pointer argument: states'),
+    'keypoints: null G': (-1, 'null pointer argument: G'),
+    'keypoints: T < 0': (-1, 'T < 0'),
+    'keypoints: table of another N': (-1, "parameter table: N of the table differs from the handle's"),
+    'keypoints: table of another del_t': (-1, "parameter table: del_t of the table differs from the handle's"),
+    'keypoints: null table, T < 0': (-1, "kr_simulate_batch_keypoints: null pointer argument: t (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: table of another N, T < 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'keypoints: table of another N, T = 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'keypoints: T < 0, null ctl': (-1, 'T < 0'),
+    'keypoints: T = 0, null ctl': (0, None),
+    'keypoints: null ctl, null states, null G': (-1, 'null pointer argument: ctl'),
+    'keypoints: null states, null G': (-1, 'null pointer argument: states'),
+    'keypoints: null history': (-1, "kr_simulate_batch_keypoints: null pointer argument: bnd (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: null table, null history': (-1, "kr_simulate_batch_keypoints: null pointer argument: t (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: null history, T < 0': (-1, "kr_simulate_batch_keypoints: null pointer argument: bnd (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: null history, table of another N': (-1, "kr_simulate_batch_keypoints: null pointer argument: bnd (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: null kp': (-1, "kr_simulate_batch_keypoints: null pointer argument: kp (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: misaligned kp': (-1, 'kr_simulate_batch_keypoints: kp must be 16-byte aligned'),
+    'keypoints: point out of range': (-1, 'kr_simulate_batch_keypoints: idx[2] = 10 lies outside [0, N) = [0, 10)'),
+    'keypoints: points not increasing': (-1, 'kr_simulate_batch_keypoints: idx[2] = 5 does not exceed idx[1] = 7 (the key points must be strictly increasing)'),
+    'keypoints: no points': (-1, 'kr_simulate_batch_keypoints: K = 0, a call takes 1 <= K <= 16 key points'),
+    'keypoints: null kp, point out of range': (-1, "kr_simulate_batch_keypoints: null pointer argument: kp (a caller with a fixed boundary repeats the row's values)"),
+    'keypoints: misaligned kp, point out of range': (-1, 'kr_simulate_batch_keypoints: idx[2] = 10 lies outside [0, N) = [0, 10)'),
+    'keypoints: point out of range, T < 0': (-1, 'kr_simulate_batch_keypoints: idx[2] = 10 lies outside [0, N) = [0, 10)'),
+    'keypoints: misaligned kp, table of another N': (-1, 'kr_simulate_batch_keypoints: kp must be 16-byte aligned'),
+    'keypoints: misaligned kp, T < 0': (-1, 'kr_simulate_batch_keypoints: kp must be 16-byte aligned'),
+    "keypoints: point of the other table's range, table of another N": (-1, "parameter table: N of the table differs from the handle's"),
+    'bank: null table': (-1, 'null pointer argument: t'),
+    'bank: null ctl': (-1, 'null pointer argument: ctl'),
+    'bank: null states': (-1, 'null pointer argument: states'),
+    'bank: null G': (-1, 'null pointer argument: G'),
+    'bank: T < 0': (-1, 'T < 0'),
+    'bank: table of another N': (-1, "parameter table: N of the table differs from the handle's"),
+    'bank: table of another del_t': (-1, "parameter table: del_t of the table differs from the handle's"),
+    'bank: null table, T < 0': (-1, 'null pointer argument: t'),
+    'bank: table of another N, T < 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'bank: table of another N, T = 0': (-1, "parameter table: N of the table differs from the handle's"),
+    'bank: T < 0, null ctl': (-1, 'T < 0'),
+    'bank: T = 0, null ctl': (0, None),
+    'bank: null ctl, null states, null G': (-1, 'null pointer argument: ctl'),
+    'bank: null states, null G': (-1, 'null pointer argument: states'),
+    'bank: null bank': (-1, 'null pointer argument: bank'),
+    'bank: null index array': (-1, 'null pointer argument: net_of_rod_host'),
+    'bank: index out of range': (-1, 'network bank: rod 2 asks for network 2, the bank holds 2'),
+    'bank: negative index': (-1, 'network bank: rod 1 asks for network -1, the bank holds 2'),
+    'bank: null table, null bank': (-1, 'null pointer argument: t'),
+    'bank: index out of range, T < 0': (-1, 'network bank: rod 2 asks for network 2, the bank holds 2'),
+    'bank: index out of range, T = 0': (-1, 'network bank: rod 2 asks for network 2, the bank holds 2'),
+    'bank: table of another N, index out of range': (-1, "parameter table: N of the table differs from the handle's"),
+    'bank: index out of range, null ctl': (-1, 'network bank: rod 2 asks for network 2, the bank holds 2'),
+}
+
+
+def test_argument_errors_of_the_c_entry_points(torch_cuda):
+    got = arg_error_pairs(torch_cuda)
+    assert list(got) == [c[0] for c in arg_error_cases()] and len(got) == len(ARG_ERROR_PAIRS)
+    for label, pair in got.items():
+        print(label, pair)
+    wrong = {k: (v, ARG_ERROR_PAIRS[k]) for k, v in got.items() if v != ARG_ERROR_PAIRS[k]}
+    assert not wrong, wrong

@@ -3,7 +3,10 @@ against a launch plumbing that records, and every line it prints - the template 
 bytes of each launch, rc / last_sim_path / last_overlap / last_waves_per_rod, the pointers the launch code fills in -
 must equal the line the parent of the planner gave for the same case (tests/golden/selection_parent.txt.gz: the probe's
 own lines; as text they are 3 MB, so they are kept compressed, the KR_MSWO_GT sections as the lines that differ from the
-default run).  The predictor image a simulate call hands to its kernels is checked against the parent's rule, restated here."""
+default run).  The predictor image a simulate call hands to its kernels is checked against the parent's rule, restated here.
+The five table-family sources (table, bank, loads, boundary, key points) have lines of their own, "src ...", which also
+print the source struct every launch received; tests/golden/selection_parent_sources.txt.gz holds those of the commit
+whose five launchers the one launch body replaced."""
 import gzip
 import os
 import shutil
@@ -13,6 +16,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "selection_parent.txt.gz")
+GOLDEN_SOURCES = os.path.join(ROOT, "tests", "golden", "selection_parent_sources.txt.gz")
 RUNS = {"default": None, "KR_MSWO_GT=1": "1", "KR_MSWO_GT=0": "0"}
 
 # the matrix of select_probe.hip (run_matrix), counted independently
@@ -23,6 +27,8 @@ PREV = N_DTYPE * 2 * 2
 TABLE_BANK = N_DTYPE * 5 * 2 * N_SCHEME * 11 * (6 + 3)      # N x B {8, 2048} x 11 option values x (6 table networks + 3 bank shapes)
 PREPARE = N_DTYPE * 2
 N_CASES = FULL + OPTIONS + N_DTYPE + PREV + TABLE_BANK + PREPARE  # (N_DTYPE: B = 2048 with overlap = 0)
+# ... and of its "src" lines (run_src_matrix): the table / bank matrix for {table, loads, boundary, key points} and the bank
+N_SRC_CASES = N_DTYPE * 5 * 2 * N_SCHEME * 11 * (4 * 6 + 3)
 
 # rows recorded from the parent (fp64 unless said; Euler, diagonal matrices, default options unless said)
 PARENT_ROWS = [
@@ -67,6 +73,7 @@ def _golden(path):
                 cur.append(line)
     base = runs["default"]
     index = {l.split(" | ")[0]: i for i, l in enumerate(base)}
+    assert len(index) == len(base), path
     for k in list(runs):
         if k != "default":  # (a section of differences)
             full = list(base)
@@ -91,9 +98,10 @@ def probe_lines(tmp_path_factory):
             env["KR_MSWO_GT"] = gt
         r = subprocess.run([str(out)], capture_output=True, text=True, env=env)
         assert r.returncode == 0, (name, r.returncode, r.stderr[-2000:])
-        lines[name] = [l for l in r.stdout.splitlines() if not l.startswith(("#", "pred "))]
+        lines[name] = [l for l in r.stdout.splitlines() if not l.startswith(("#", "pred ", "src "))]
         if gt is None:
             lines["pred"] = [l for l in r.stdout.splitlines() if l.startswith("pred ")]
+            lines["src"] = [l for l in r.stdout.splitlines() if l.startswith("src ")]
     return lines
 
 
@@ -121,6 +129,28 @@ def test_selection_equals_parent(probe_lines, run):
     bad = [(w, g) for w, g in zip(want, got) if w != g]
     assert not bad, "%d of %d lines differ; first:\nparent: %s\nnow:    %s" % (len(bad), N_CASES, bad[0][0], bad[0][1])
     assert not any("ARGS{" in l for l in got)  # a scalar member of SimArgs / StepArgs that did not arrive as passed
+
+
+def test_sources_equal_parent(probe_lines):
+    """Every table-family source through launch_sim: the selection and, per launch, the source struct the kernel received
+    (table rows and N; the loads or boundary history; kp, K and both mask words; the bank's index array and stride, each
+    a sentinel of its own) equal what the parent's five launchers gave."""
+    want = _golden(GOLDEN_SOURCES)["default"]
+    got = probe_lines["src"]
+    assert len(want) == len(got) == N_SRC_CASES, (len(want), len(got), N_SRC_CASES)
+    assert len({l.split(" | ")[0] for l in got}) == N_SRC_CASES  # every combination is one line
+    bad = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not bad, "%d of %d lines differ; first:\nparent: %s\nnow:    %s" % (len(bad), N_SRC_CASES, bad[0][0], bad[0][1])
+    assert not any("ARGS{" in l for l in got)
+    # every kind launches all three of its kernels somewhere, and every sentinel is seen where it belongs
+    for kind, field in (("tab", "src{rows=0x12000 N=100}"), ("loads", "N=100 loads=0x20000}"), ("bnd", "N=100 bnd=0x30000}"),
+                        ("kp", "N=100 bnd=0x30000 kp=0x50000 K=3 lo=100000005 hi=8000000000000002}")):
+        mine = [l for l in got if l.startswith("src f64,100,") and l.split(" | ")[0].split(",")[6] == kind]
+        launched = " ".join(l.split(" | ")[2] for l in mine if l.split(" | ")[1].startswith("0 "))
+        assert "mso_sim_kernel<double,true,18,1,RodTable" in launched and ",false,1,RodTable" in launched and ",true,1,RodTable" in launched, kind
+        assert all(field in part for l in mine if l.split(" | ")[1].startswith("0 ") for part in l.split(" | ")[2].split("; ")), kind
+    bank = [l for l in got if l.startswith("src f32,9,8,E,d1,n1,bank | 0 ")]
+    assert bank and "src{rows=0x11000 N=9 idx=0x60000 stride=256 layers=3}" in bank[0]
 
 
 def test_forced_tile_placement_changes_the_plan(probe_lines):

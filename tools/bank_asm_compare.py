@@ -27,30 +27,7 @@ def normalise(name):
 
 
 def main():
-    parent, branch = tac.load_dir(sys.argv[1]), tac.load_dir(sys.argv[2])
-    dm = tac.demangle(sorted(set(parent) | set(branch)))
-    bn = {normalise(dm[name]): name for name in branch}
-    print(f"part 1: {len(parent)} kernels of the parent build against this build ({len(branch)} kernels)")
-    bad = 0
-    for name in sorted(parent, key=lambda n: (parent[n]["unit"], dm[n])):
-        key = normalise(dm[name])
-        if key not in bn:
-            print(f"MISSING  {parent[name]['unit']}: {dm[name]}"); bad += 1; continue
-        a, b = parent[name], branch[bn[key]]
-        diffs = [f"{k} {a['meta'][k]} -> {b['meta'][k]}" for k in tac.KEYS if a["meta"][k] != b["meta"][k]]
-        if a["loops"] != b["loops"]: diffs.append(f"loop census differs ({len(a['loops'])} / {len(b['loops'])} loops)")
-        if a["body"] != b["body"] and not diffs: diffs.append("instruction text differs (same resources and census)")
-        renamed = " [name normalised]" if bn[key] != name else ""
-        if diffs:
-            bad += 1
-            print(f"DIFFERS  {a['unit']}: {dm[name]}{renamed}: " + "; ".join(diffs))
-        else:
-            m = a["meta"]
-            print(f"same     {a['unit']}: {dm[name]}{renamed}: vgpr {m['.vgpr_count']} sgpr {m['.sgpr_count']} private "
-                  f"{m['.private_segment_fixed_size']} lds {m['.group_segment_fixed_size']} loops {len(a['loops'])} "
-                  f"instructions {len(a['body'])} (text identical)")
-    print(f"part 1: {bad} of {len(parent)} kernels differ")
-    print()
+    bad, branch, dm, bn = tac.part1(sys.argv, normalise)
     print("part 2: bank kernels (kr::MlpBank<T>) next to their one-network table twins in this build")
     smem = lambda k: sum(dict(l[1]).get("smem", 0) for l in k["loops"])
     n_bank = 0

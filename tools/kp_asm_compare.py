@@ -24,20 +24,7 @@ import tab_asm_compare as tac  # noqa: E402
 
 
 def main():
-    parent, branch = tac.load_dir(sys.argv[1]), tac.load_dir(sys.argv[2])
-    dm = tac.demangle(sorted(set(parent) | set(branch)))
-    bn = {tac.normalise(dm[name]): name for name in branch}
-    bad = 0
-    for name in sorted(parent, key=lambda n: (parent[n]["unit"], dm[n])):
-        key = tac.normalise(dm[name])
-        if key not in bn:
-            print(f"MISSING  {parent[name]['unit']}: {dm[name]}"); bad += 1; continue
-        a, b = parent[name], branch[bn[key]]
-        if a["meta"] != b["meta"] or a["loops"] != b["loops"] or a["body"] != b["body"]:
-            print(f"DIFFERS  {a['unit']}: {dm[name]}"); bad += 1
-    print(f"part 1: {bad} of {len(parent)} kernels of the parent build differ in this build ({len(branch)} kernels): resources, "
-          "loop census, instruction text")
-    print()
+    bad, branch, dm, bn = tac.part1(sys.argv, each=False)
     print("part 2: key-point kernels (kr::RodTableBndKp<T>) next to their boundary twins in this build")
     cnt = lambda l, k: dict(l[1]).get(k, 0)
     n_bnd = 0

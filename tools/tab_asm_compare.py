@@ -121,32 +121,47 @@ def fmt_loop(lp):
     return f"instr {n:5d} vector {vec:5d} inner {inner}  " + " ".join(f"{k}={v}" for k, v in c)
 
 
-def main():
-    parent, branch = load_dir(sys.argv[1]), load_dir(sys.argv[2])
+def part1(argv, norm=None, each=True, new_ok=True):
+    """Part 1 of every *_asm_compare tool, and all of asm_unchanged.py: every kernel of the parent build (argv[1]) against the
+    kernel of the same name, normalised by `norm`, in this build (argv[2]).  Prints a line per kernel (`each`) or per
+    difference, then the verdict; a kernel the parent does not have counts only where `new_ok` is False.
+    Returns (differences, kernels of this build, their demangled names, {normalised name: mangled name})."""
+    norm = norm or normalise
+    parent, branch = load_dir(argv[1]), load_dir(argv[2])
     dm = demangle(sorted(set(parent) | set(branch)))
-    bn = {}
-    for name in branch: bn[normalise(dm[name])] = name
-    print(f"part 1: {len(parent)} kernels of the parent build against this build ({len(branch)} kernels)")
+    bn = {norm(dm[name]): name for name in branch}
+    if each: print(f"part 1: {len(parent)} kernels of the parent build against this build ({len(branch)} kernels)")
     bad = 0
     for name in sorted(parent, key=lambda n: (parent[n]["unit"], dm[n])):
-        key = normalise(dm[name])
+        key = norm(dm[name])
         if key not in bn:
             print(f"MISSING  {parent[name]['unit']}: {dm[name]}"); bad += 1; continue
         a, b = parent[name], branch[bn[key]]
         diffs = [f"{k} {a['meta'][k]} -> {b['meta'][k]}" for k in KEYS if a["meta"][k] != b["meta"][k]]
         if a["loops"] != b["loops"]: diffs.append(f"loop census differs ({len(a['loops'])} / {len(b['loops'])} loops)")
-        same_body = a["body"] == b["body"]
-        if not same_body and not diffs: diffs.append("instruction text differs (same resources and census)")
+        if a["body"] != b["body"] and not diffs: diffs.append("instruction text differs (same resources and census)")
         renamed = " [name normalised]" if bn[key] != name else ""
         if diffs:
             bad += 1
             print(f"DIFFERS  {a['unit']}: {dm[name]}{renamed}: " + "; ".join(diffs))
-        else:
+        elif each:
             m = a["meta"]
             print(f"same     {a['unit']}: {dm[name]}{renamed}: vgpr {m['.vgpr_count']} sgpr {m['.sgpr_count']} private {m['.private_segment_fixed_size']} "
                   f"lds {m['.group_segment_fixed_size']} loops {len(a['loops'])} instructions {len(a['body'])} (text identical)")
-    print(f"part 1: {bad} of {len(parent)} kernels differ")
+    if not new_ok:
+        have = {norm(dm[name]) for name in parent}
+        for key in sorted(set(bn) - have):
+            print(f"NEW      {branch[bn[key]]['unit']}: {dm[bn[key]]}"); bad += 1
+    if each: print(f"part 1: {bad} of {len(parent)} kernels differ")
+    else:
+        print(f"part 1: {bad} of {len(parent)} kernels of the parent build differ in this build ({len(branch)} kernels): resources, "
+              "loop census, instruction text")
     print()
+    return bad, branch, dm, bn
+
+
+def main():
+    bad, branch, dm, bn = part1(sys.argv)
     print("part 2: table kernels (kr::RodTable<T>) next to their plain twins in this build")
     for name in sorted(branch, key=lambda n: dm[n]):
         d = dm[name]
