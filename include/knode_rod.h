@@ -404,12 +404,22 @@ int kr_mlp_bank_check(const kr_params* base, int K, int n_layers, const int32_t*
  * K packed images lie a constant stride apart in one allocation.
  * Source lifetime: the bank has finished reading W and b - host or device - when this call returns (it synchronises
  * `stream`); the caller may free or overwrite them at once.
- * The bank belongs to the handle's device and is immutable; it may be used with any handle on that device.  Destroy it
- * after the last call that uses it has finished on its stream. */
+ * The bank belongs to the handle's device and is changed only by kr_mlp_bank_repack, ordered on its stream; it may be
+ * used with any handle on that device.  Destroy it after the last call that uses it has finished on its stream. */
 int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, const int32_t* acts,
                        const float* const* W, const float* const* b, int src_on_device, void* stream,
                        kr_mlp_bank** out);
 int kr_mlp_bank_destroy(kr_mlp_bank* bank);
+/* In-place refresh: packs K = the bank's K networks of the bank's shape into the existing bank (W, b as for
+ * kr_mlp_bank_create: K * n_layers pointers, network-major), with the gather plan and the kernel creation used - the
+ * result is bit-identical to a fresh kr_mlp_bank_create from the same weights.  Allocates nothing.  With
+ * src_on_device = 1 it does not synchronise: the pack launches are ordered on `stream` like any other call, a simulate
+ * call queued behind it on the handle sees the new weights, one queued before it the old ones, and the sources must
+ * stay unchanged until the launches have run.  With host sources the call returns when they have been read.
+ * This is how live weights of a training reach a closed-loop evaluation (physics_train.py:136-167: evaluate() every
+ * 50 epochs) without a host copy.  KR_E_ARG: a NULL among the K * n_layers pointers (named), a bank of another device. */
+int kr_mlp_bank_repack(kr_handle* h, kr_mlp_bank* bank, const float* const* W, const float* const* b, int src_on_device,
+                       void* stream);
 /* kr_simulate_batch_table with the MLP on (there is no use_nn), rod b evaluating network net_of_rod_host[b].
  * net_of_rod_host: HOST array of B = the table's B entries.  Every entry is range-checked on the host BEFORE anything
  * is copied or launched (KR_E_ARG naming the first bad rod; no output buffer is touched), then the array is copied to
@@ -419,6 +429,25 @@ int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_b
                            const int32_t* net_of_rod_host, int64_t T, int scheme, const void* ctl, void* states,
                            int ring, void* G, void* tip, double tol, int maxit, int32_t* status,
                            const void* state_prev_init, int dtype, void* stream);
+/* The evaluation half of the reference's experiment rolls every trained network out and scores it at key points
+ * against a recorded run (physics_multitrain.py:180-233), and does the same during training to pick the best weights
+ * (physics_train.py:136-167).  kr_simulate_batch_bank_keypoints is kr_simulate_batch_bank in which rod b also solves
+ * step t with bnd[b][t] - the KR_BND values, meaning exactly what they mean for kr_simulate_batch_boundary (below) -
+ * and which writes kp[T][B][K][KR_SLOTS] exactly as kr_simulate_batch_keypoints (below) does: a grid of trained
+ * networks scored from K records per step instead of the full history, under a tip disturbance or on a moving base.
+ * K may be 0 HERE, with idx_host and kp both NULL: the bank form of the boundary call (kr_keypoints_check itself keeps
+ * refusing K = 0).  For K >= 1 the rule for idx_host is kr_keypoints_check's and kp must be 16-byte aligned.
+ * t, bank, net_of_rod_host and bnd are required.  Every argument check - NULLs, the network index range, the idx rule,
+ * a table that does not match the handle - and every refusal of the planner is made on the host BEFORE anything is
+ * copied or launched: KR_E_ARG naming the first bad entry, or KR_E_UNSUPPORTED naming the rule; no output buffer is
+ * touched.  ring, state_prev_init, keep_predictor, a call cut into pieces (bnd sliced like ctl, kp like tip), failed
+ * steps and last_sim_path / last_waves_per_rod / last_overlap = 2 / 1 / 0 are as for the two parents.
+ * Served and refused: exactly as kr_simulate_batch_bank, with messages that name this call. */
+int kr_simulate_batch_bank_keypoints(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank,
+                                     const int32_t* net_of_rod_host, int64_t T, int scheme, const void* ctl,
+                                     const void* bnd, int K, const int32_t* idx_host, void* kp, void* states, int ring,
+                                     void* G, void* tip, double tol, int maxit, int32_t* status,
+                                     const void* state_prev_init, int dtype, void* stream);
 
 /* ---- per-step tip loads: a wrench history per rod ---------------------- */
 /* Every simulate call above freezes the tip wrench for the whole call (the handle's F_tip / M_tip, or the rod's table
@@ -440,7 +469,7 @@ int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_b
  * ring, state_prev_init and the options keep_predictor, residual_test, predictor, nn_* as there.  Afterwards
  * last_sim_path = 2, last_waves_per_rod = 1, last_overlap as for the table call.  Everything the table call refuses is
  * refused here with KR_E_UNSUPPORTED and a message that names the rule; no output buffer is touched.
- * NOT served with loads: a network bank, several wavefronts per rod, N > 128, RK4, one launch per step, kr_step_batch
+ * NOT served with loads: a network bank (kr_simulate_batch_bank_keypoints takes the wrench in bnd), several wavefronts per rod, N > 128, RK4, one launch per step, kr_step_batch
  * (per-step launches take their wrench from kr_set_params).  A distributed load along the rod is outside this call
  * (a moving base: kr_simulate_batch_boundary below).  The first call of a shape does the one-time host work kr_simulate_prepare does for
  * kr_simulate_batch itself. */
@@ -494,7 +523,8 @@ int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T,
  * sweep that replaces it overwrites them, like the tip: nothing of a rejected sweep stays in kp.
  * Served and refused: exactly as kr_simulate_batch_boundary, with messages that name this call; no output buffer of a
  * refused call is touched.  Afterwards last_sim_path = 2, last_waves_per_rod = 1, last_overlap as for the table call.
- * NO key-point form: a network bank, several wavefronts per rod, N > 128, RK4, one launch per step.
+ * A network bank: served by kr_simulate_batch_bank_keypoints (above).  NO key-point form: several wavefronts per rod,
+ * N > 128, RK4, one launch per step.
  * Failed steps: see FAILED STEPS at kr_simulate_batch. */
 #define KR_KEYPOINTS_MAX 16
 int kr_keypoints_check(int N, int K, const int32_t* idx_host);

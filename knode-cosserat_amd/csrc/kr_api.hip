@@ -237,7 +237,7 @@ static int step_impl(kr_handle* h, int scheme, int use_nn, const StepArgs<T>& a,
   return KR_OK;
 }
 
-// What the six simulate entry points take alike (knode_rod.h: kr_simulate_batch)
+// What the seven simulate entry points take alike (knode_rod.h: kr_simulate_batch)
 struct SimCall {
   int64_t T_steps;
   int scheme;
@@ -1235,34 +1235,22 @@ int kr_mlp_bank_check(const kr_params* base, int K, int n_layers, const int32_t*
 
 int kr_mlp_bank_destroy(kr_mlp_bank* bk) {
   if (!bk) return KR_OK;
-  if (bk->arena) (void)hipFree(bk->arena);
+  if (kr_mlp_plan* P = bk->plan) {  // (owns the arena, the index table and the staging area)
+    if (P->idx) (void)hipFree(P->idx);
+    if (P->staging) (void)hipFree(P->staging);
+    if (P->arena) (void)hipFree(P->arena);
+    delete P;
+  }
   delete bk;
   return KR_OK;
 }
 
-int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* W,
-                       const float* const* b, int src_on_device, void* stream, kr_mlp_bank** out) {
-  KR_CHECK_H(h);
-  KR_CHECK_PTR(out);
-  *out = nullptr;
-  KR_CHECK_PTR(dims); KR_CHECK_PTR(acts); KR_CHECK_PTR(W); KR_CHECK_PTR(b);
-  if (int rc = bank_check_shape(h->params.nn_input_history, h->params.N, K, n_layers, dims, acts)) return rc;
-  for (int i = 0; i < K * n_layers; ++i) { KR_CHECK_PTR(W[i]); KR_CHECK_PTR(b[i]); }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc_order_ = order_stream(h, s)) return rc_order_;
-  // the gather plan of kr_set_mlp for this shape, its arena K images long
-  kr_mlp_plan P;
-  auto drop = [&P]() {
-    if (P.idx) (void)hipFree(P.idx);
-    if (P.staging) (void)hipFree(P.staging);
-    if (P.arena) (void)hipFree(P.arena);
-  };
-  if (int rc = build_mlp_plan(h, n_layers, dims, acts, P, (size_t)K)) { drop(); return rc; }
-  if (!P.mf.mfma_ok || !P.mf.jvp_ok) {  // (bank_check_shape restates these rules; the plan has the last word)
-    drop();
-    set_error("network bank: a shape the persistent one-wavefront kernel does not evaluate");
-    return KR_E_UNSUPPORTED;
-  }
+// Packs K networks into the K images of a plan's arena: kr_mlp_bank_create and kr_mlp_bank_repack, hence bit-identical.
+// Device sources: K launches on `s`, nothing else.  Host sources go through the plan's one staging area: network k + 1 is
+// copied in only after the pack launch of network k has finished.
+static hipError_t bank_pack(const kr_mlp_plan& P, int K, const float* const* W, const float* const* b, int src_on_device, hipStream_t s) {
+  const int n_layers = P.mf.n_layers;
+  const int* dims = P.mf.dims;
   const uint32_t total = P.jobs.start[P.jobs.n];
   int grid = (int)((total + 255) / 256);
   if (grid > 1024) grid = 1024;
@@ -1276,7 +1264,7 @@ int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, c
       if (src_on_device) {
         J.src[2 * l] = Wl;
         J.src[2 * l + 1] = bl;
-      } else {  // (one staging area: network k + 1 is copied in only after the pack launch of network k has finished, below)
+      } else {
         e = hipMemcpyAsync(P.staging + P.src_off[2 * l], Wl, sizeof(float) * dims[l] * dims[l + 1], hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(P.staging + P.src_off[2 * l + 1], bl, sizeof(float) * dims[l + 1], hipMemcpyHostToDevice, s);
         J.src[2 * l] = P.staging + P.src_off[2 * l];
@@ -1288,7 +1276,35 @@ int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, c
     e = hipGetLastError();
     if (e == hipSuccess && !src_on_device) e = hipStreamSynchronize(s);
   }
-  // the bank has read its sources, host or device, when this returns; the plan's index table and staging go with it
+  return e;
+}
+
+int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* W,
+                       const float* const* b, int src_on_device, void* stream, kr_mlp_bank** out) {
+  KR_CHECK_H(h);
+  KR_CHECK_PTR(out);
+  *out = nullptr;
+  KR_CHECK_PTR(dims); KR_CHECK_PTR(acts); KR_CHECK_PTR(W); KR_CHECK_PTR(b);
+  if (int rc = bank_check_shape(h->params.nn_input_history, h->params.N, K, n_layers, dims, acts)) return rc;
+  for (int i = 0; i < K * n_layers; ++i) { KR_CHECK_PTR(W[i]); KR_CHECK_PTR(b[i]); }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc_order_ = order_stream(h, s)) return rc_order_;
+  // the gather plan of kr_set_mlp for this shape, its arena K images long; the bank keeps it (kr_mlp_bank_repack)
+  kr_mlp_plan* const P = new kr_mlp_plan;
+  auto drop = [P]() {
+    if (P->idx) (void)hipFree(P->idx);
+    if (P->staging) (void)hipFree(P->staging);
+    if (P->arena) (void)hipFree(P->arena);
+    delete P;
+  };
+  if (int rc = build_mlp_plan(h, n_layers, dims, acts, *P, (size_t)K)) { drop(); return rc; }
+  if (!P->mf.mfma_ok || !P->mf.jvp_ok) {  // (bank_check_shape restates these rules; the plan has the last word)
+    drop();
+    set_error("network bank: a shape the persistent one-wavefront kernel does not evaluate");
+    return KR_E_UNSUPPORTED;
+  }
+  hipError_t e = bank_pack(*P, K, W, b, src_on_device, s);
+  // the bank has read its sources, host or device, when this returns
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     drop();
@@ -1297,14 +1313,31 @@ int kr_mlp_bank_create(kr_handle* h, int K, int n_layers, const int32_t* dims, c
   kr_mlp_bank* bk = new kr_mlp_bank();
   bk->device = h->device;
   bk->K = K;
-  bk->mf = P.mf;
-  bk->md = P.md;
-  bk->stride = P.arena_bytes;
-  bk->arena = P.arena;
-  P.arena = nullptr;
-  drop();
+  bk->mf = P->mf;
+  bk->md = P->md;
+  bk->stride = P->arena_bytes;
+  bk->arena = P->arena;
+  bk->plan = P;
   *out = bk;
   return KR_OK;
+}
+
+// K networks of the bank's shape into the existing bank: the plan and kernel of kr_mlp_bank_create, no allocation, and
+// with device sources no synchronisation - the launches are ordered on `stream` like any other call's
+int kr_mlp_bank_repack(kr_handle* h, kr_mlp_bank* bank, const float* const* W, const float* const* b, int src_on_device, void* stream) {
+  KR_CHECK_H(h);
+  KR_CHECK_PTR(bank); KR_CHECK_PTR(W); KR_CHECK_PTR(b);
+  if (bank->device != h->device) { set_error("kr_mlp_bank_repack: device of the bank differs from the handle's"); return KR_E_ARG; }
+  for (int i = 0; i < bank->K * bank->mf.n_layers; ++i)
+    if (!W[i] || !b[i]) {
+      set_error("kr_mlp_bank_repack: null pointer argument: " + std::string(!W[i] ? "W[" : "b[") + std::to_string(i) + "] (the bank holds " +
+                std::to_string(bank->K) + " networks of " + std::to_string(bank->mf.n_layers) + " layers)");
+      return KR_E_ARG;
+    }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc_order_ = order_stream(h, s)) return rc_order_;
+  const hipError_t e = bank_pack(*bank->plan, bank->K, W, b, src_on_device, s);
+  return e == hipSuccess ? KR_OK : hip_fail(e, "kr_mlp_bank_repack");
 }
 
 static int ensure_net_idx(kr_handle* h, int64_t B) {
@@ -1319,6 +1352,58 @@ static int ensure_net_idx(kr_handle* h, int64_t B) {
   KR_HIP(hipMalloc(&h->net_idx_buf, bytes + bytes / 4));
   h->net_idx_cap = bytes + bytes / 4;
   return KR_OK;
+}
+
+// kr_simulate_batch_bank with bnd[b][t] for rod b's step t and the key-point records of kr_simulate_batch_keypoints
+// (K = 0: neither idx nor kp; the bank form of kr_simulate_batch_boundary).  Every check before anything is copied.
+int kr_simulate_batch_bank_keypoints(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank, const int32_t* net_of_rod_host,
+                                     int64_t T, int scheme, const void* ctl, const void* bnd, int K, const int32_t* idx_host, void* kp,
+                                     void* states, int ring, void* G, void* tip, double tol, int maxit, int32_t* status,
+                                     const void* state_prev_init, int dtype, void* stream) {
+  static const char* const NAME = "kr_simulate_batch_bank_keypoints";
+  const std::string who = std::string(NAME) + ": ";
+  KR_CHECK_H(h);
+  KR_CHECK_DTYPE(dtype);
+  if (!t || !bank || !net_of_rod_host || !bnd) {
+    set_error(who + "null pointer argument: " + (!t ? "t" : !bank ? "bank" : !net_of_rod_host ? "net_of_rod_host" : "bnd") +
+              " (a caller with a fixed boundary repeats the row's values)");
+    return KR_E_ARG;
+  }
+  if (int rc = tab_matches(h, t)) return rc;
+  if (bank->device != h->device) { set_error(who + "device of the bank differs from the handle's"); return KR_E_ARG; }
+  for (int64_t b = 0; b < t->B; ++b)
+    if (net_of_rod_host[b] < 0 || net_of_rod_host[b] >= bank->K) {
+      set_error(who + "rod " + std::to_string(b) + " asks for network " + std::to_string(net_of_rod_host[b]) + ", the bank holds " +
+                std::to_string(bank->K));
+      return KR_E_ARG;
+    }
+  SimSrc src = make_src(KR_SRC_BANK_KEYPOINTS, t, bnd);
+  if (K == 0) {
+    if (idx_host || kp) { set_error(who + "K = 0 takes neither idx nor kp (pass NULL for both)"); return KR_E_ARG; }
+  } else {
+    if (int rc = keypoints_mask(NAME, t->N, K, idx_host, src.kp.mask_lo, src.kp.mask_hi)) return rc;
+    if (!kp) { set_error(who + "null pointer argument: kp"); return KR_E_ARG; }
+    if ((uintptr_t)kp & 15) { set_error(who + "kp must be 16-byte aligned"); return KR_E_ARG; }
+    src.kp.kp = kp;
+    src.kp.K = K;
+  }
+  if (T < 0) { set_error(who + "T < 0"); return KR_E_ARG; }
+  if (T == 0 || t->B == 0) return KR_OK;
+  KR_CHECK_PTR(ctl); KR_CHECK_PTR(states); KR_CHECK_PTR(G);
+  // what the planner refuses is refused before the index array is copied
+  src.bank = bank;
+  {
+    const PlanQuery q = plan_query(src, t->B, T, scheme, 1);
+    const SimPlan plan = dtype == KR_F32 ? plan_simulate<float>(h, q) : plan_simulate<double>(h, q);
+    if (plan.rc) return refuse_plan(plan);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc_order_ = order_stream(h, s)) return rc_order_;
+  if (int rc = ensure_net_idx(h, t->B)) return rc;
+  KR_HIP(hipMemcpyAsync(h->net_idx_buf, net_of_rod_host, sizeof(int32_t) * (size_t)t->B, hipMemcpyHostToDevice, s));
+  KR_HIP(hipStreamSynchronize(s));
+  src.net_idx = static_cast<const int32_t*>(h->net_idx_buf);
+  return simulate_dispatch(h, src, t->B, SimCall{T, scheme, ctl, states, ring, G, tip, tol, maxit, status, 1, state_prev_init, dtype, stream}, s);
 }
 
 int kr_simulate_batch_bank(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank, const int32_t* net_of_rod_host,

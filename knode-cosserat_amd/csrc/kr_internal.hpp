@@ -132,14 +132,16 @@ struct kr_param_table {
 
 // Bank of K networks of one shape (kr_mlp_bank_create): every network packed like the handle's own (the gather plan
 // and mlp_pack_kernel of kr_set_mlp), the K packed images `stride` bytes apart in one arena - network k's buffers are
-// those of network 0 (mf / md) moved by k * stride.  Immutable after creation.
+// those of network 0 (mf / md) moved by k * stride.  Changed only by kr_mlp_bank_repack, ordered on its stream; shape,
+// K, stride and every address stay what creation made them.
 struct kr_mlp_bank {
   int device = 0;
   int K = 0;
   kr::MlpDev<float> mf{};    // descriptor of network 0
   kr::MlpDev<double> md{};
   size_t stride = 0;         // bytes, a multiple of 256
-  unsigned char* arena = nullptr;  // [K][stride], device
+  unsigned char* arena = nullptr;  // [K][stride], device (owned by `plan`)
+  struct kr_mlp_plan* plan = nullptr;  // the gather plan creation packed with, kept for kr_mlp_bank_repack (kr_api.hip)
 };
 
 namespace kr {
@@ -278,7 +280,9 @@ enum SimFamily {
 };
 // Where a rod's constants, its per-step data and its network come from: one kind per simulate entry point.  Every kind
 // but the first is a table call (SimSrc::table) served by the one-wavefront persistent kernels only (plan_table).
-enum SimKind { KR_SRC_HANDLE, KR_SRC_TABLE, KR_SRC_LOADS, KR_SRC_BOUNDARY, KR_SRC_KEYPOINTS, KR_SRC_BANK };
+enum SimKind { KR_SRC_HANDLE, KR_SRC_TABLE, KR_SRC_LOADS, KR_SRC_BOUNDARY, KR_SRC_KEYPOINTS, KR_SRC_BANK, KR_SRC_BANK_KEYPOINTS };
+// (the kinds whose network comes from a bank)
+constexpr bool sim_kind_banked(int kind) { return kind == KR_SRC_BANK || kind == KR_SRC_BANK_KEYPOINTS; }
 // ... and how a kind is spoken of: its entry point, the word for it in a refusal, and the end of the refusal sentence
 struct SimKindText {
   const char *api, *word, *tail;
@@ -290,9 +294,11 @@ constexpr SimKindText kSimKindText[] = {
     {"kr_simulate_batch_boundary", "boundary", "not served with per-step boundary data; nothing falls back to a frozen base or wrench"},
     {"kr_simulate_batch_keypoints", "key-point", "not served with key-point records; nothing falls back to a call without them"},
     {"kr_simulate_batch_bank", "bank", "not served with a network bank; nothing falls back to the handle's MLP"},
+    {"kr_simulate_batch_bank_keypoints", "bank key-point",
+     "not served with a network bank and per-step boundary data; nothing falls back to the handle's MLP or a frozen boundary"},
 };
-// kr_simulate_batch_keypoints: kp[T][B][K][KR_SLOTS] of the call's element type and the marked grid points, bit j of
-// (mask_lo, mask_hi) = grid point j
+// kr_simulate_batch_keypoints / _bank_keypoints: kp[T][B][K][KR_SLOTS] of the call's element type and the marked grid
+// points, bit j of (mask_lo, mask_hi) = grid point j (the bank form also with K = 0: no pointer, an empty mask)
 struct KpDst {
   void* kp = nullptr;
   int K = 0;
@@ -302,9 +308,9 @@ struct KpDst {
 struct SimSrc {
   int kind = KR_SRC_HANDLE;
   const kr_param_table* table = nullptr;  // every kind but KR_SRC_HANDLE
-  const void* hist = nullptr;             // KR_SRC_LOADS: loads[B][T][6]; KR_SRC_BOUNDARY / _KEYPOINTS: bnd[B][T][KR_BND]; element type of the call
-  KpDst kp;                               // KR_SRC_KEYPOINTS: where the key-point records go
-  const kr_mlp_bank* bank = nullptr;      // KR_SRC_BANK
+  const void* hist = nullptr;             // KR_SRC_LOADS: loads[B][T][6]; KR_SRC_BOUNDARY / _KEYPOINTS / _BANK_KEYPOINTS: bnd[B][T][KR_BND]; element type of the call
+  KpDst kp;                               // KR_SRC_KEYPOINTS / _BANK_KEYPOINTS: where the key-point records go
+  const kr_mlp_bank* bank = nullptr;      // KR_SRC_BANK / _BANK_KEYPOINTS
   const int32_t* net_idx = nullptr;       // ... and the device copy of the caller's index array
 };
 struct SimPlan {
@@ -410,6 +416,8 @@ template <typename T>
 int launch_kp_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_kp_*.hip
 template <typename T>
 int launch_bank_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bank_*.hip
+template <typename T>
+int launch_bankkp_sim(kr_handle* h, const SimSrc& src, const SimPlan& p, const SimArgs<T>& a, const LaunchAt& at);  // kr_bankkp_*.hip
 int ensure_resume(kr_handle* h, int64_t B);
 int ensure_hist_ws(kr_handle* h, size_t bytes);
 
@@ -430,6 +438,7 @@ inline int launch_sim(kr_handle* h, const SimPlan& p, const SimSrc& src, SimArgs
     case KR_SRC_BOUNDARY: return launch_bnd_sim<T>(h, src, p, a, at);
     case KR_SRC_KEYPOINTS: return launch_kp_sim<T>(h, src, p, a, at);
     case KR_SRC_BANK: return launch_bank_sim<T>(h, src, p, a, at);
+    case KR_SRC_BANK_KEYPOINTS: return launch_bankkp_sim<T>(h, src, p, a, at);
     default: break;  // (KR_SRC_HANDLE: by family)
   }
   switch (p.family) {

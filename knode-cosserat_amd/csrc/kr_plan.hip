@@ -142,12 +142,12 @@ SimPlan plan_one_wave(const kr_handle* h, SimPlan p, const PlanQuery& q, int N, 
   return p;
 }
 
-// kr_simulate_batch_table / _bank / _loads / _boundary / _keypoints (a table call whose tip wrench, or whose base state and tip
+// kr_simulate_batch_table / _bank / _bank_keypoints / _loads / _boundary / _keypoints (a table call whose tip wrench, or whose base state and tip
 // wrench, vary in time, the latter also with key-point records: the same plan, the loads, boundary or key-point instantiations of the same kernels): the one-wavefront persistent kernels only, and a refusal (never the handle's own
 // parameters or network) for everything they do not serve
 template <typename T>
 SimPlan plan_table(const kr_handle* h, const PlanQuery& q) {
-  const bool bank = q.source == KR_SRC_BANK;
+  const bool bank = sim_kind_banked(q.source);
   const SimKindText& text = kSimKindText[q.source];
   const char* const word = text.word;
   char what[128];

@@ -114,15 +114,19 @@ def _robots_rows(robot, robots, B):
     return rows
 
 
-def _robots_networks(robot, robots):
+def _robots_networks(robot, robots, zero_ok=False):
     """Networks of ``robots`` for ``simulate_batch(..., per_robot_nn=True)``: ``(networks, net_of_rod)`` with the
     distinct networks in order of first appearance (the digest of CosseratRod._push_mlp tells them apart).  Host-side
-    validation only (no device call)."""
+    validation only (no device call).  ``zero_ok`` (``simulate_bank``): a robot with ``nn_path is None`` takes a zero
+    network of the others' shape - the reference's network-free "baseline" rows in the same launch."""
     base = robot._params()
     keys, networks, net_of_rod = {}, [], []
     model0 = shape0 = None
     for b, r in enumerate(robots):
         model, param_ls = getattr(r, "nn_model", None), getattr(r, "param_ls", None)
+        if zero_ok and getattr(r, "nn_path", None) is None:
+            net_of_rod.append(None)
+            continue
         if getattr(r, "nn_path", None) is None or model is None or param_ls is None:
             raise kn.KrError(f"simulate_batch: rod {b}: per_robot_nn needs a network on every robot (nn_path / nn_model / "
                              "param_ls, as the reference leaves a robot after loading nn_path)")
@@ -150,6 +154,13 @@ def _robots_networks(robot, robots):
             keys[key] = len(networks)
             networks.append(net)
         net_of_rod.append(keys[key])
+    if shape0 is None:
+        raise kn.KrError("simulate_batch: no robot carries a network (nn_path is None on all of them): the shape of the zero "
+                         "network is that of the others")
+    if None in net_of_rod:  # W = 0, b = 0: the MLP's 25 outputs vanish and the rod is the physics alone
+        weights, biases, acts0 = networks[0]
+        networks.append(([np.zeros_like(w) for w in weights], [np.zeros_like(v) for v in biases], list(acts0)))
+        net_of_rod = [len(networks) - 1 if k is None else k for k in net_of_rod]
     dims, acts = shape0
     rc, msg = kn.mlp_bank_check(base, len(networks), dims, acts)
     if rc != 0:
@@ -331,21 +342,22 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     tip_loads: a tip wrench that varies in time, [B, T, 6] or [T, 6] (shared by all rods): rod b solves step t with
     F_tip, M_tip = tip_loads[b, t, :3], tip_loads[b, t, 3:] - the reference with ``robot.F_tip`` / ``robot.M_tip``
     assigned before that solve.  The values replace the robot's own wrench; with ``robots=`` row b keeps everything else.
-    Composes with ``score`` and ``tip_only``; not served with ``per_robot_nn``.
+    Composes with ``score`` and ``tip_only``; not served with ``per_robot_nn`` (``simulate_bank`` serves it).
 
     base_motion: a base that moves in time, [B, T, 13] or [T, 13] (shared by all rods), columns ``p0 (3) h0 (4) q0 (3)
     w0 (3)``: rod b solves step t with that base state - the reference with ``robot.p0 / h0 / q0 / w0`` assigned before
     that solve (a platform, a carriage, the wrist of an arm).  The values replace the robot's own; ``h0`` is not
     normalised; record 0 of state t + 1 holds them exactly.  The caller supplies consistent ``q0`` / ``w0``.  Composes
     with ``robots``, ``tip_loads`` (without it every rod keeps its own ``F_tip`` / ``M_tip``), ``score`` and ``tip_only``;
-    not served with ``per_robot_nn``.
+    not served with ``per_robot_nn`` (``simulate_bank`` serves it).
 
     key_points: a list of 1 .. 16 grid points (a negative index counts from the tip; sorted and de-duplicated here): the
     result gains ``kp`` float[B, T+1, 25, K], the states at those points in the reference's row order, entry 0 the initial
     state - ``traj[:, :, :, key_points]`` wherever both exist - and ``key_points`` int32[K], the order used.  With
     ``tip_only=True`` this is the way to the states at a few points of a long run of a large batch: the full history is
     never stored.  Composes with ``robots``, ``tip_loads``, ``base_motion`` (without them the boundary is each rod's own, on
-    every step) and ``tip_only``; not served with ``per_robot_nn``.  With ``key_points``, ``score`` is accepted with
+    every step) and ``tip_only``; not served with ``per_robot_nn`` (per-rod networks with ``key_points`` / ``base_motion`` /
+    ``tip_loads``: ``simulate_bank``).  With ``key_points``, ``score`` is accepted with
     ``tip_only=True``: ``dtw`` is the DTW of the path of ``score["point"]``, which must then be a key point, and
     ``mse_kp`` the pose MSE over the K key points against the reference at those points (``mse``, the all-points quantity,
     is there only when the full history is).
@@ -366,7 +378,8 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
                 ("tip_loads", tip_loads, "per-step tip loads have"))
     for name, value, what in per_step:
         if value is not None and per_robot_nn:
-            raise kn.KrError(f"simulate_batch: {name} with per_robot_nn=True is not served ({what} no network-bank form)")
+            raise kn.KrError(f"simulate_batch: {name} with per_robot_nn=True is not served here ({what} their network-bank form in "
+                             "knode.simulate_bank)")
     if score is not None or any(value is not None for _, value, _ in per_step):
         ctl_shape = np.asarray(ctl).shape
         if len(ctl_shape) != 3:
@@ -401,11 +414,23 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         if robots is None:
             raise kn.KrError("simulate_batch: per_robot_nn needs robots=[...]")
         networks, net_of_rod = _robots_networks(robot, robots)
+    if score is None:
+        score_ref = score_point = None
+    return _run_batch(robot._native(), ctl, dtype, scheme, return_states, tol, maxit, tip_only, robot._use_nn, rows, networks, None,
+                      net_of_rod, loads, bnd, kp_idx, score_ref, score_point)
+
+
+def _run_batch(h, ctl, dtype, scheme, return_states, tol, maxit, tip_only, use_nn, rows, networks, bank, net_of_rod, loads, bnd,
+               kp_idx, score_ref, score_point, scores_only=False):
+    """The device half of ``simulate_batch`` / ``simulate_bank`` on handle ``h``, everything validated by the caller:
+    ``rows`` the table's, ``networks`` of a bank made and closed here or ``bank`` a live one of the caller's, ``loads`` /
+    ``bnd`` / ``kp_idx`` / ``score_ref`` as the caller's helpers return them (None: without)."""
     import torch
-    h = robot._native()
     table = h.param_table(rows) if rows is not None else None
-    bank = h.mlp_bank(networks) if networks is not None else None
-    dev = f"cuda:{robot.device}"
+    own_bank = networks is not None
+    if own_bank:
+        bank = h.mlp_bank(networks)
+    dev = f"cuda:{h.device}"
     tdt = torch.float64 if dtype in ("f64", torch.float64, np.float64) else torch.float32
     ctl_t = torch.as_tensor(np.asarray(ctl, dtype=np.float64), device=dev).to(tdt).contiguous()
     B, T = ctl_t.shape[0], ctl_t.shape[1]
@@ -422,9 +447,10 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         kp_all = torch.empty((T + 1, B, len(kp_idx), kn.KR_SLOTS), dtype=tdt, device=dev)
         kp_all[0] = states[0][:, torch.as_tensor(kp_idx.astype(np.int64), device=dev)]
     h.simulate(ctl_t, states, G, ring=tip_only, tip=tip, status=status,
-               scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=robot._use_nn,
+               scheme=kn.KR_RK4 if scheme == "rk4" else kn.KR_EULER, tol=tol, maxit=maxit, use_nn=use_nn,
                table=table, bank=bank, net_of_rod=net_of_rod, loads=loads_t, bnd=bnd_t,
                **({"key_points": kp_idx, "kp": kp_all[1:]} if kp_idx is not None else {}))
+    score = score_ref
     if score is not None:  # queued behind the run; the copies below wait for both
         Tr = score_ref.shape[1]
         ref_states = h.pack_poses(score_ref, tdt)  # [Tr, 1 or B, N, KR_SLOTS], packed once
@@ -438,13 +464,20 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         if kp_idx is not None:
             ref_kp = ref_states[:, :, torch.as_tensor(kp_idx.astype(np.int64), device=dev)].contiguous()
             score_mse_kp, _ = h.pose_mse_points(kp_all[:Tr], ref_kp)
+    if scores_only:  # (evaluate_bank: nothing but the scores leaves the device; .cpu() waits for the run)
+        out = {"dtw": score_dtw.cpu().numpy(), "mse_kp": score_mse_kp.cpu().numpy()}
+        table.close()
+        if own_bank:
+            bank.close()
+        return out
     out = {"tip": tip.cpu().numpy(), "status": status.cpu().numpy(), "G": G.cpu().numpy()}  # (.cpu() waits for the run)
     if table is not None:
         table.close()
     if bank is not None:
         out["net_of_rod"] = np.asarray(net_of_rod, dtype=np.int32)
         out["n_networks"] = bank.K
-        bank.close()
+        if own_bank:
+            bank.close()
     if score is not None:
         out["dtw"] = score_dtw.cpu().numpy()
         if score_mse is not None:
@@ -463,6 +496,63 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
             traj[:, t, 19:] = z
         out["traj"] = traj.cpu().numpy()
     return out
+
+
+def _bank_call_inputs(robot, robots, ctl, tip_only, score, tip_loads, base_motion, key_points, check_finite):
+    """Everything ``simulate_bank`` validates and prepares on the host, before the first device or library call that
+    needs a GPU: ``(rows, networks, net_of_rod, bnd, kp_idx, score_ref, score_point)``."""
+    ctl_shape = np.asarray(ctl).shape
+    if len(ctl_shape) != 3:
+        raise kn.KrError(f"simulate_batch: ctl must be [B, T, 4]; got {ctl_shape}")
+    B, T = int(ctl_shape[0]), int(ctl_shape[1])
+    if robots is None:
+        raise kn.KrError("simulate_batch: simulate_bank needs robots=[...], one per rod (rod b runs with the network robots[b] carries)")
+    kp_idx = _key_points(key_points, int(robot.N)) if key_points is not None else None
+    base = _base_motion(base_motion, B, T, check_finite) if base_motion is not None else None
+    loads = _tip_loads(tip_loads, B, T, check_finite) if tip_loads is not None else None
+    score_ref = score_point = None
+    if score is not None:
+        score_ref, score_point = _score_reference(robot, score, B, T, tip_only and kp_idx is None)
+        if tip_only and score_point not in kp_idx.tolist():
+            raise kn.KrError(f"simulate_batch: score point {score_point} is not one of the key points {kp_idx.tolist()} "
+                             "(tip_only=True keeps the states at the key points only)")
+    robots = list(robots)
+    rows = _robots_rows(robot, robots, B)
+    networks, net_of_rod = _robots_networks(robot, robots, zero_ok=True)
+    if base is None:  # a bank call with per-step data is a boundary call: each rod's own base on every step
+        base = _base_of_rows(rows, T)
+    return rows, networks, net_of_rod, _boundary(base, loads, rows), kp_idx, score_ref, score_point
+
+
+def _named(fn, *args):
+    """``fn(*args)`` with the messages of the helpers it shares with ``simulate_batch`` naming ``simulate_bank``."""
+    try:
+        return fn(*args)
+    except kn.KrError as e:
+        err = kn.KrError(str(e).replace("simulate_batch:", "simulate_bank:"))
+        if hasattr(e, "code"):
+            err.code = e.code
+        raise err from None
+
+
+def simulate_bank(robot, robots, ctl, dtype="f64", tol=0.0, maxit=0, tip_only=False, return_states=True, score=None,
+                  tip_loads=None, base_motion=None, key_points=None, check_finite=True):
+    """``simulate_batch(robot, ctl, robots=robots, per_robot_nn=True)`` that also takes the per-step arguments: B rods in
+    ONE launch, rod b with the parameters of ``robots[b]`` AND the network ``robots[b]`` carries, under ``tip_loads`` /
+    ``base_motion`` and with ``key_points`` records - the evaluation half of the reference's experiment
+    (physics_multitrain.py:180-233: every trained network rolled out and scored at key points against a recorded run).
+
+    Every argument means what it means in ``simulate_batch``; the result is laid out the same way (``tip``, ``status``,
+    ``G``, ``net_of_rod``, ``n_networks``, ``traj`` unless ``tip_only`` or ``return_states=False``, ``kp`` / ``key_points``
+    with key points, ``dtw`` / ``mse`` / ``mse_kp`` with ``score``).  A robot with ``nn_path is None`` takes a zero network
+    of the others' shape: the reference's network-free "baseline" rows ride in the same launch.  Without ``base_motion`` /
+    ``tip_loads`` the boundary is each rod's own on every step.  With ``tip_only=True``, ``score`` needs ``key_points`` and
+    a score point among them.  Everything is validated on the host before the first device or library call.  Euler only,
+    one network shape per call, 9 <= N <= 128 (what ``kr_simulate_batch_bank_keypoints`` serves)."""
+    rows, networks, net_of_rod, bnd, kp_idx, score_ref, score_point = _named(
+        _bank_call_inputs, robot, robots, ctl, tip_only, score, tip_loads, base_motion, key_points, check_finite)
+    return _run_batch(robot._native(), ctl, dtype, "euler", return_states, tol, maxit, tip_only, True, rows, networks, None, net_of_rod,
+                      None, bnd, kp_idx, score_ref, score_point)
 
 
 def simulate(robot, ctl, robot_reference=None):

@@ -206,6 +206,24 @@ def evaluate_batch(robot, robots, controls, reference, per_robot_nn=False, point
     return out["dtw"], out["mse"]
 
 
+def evaluate_bank(robot, robots, controls, reference, key_points, point=-1, dtype="f64"):
+    """physics_multitrain.py:180-233 for a grid of trained networks in ONE tip-only launch: rod b runs with the parameters and
+    the network of ``robots[b]`` (``knode.simulate_bank``) over ``controls[b]`` on a three-state ring, the records of
+    ``key_points`` are the only states stored, and states 0 .. Tr-1 are scored on the device against ``reference``
+    ([Tr, >=7, N] or [B, Tr, >=7, N]).  Returns ``(dtw[B], mse_kp[B])``: the exact DTW of the path of grid point ``point``
+    (-1: the tip; it must be a key point) and the pose MSE x 1000 over the key points.  Nothing but the scores leaves the
+    device."""
+    import knode
+    import krod_native as kn
+    if key_points is None:
+        raise kn.KrError("evaluate_bank: key_points is required (a tip-only run keeps the states at the key points only)")
+    rows, networks, net_of_rod, bnd, kp_idx, score_ref, score_point = knode._named(
+        knode._bank_call_inputs, robot, robots, controls, True, {"reference": reference, "point": point}, None, None, key_points, True)
+    out = knode._run_batch(robot._native(), controls, dtype, "euler", False, 0.0, 0, True, True, rows, networks, None, net_of_rod, None, bnd,
+                           kp_idx, score_ref, score_point, scores_only=True)
+    return out["dtw"], out["mse_kp"]
+
+
 def evaluate(robot_eval, torch_robot, controls, reference, eval_len=None, tip_index=-1, exact=False):
     """physics_train.py:136-167: put the current weights of `torch_robot` into the NumPy-side robot,
     roll it out in closed loop over `controls` and score the tip path against `reference[:, :3, tip]` with FastDTW

@@ -114,6 +114,9 @@ _PROTOS = {
     "kr_mlp_bank_create": (_int, [_vp, _int, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _int, _vp,
                                   C.POINTER(_vp)]),
     "kr_mlp_bank_destroy": (_int, [_vp]),
+    "kr_mlp_bank_repack": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _int, _vp]),
+    "kr_simulate_batch_bank_keypoints": (_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i64, _int, _vp, _vp, _int, C.POINTER(C.c_int32),
+                                                _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp, _vp, _int, _vp]),
     "kr_simulate_batch_bank": (_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i64, _int, _vp, _vp, _int, _vp, _vp, C.c_double, _int, _vp,
                                       _vp, _int, _vp]),
     "kr_next_segment_physics": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp]),
@@ -302,22 +305,44 @@ class ParamTable:
             pass
 
 
+def _on_device(x):
+    return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+
+
+def _bank_layer(x, k, on_device):
+    """One weight or bias array of network k as the library reads it: a float32 host array, or - a bank of device
+    sources - the contiguous float32 device tensor itself (never copied)."""
+    if not on_device:
+        if _on_device(x):
+            raise KrError(f"network bank: network {k} holds a device tensor next to host arrays (one kind per bank)")
+        return np.ascontiguousarray(x.detach().numpy() if hasattr(x, "detach") else x, dtype=np.float32)
+    if not _on_device(x) or str(x.dtype) != "torch.float32" or not x.is_contiguous():
+        raise KrError(f"network bank: network {k}: device sources are contiguous float32 device tensors, all of them")
+    return x
+
+
+def _bank_addr(x):
+    return x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data
+
+
 def _bank_shape(networks):
     """(dims, acts, per-network float32 arrays) of a sequence of (weights, biases, acts); every network must have the
-    shape of the first.  Host only."""
+    shape of the first.  Host only.  The arrays are host arrays or - all of them - device tensors, which are handed
+    to the library where they lie."""
     nets = list(networks)
     if not nets:
         return [], [], []
+    on_device = bool(nets[0][0]) and _on_device(nets[0][0][0])
     packed, dims0, acts0 = [], None, None
     for k, (weights, biases, acts) in enumerate(nets):
-        Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
+        Ws = [_bank_layer(w, k, on_device) for w in weights]
+        bs = [_bank_layer(b, k, on_device) for b in biases]
         if not Ws or len(Ws) != len(bs) or len(Ws) != len(acts) or any(w.ndim != 2 for w in Ws):
             raise KrError(f"network bank: network {k}: malformed layer lists")
         dims = [Ws[0].shape[1]] + [w.shape[0] for w in Ws]
         for l in range(len(Ws)):
-            if Ws[l].shape[1] != dims[l] or bs[l].shape != (dims[l + 1],):
-                raise KrError(f"network bank: network {k}, layer {l}: inconsistent shapes {Ws[l].shape} / {bs[l].shape}")
+            if Ws[l].shape[1] != dims[l] or tuple(bs[l].shape) != (dims[l + 1],):
+                raise KrError(f"network bank: network {k}, layer {l}: inconsistent shapes {tuple(Ws[l].shape)} / {tuple(bs[l].shape)}")
         acts = [int(a) for a in acts]
         if dims0 is None:
             dims0, acts0 = dims, acts
@@ -343,22 +368,45 @@ def mlp_bank_check(base: KrParams, K: int, dims, acts):
 class MlpBank:
     """Owns one kr_mlp_bank: K networks of one shape, ``networks[k] = (weights, biases, acts)`` as for
     ``Handle.set_mlp``; rod b of ``Handle.simulate(..., table=, bank=, net_of_rod=)`` evaluates network
-    ``net_of_rod[b]``.  Immutable; usable as a context manager.  Close it only after the last call that uses it has
-    finished on its stream."""
+    ``net_of_rod[b]``, and with ``bnd=`` / ``key_points=`` beside them the call takes per-step boundary data and
+    writes key-point records too.  The arrays are host arrays or - all of them - float32 device tensors.  Changed only
+    by ``repack``; usable as a context manager.  Close it only after the last call that uses it has finished on its
+    stream."""
 
     def __init__(self, handle: "Handle", networks):
         self.lib = handle.lib
+        self._handle = handle
         dims, acts, packed = _bank_shape(networks)
         self.K = len(packed)
         self.dims, self.acts = tuple(dims), tuple(acts)
         n = len(acts)
         dims_c = (C.c_int32 * max(len(dims), 1))(*dims)
         acts_c = (C.c_int32 * max(n, 1))(*acts)
-        Wp = (_vp * max(self.K * n, 1))(*[w.ctypes.data for Ws, _ in packed for w in Ws])
-        bp = (_vp * max(self.K * n, 1))(*[b.ctypes.data for _, bs in packed for b in bs])
+        Wp, bp, on_device = self._sources(packed)
         self._b = _vp()
-        # (the library has read the host arrays when create returns: `packed` need not outlive this call)
-        check(self.lib.kr_mlp_bank_create(handle._h, self.K, n, dims_c, acts_c, Wp, bp, 0, _stream(), C.byref(self._b)))
+        # (the library has read the arrays, host or device, when create returns: `packed` need not outlive this call)
+        check(self.lib.kr_mlp_bank_create(handle._h, self.K, n, dims_c, acts_c, Wp, bp, on_device, _stream(), C.byref(self._b)))
+
+    def _sources(self, packed):
+        n = len(self.acts)
+        Wp = (_vp * max(self.K * n, 1))(*[_bank_addr(w) for Ws, _ in packed for w in Ws])
+        bp = (_vp * max(self.K * n, 1))(*[_bank_addr(b) for _, bs in packed for b in bs])
+        return Wp, bp, int(bool(packed) and _on_device(packed[0][0][0]))
+
+    def repack(self, networks):
+        """New weights for all K networks, in place: ``networks`` as for the constructor and of the bank's shape.  The
+        result is bit-identical to a fresh bank.  Nothing is allocated; device tensors are read where they lie by
+        launches ordered on the current stream (no synchronisation, no host copy) and must stay unchanged until those
+        have run.  Calls queued behind it see the new weights."""
+        if not self._b:
+            raise KrError("network bank: repack of a closed bank")
+        dims, acts, packed = _bank_shape(networks)
+        if len(packed) != self.K or tuple(dims) != self.dims or tuple(acts) != self.acts:
+            raise KrError(f"network bank: repack takes {self.K} networks of layers {list(self.dims)} / activations {list(self.acts)}; "
+                          f"got {len(packed)} of {dims} / {acts}")
+        Wp, bp, on_device = self._sources(packed)
+        check(self.lib.kr_mlp_bank_repack(self._handle._h, self._b, Wp, bp, on_device, _stream()))
+        return self
 
     def close(self):
         if getattr(self, "_b", None) is not None and self._b:
@@ -381,13 +429,14 @@ class MlpBank:
 
 # Handle.simulate, per kind of call: what it says beside bank= / net_of_rod=, beside loads=, and when what it needs is missing
 _SIM_RULES = {
-    "keypoints": ("key_points= together with bank=: key-point records are not served with a network bank",
+    "keypoints": (None,
                   "key_points= together with loads=: a key-point call takes bnd (its last six columns are the tip wrench)",
                   "a key-point call needs table= and bnd= (a caller with a fixed boundary repeats the rows' values)"),
-    "boundary": ("bnd= together with bank=: per-step boundary data is not served with a network bank",
+    "boundary": (None,
                  "bnd= together with loads=: the last six columns of bnd are the tip wrench",
                  "a boundary call needs table= (a table of identical rows when only the boundary varies)"),
-    "loads": ("loads= together with bank=: per-step tip loads are not served with a network bank", None,
+    "loads": ("loads= together with bank=: per-step tip loads ride with a network bank in bnd= (the last six columns of bnd are "
+              "the tip wrench)", None,
               "a loads call needs table= (a table of identical rows when only the loads vary)"),
     "bank": (None, None, "a bank call needs table=, bank= and net_of_rod= together"),
 }
@@ -585,6 +634,10 @@ class Handle:
             raise KrError(no_bank)
         if no_loads and loads is not None:
             raise KrError(no_loads)
+        # bnd= (and key_points= / kp=) beside a bank: kr_simulate_batch_bank_keypoints, checked as each part is alone
+        with_bank = banked and kind in ("keypoints", "boundary")
+        if with_bank and (bank is None or net_of_rod is None or not isinstance(bank, MlpBank)):
+            raise KrError("bnd= / key_points= together with a bank need bank= (an MlpBank) and net_of_rod= together")
         if needs and (table is None or (kind == "keypoints" and bnd is None) or (kind == "bank" and (bank is None or net_of_rod is None))):
             raise KrError(needs)
         if kind == "keypoints" and (key_points is None or kp is None):
@@ -599,6 +652,10 @@ class Handle:
         if kind in ("keypoints", "bank"):
             idx = np.ascontiguousarray(np.asarray(key_points if kind == "keypoints" else net_of_rod).reshape(-1), dtype=np.int32)
             idx_p, K = idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size)
+        if with_bank:  # rod b: row b of the table, network net_of_rod[b] of the bank
+            nets = np.ascontiguousarray(np.asarray(net_of_rod).reshape(-1), dtype=np.int32)
+            if nets.size != B:
+                raise KrError(f"ctl holds {B} rods, net_of_rod {nets.size}")
         if kind == "keypoints" and (tuple(kp.shape) != (T, B, K, KR_SLOTS) or kp.dtype != ctl.dtype or not kp.is_contiguous()):
             # kp[t, b, k] receives the complete record of grid point key_points[k] of the state step t writes
             raise KrError(f"kp must be a contiguous [{T}, {B}, {K}, {KR_SLOTS}] tensor of {ctl.dtype}; got {tuple(kp.shape)} {kp.dtype}")
@@ -615,6 +672,10 @@ class Handle:
             rc = lib.kr_simulate_batch_table(h, table._t, *head, *mid, nn, *end)
         elif kind == "loads":
             rc = lib.kr_simulate_batch_loads(h, table._t, *head, _ptr(loads), *mid, nn, *end)
+        elif with_bank:  # (a bank's networks are on: no use_nn; a boundary call is the key-point call with K = 0)
+            points = (K, idx_p, _ptr(kp)) if kind == "keypoints" else (0, None, None)
+            rc = lib.kr_simulate_batch_bank_keypoints(h, table._t, bank._b, nets.ctypes.data_as(C.POINTER(C.c_int32)), *head, _ptr(bnd),
+                                                      *points, *mid, *end)
         elif kind == "boundary":
             rc = lib.kr_simulate_batch_boundary(h, table._t, *head, _ptr(bnd), *mid, nn, *end)
         elif kind == "keypoints":

@@ -482,7 +482,7 @@ class KnodeBankTrainer:
 
     Parameters, gradients, moments and schedules are ``[n_nets][...]`` buffers; robot k's ``nn_models`` parameters become
     views of row k, so checkpoints, ``krod_eval.evaluate`` and ``simulate_batch(..., per_robot_nn=True)`` see the live
-    weights.  Not served (KrError, never a loop over single trainings): robots of differing MLP structure, networks the
+    weights; ``evaluate`` rolls all of them out closed-loop in one launch, straight from those buffers.  Not served (KrError, never a loop over single trainings): robots of differing MLP structure, networks the
     bank kernels do not take, data-parallel training."""
 
     def __init__(self, robots, trajs, controls, key_pt_idx, lr=1e-2, weight_decay=0.0, clamp_weights=True,
@@ -574,6 +574,8 @@ class KnodeBankTrainer:
         self._bank = None
         self._repack = True
         self._param_versions = None
+        self._structs = structs
+        self._eval_bank = None
         self._make_bank()
 
     def _make_bank(self):
@@ -605,8 +607,53 @@ class KnodeBankTrainer:
     def __del__(self):
         try:
             self.close()
+            self._close_eval_bank()
         except Exception:
             pass
+
+    def _close_eval_bank(self):
+        """Frees the simulate bank of ``evaluate`` (after everything queued on it has finished)."""
+        if getattr(self, "_eval_bank", None) is not None:
+            torch.cuda.synchronize()
+            self._eval_bank.close()
+            self._eval_bank = None
+
+    def evaluate(self, controls, reference, key_points, point=-1, dtype="f64"):
+        """physics_train.py:136-167 for all ``n_nets`` live networks at once: rod k runs closed-loop over ``controls[k]``
+        ([n_nets, T, 4]) with the parameters of ``robots[k]`` and network k as it lies in ``flat_p`` - a simulate bank of
+        device sources, created on first use and repacked in place afterwards (``MlpBank.repack``: no host copy of a weight,
+        no allocation, ordered behind the epochs queued so far) - in one tip-only launch that stores the records of
+        ``key_points`` only, scored on the device against ``reference`` ([Tr, >=7, N] or [n_nets, Tr, >=7, N]).  Returns
+        ``(dtw[n_nets], mse_kp[n_nets])`` as ``krod_eval.evaluate_bank`` does; ``point`` (-1: the tip) must be a key point.
+        Everything is validated on the host before the first device call."""
+        import knode
+        ctl_shape = np.asarray(controls).shape
+        if len(ctl_shape) != 3 or ctl_shape[0] != self.n_nets:
+            raise kn.KrError(f"KnodeBankTrainer.evaluate: controls must be [n_nets, T, 4] = [{self.n_nets}, T, 4]; got {ctl_shape}")
+        B, T = int(ctl_shape[0]), int(ctl_shape[1])
+        if key_points is None:
+            raise kn.KrError("KnodeBankTrainer.evaluate: key_points is required (a tip-only run keeps the states at the key points only)")
+        carrier = self.robots[0]
+        kp_idx = knode._key_points(key_points, int(carrier.N))
+        score_ref, score_point = knode._score_reference(carrier, {"reference": reference, "point": point}, B, T, False)
+        if score_point not in kp_idx.tolist():
+            raise kn.KrError(f"KnodeBankTrainer.evaluate: score point {score_point} is not one of the key points {kp_idx.tolist()}")
+        rows = knode._robots_rows(carrier, self.robots, B)
+        dims, acts = [int(d) for d in self.dims_c], [int(a) for a in self.acts_c]
+        rc, msg = kn.mlp_bank_check(carrier._params(), B, dims, acts)
+        if rc != 0:
+            err = kn.KrError(f"libknode_rod error {rc}: {msg}")
+            err.code = rc
+            raise err
+        bnd = knode._boundary(knode._base_of_rows(rows, T), None, rows)
+        nets = [([l.weight.data for l, _ in st], [l.bias.data for l, _ in st], [a for _, a in st]) for st in self._structs]
+        if self._eval_bank is None:
+            self._eval_bank = self.h.mlp_bank(nets)
+        else:
+            self._eval_bank.repack(nets)
+        out = knode._run_batch(self.h, controls, dtype, "euler", False, 0.0, 0, True, True, rows, None, self._eval_bank,
+                               list(range(B)), None, bnd, kp_idx, score_ref, score_point, scores_only=True)
+        return out["dtw"], out["mse_kp"]
 
     def weights_changed(self):
         """Tell the trainer that some parameters were written from outside (a loaded checkpoint): the next epoch packs the
