@@ -718,9 +718,11 @@ int kr_estimate_state(kr_handle* h, int64_t T, const double* data, const double*
  * All metric arithmetic is fp64 whatever `dtype`, which is only the element type of the inputs; outputs are double.
  * The calls use none of the handle's scratch; kr_pose_mse_batch takes N from the handle, kr_pose_mse_points_batch
  * and kr_dtw_batch read no parameter at all.
- * FastDTW (what the reference calls) is NOT built on the device: it needs the warp path traced back on every level of
- * its pyramid, its parity with the third-party package is unpinned in this project anyway (krod_eval.py), and the
- * exact distance below is the quantity it approximates (and a lower bound of it). */
+ * Two tip metrics: kr_dtw_batch, the exact DTW, and kr_fastdtw_batch, FastDTW - what the reference calls
+ * (fastdtw(a, b)[0], radius 1) - whose warp path is traced back on every level of its pyramid on the device.  The
+ * exact distance is the quantity FastDTW approximates and a lower bound of it; the two differ on a good share of
+ * ordinary paths.  Parity of krod_eval's statement of FastDTW with the third-party package stays unpinned
+ * (krod_eval.py): kr_fastdtw_batch is bit-identical to krod_eval, whatever that parity is. */
 #define KR_DTW_MAX_LEN 4096
 
 /* Exact dynamic-time-warping distance, L1 point distance, between 3-vectors - what
@@ -740,6 +742,39 @@ int kr_dtw_batch(kr_handle* h, int64_t B,
                  const void* a, int64_t Ta, int64_t a_rod_stride, int64_t a_step_stride,
                  const void* b, int64_t Tb, int64_t b_rod_stride, int64_t b_step_stride,
                  double* dist, int dtype, void* stream);
+
+/* FastDTW (S. Salvador, P. Chan 2007), L1 point distance between 3-vectors, as krod_eval._fastdtw states it - the
+ * metric of physics_multitrain.py:211-213 / physics_train.py:159 at radius 1.  a, b and their strides: exactly as for
+ * kr_dtw_batch.  dist[B]; path[B][Ta + Tb - 1][2] and path_len[B] (both nullable, but only together): the level-0 warp
+ * path of every rod as (i, j) pairs from (0, 0) to (Ta - 1, Tb - 1); entries past path_len[b] are left untouched.
+ * The algorithm: level l + 1 of the pyramid is x[i] = (x[2i] + x[2i + 1]) / 2 per component for i < len / 2 (an odd
+ * last sample is dropped), descending while both lengths are >= radius + 2; the deepest level is an exact DTW; every
+ * level's recurrence is cost = (|dx| + |dy|) + |dz|, predecessor = the FIRST minimum in the order up (i - 1, j), left
+ * (i, j - 1), diagonal, D = predecessor + cost, cells outside the level's window +inf; the window of the next finer
+ * level gives fine rows 2c and 2c + 1 the columns [2 lo, 2 hi + 1] (clipped), lo = min(j) - radius, hi = max(j) + radius
+ * over the cells of the coarse path with |i - c| <= radius.  dist, path_len and path are bit-identical to
+ * krod_eval.fastdtw_distance / fastdtw_path on the same (upcast) samples; with a radius that covers the whole table
+ * dist is kr_dtw_batch's.
+ * A rod with a sample that is not finite in either sequence gets dist = NaN and path_len = 0 (its path entries are
+ * left untouched); the call returns KR_OK and every other rod's outputs are bit for bit those of the clean call.
+ * ws: caller-owned device scratch of kr_fastdtw_ws_bytes(B, Ta, Tb, radius) bytes (the back-pointers of level 0 where
+ * they do not fit the LDS; 0 for short sequences - ws may then be NULL; always a multiple of 16).  The call uses none
+ * of the handle's scratch; two calls in flight need two workspaces.  Nothing outside the Ta, Tb samples of a rod, its
+ * outputs and its slice of ws is touched.
+ * KR_E_ARG: a null handle, a, b or dist; B, Ta or Tb < 1; a negative stride; radius < 1 (radius 0 leaves rows without a
+ * window in the host statement); only one of path / path_len; ws NULL while the size is nonzero.  KR_E_UNSUPPORTED:
+ * radius > KR_FASTDTW_MAX_RADIUS or a length > KR_FASTDTW_MAX_LEN.  In every refusal nothing is launched and no
+ * output byte is written.
+ * One wavefront per rod: a banded form of kr_dtw_batch's sweep per level, two bits of back-pointer per cell, one walk
+ * back per level (at level 0 only when the path is asked for). */
+#define KR_FASTDTW_MAX_LEN 1024
+#define KR_FASTDTW_MAX_RADIUS 8
+size_t kr_fastdtw_ws_bytes(int64_t B, int64_t Ta, int64_t Tb, int radius);
+int kr_fastdtw_batch(kr_handle* h, int64_t B,
+                     const void* a, int64_t Ta, int64_t a_rod_stride, int64_t a_step_stride,
+                     const void* b, int64_t Tb, int64_t b_rod_stride, int64_t b_step_stride,
+                     int radius, double* dist, int32_t* path, int32_t* path_len, void* ws,
+                     int dtype, void* stream);
 
 /* physics_multitrain.py:215-222 per rod: mse[b] = 1000 * mean over the first T states and the handle's N grid points
  * of the 3 squared position errors and the 3 squared zyx-Euler-angle errors (6*T*N terms).

@@ -281,13 +281,30 @@ def _kp_rows(records):
     return np.ascontiguousarray(np.concatenate([r[:, :, 12:25], r[:, :, 0:12]], axis=2))
 
 
+SCORE_METRICS = ("dtw", "fastdtw")
+
+
+def _score_metric(score):
+    """``(metric, radius)`` of a ``score`` dictionary: ``"dtw"`` (default; the exact distance, the radius is not used) or
+    ``"fastdtw"`` with ``radius`` 1 .. 8 (default 1, the reference's).  Host-side validation only."""
+    metric = score.get("metric", "dtw")
+    if metric not in SCORE_METRICS:
+        raise kn.KrError(f'simulate_batch: score metric must be "dtw" or "fastdtw"; got {metric!r}')
+    radius = score.get("radius", 1)
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= kn.KR_FASTDTW_MAX_RADIUS:
+        raise kn.KrError(f"simulate_batch: score radius must be an integer 1 .. {kn.KR_FASTDTW_MAX_RADIUS}; got {radius!r}")
+    return metric, int(radius)
+
+
 def _score_reference(robot, score, B, T, tip_only):
     """``(reference[R, Tr, >=7, N], point)`` of ``simulate_batch(..., score=...)``, R = 1 or B; host-side validation only
-    (no device call)."""
+    (no device call), ``metric`` and ``radius`` included (``_score_metric`` returns them)."""
     if tip_only:
         raise kn.KrError("simulate_batch: score needs the state history (tip_only=True keeps three states)")
     if not isinstance(score, dict) or "reference" not in score:
-        raise kn.KrError('simulate_batch: score must be {"reference": array[, "point": grid point]}')
+        raise kn.KrError('simulate_batch: score must be {"reference": array[, "point": grid point][, "metric": "dtw" | "fastdtw"]'
+                         '[, "radius": 1 .. 8]}')
+    metric, _ = _score_metric(score)
     ref = np.asarray(score["reference"], dtype=np.float64)
     N = int(robot.N)
     shared = ref.ndim == 3
@@ -304,6 +321,8 @@ def _score_reference(robot, score, B, T, tip_only):
         raise kn.KrError(f"simulate_batch: score reference holds {R} rods, ctl {B}")
     if Tr < 1 or Tr > T + 1:
         raise kn.KrError(f"simulate_batch: score reference has {Tr} states, the run 1 .. {T + 1}")
+    if metric == "fastdtw" and Tr > kn.KR_FASTDTW_MAX_LEN:  # (refused here, not after the run)
+        raise kn.KrError(f"simulate_batch: score metric fastdtw serves at most {kn.KR_FASTDTW_MAX_LEN} states, the reference has {Tr}")
     point = score.get("point", None)
     point = N - 1 if point is None else int(point)
     if not -N <= point < N:
@@ -338,6 +357,9 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
     distance (L1) of the path of grid point p (default N - 1, the tip - the reference's literal 9 at its N = 10) to the
     reference's, and ``mse`` float64[B], the position + zyx-Euler MSE x 1000 (``krod_eval.dtw_distance`` /
     ``pos_euler_mse``).  With ``return_states=False`` no trajectory leaves the device.
+    ``"metric": "fastdtw"`` (and ``"radius"``, 1 .. 8, default 1) makes ``dtw`` the FastDTW distance instead - the number
+    the reference's ``fastdtw(...)[0]`` prints, ``krod_eval.fastdtw_distance`` bit for bit (``kr_fastdtw_batch``); the
+    default ``"dtw"`` is the exact distance, as before.  ``dtw_metric`` in the result names the metric used.
 
     tip_loads: a tip wrench that varies in time, [B, T, 6] or [T, 6] (shared by all rods): rod b solves step t with
     F_tip, M_tip = tip_loads[b, t, :3], tip_loads[b, t, 3:] - the reference with ``robot.F_tip`` / ``robot.M_tip``
@@ -392,6 +414,7 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         loads = _tip_loads(tip_loads, int(ctl_shape[0]), int(ctl_shape[1]), check_finite)
     if score is not None:
         score_ref, score_point = _score_reference(robot, score, int(ctl_shape[0]), int(ctl_shape[1]), tip_only and kp_idx is None)
+        score_metric, score_radius = _score_metric(score)
         if tip_only and score_point not in kp_idx.tolist():
             raise kn.KrError(f"simulate_batch: score point {score_point} is not one of the key points {kp_idx.tolist()} "
                              "(tip_only=True keeps the states at the key points only)")
@@ -416,15 +439,17 @@ def simulate_batch(robot, ctl, dtype="f64", scheme="euler", return_states=True, 
         networks, net_of_rod = _robots_networks(robot, robots)
     if score is None:
         score_ref = score_point = None
+        score_metric, score_radius = "dtw", 1
     return _run_batch(robot._native(), ctl, dtype, scheme, return_states, tol, maxit, tip_only, robot._use_nn, rows, networks, None,
-                      net_of_rod, loads, bnd, kp_idx, score_ref, score_point)
+                      net_of_rod, loads, bnd, kp_idx, score_ref, score_point, score_metric=score_metric, score_radius=score_radius)
 
 
 def _run_batch(h, ctl, dtype, scheme, return_states, tol, maxit, tip_only, use_nn, rows, networks, bank, net_of_rod, loads, bnd,
-               kp_idx, score_ref, score_point, scores_only=False):
+               kp_idx, score_ref, score_point, scores_only=False, score_metric="dtw", score_radius=1):
     """The device half of ``simulate_batch`` / ``simulate_bank`` on handle ``h``, everything validated by the caller:
     ``rows`` the table's, ``networks`` of a bank made and closed here or ``bank`` a live one of the caller's, ``loads`` /
-    ``bnd`` / ``kp_idx`` / ``score_ref`` as the caller's helpers return them (None: without)."""
+    ``bnd`` / ``kp_idx`` / ``score_ref`` as the caller's helpers return them (None: without); ``score_metric`` /
+    ``score_radius`` as ``_score_metric`` returns them."""
     import torch
     table = h.param_table(rows) if rows is not None else None
     own_bank = networks is not None
@@ -459,13 +484,17 @@ def _run_batch(h, ctl, dtype, scheme, return_states, tol, maxit, tip_only, use_n
             path = kp_all[:Tr, :, kp_idx.tolist().index(score_point), 12:15].permute(1, 0, 2)
         else:
             path = states[:Tr, :, score_point, 12:15].permute(1, 0, 2)
-        score_dtw = h.dtw(path, ref_path[0] if ref_path.shape[0] == 1 else ref_path)
+        ref_path = ref_path[0] if ref_path.shape[0] == 1 else ref_path
+        if score_metric == "fastdtw":  # (no fall-back: the metric asked for, or the library's error)
+            score_dtw = h.fastdtw(path, ref_path, radius=score_radius)
+        else:
+            score_dtw = h.dtw(path, ref_path)
         score_mse = None if tip_only else h.pose_mse(states[:Tr], ref_states)[0]
         if kp_idx is not None:
             ref_kp = ref_states[:, :, torch.as_tensor(kp_idx.astype(np.int64), device=dev)].contiguous()
             score_mse_kp, _ = h.pose_mse_points(kp_all[:Tr], ref_kp)
     if scores_only:  # (evaluate_bank: nothing but the scores leaves the device; .cpu() waits for the run)
-        out = {"dtw": score_dtw.cpu().numpy(), "mse_kp": score_mse_kp.cpu().numpy()}
+        out = {"dtw": score_dtw.cpu().numpy(), "dtw_metric": score_metric, "mse_kp": score_mse_kp.cpu().numpy()}
         table.close()
         if own_bank:
             bank.close()
@@ -480,6 +509,7 @@ def _run_batch(h, ctl, dtype, scheme, return_states, tol, maxit, tip_only, use_n
             bank.close()
     if score is not None:
         out["dtw"] = score_dtw.cpu().numpy()
+        out["dtw_metric"] = score_metric
         if score_mse is not None:
             out["mse"] = score_mse.cpu().numpy()
         if kp_idx is not None:
@@ -551,8 +581,9 @@ def simulate_bank(robot, robots, ctl, dtype="f64", tol=0.0, maxit=0, tip_only=Fa
     one network shape per call, 9 <= N <= 128 (what ``kr_simulate_batch_bank_keypoints`` serves)."""
     rows, networks, net_of_rod, bnd, kp_idx, score_ref, score_point = _named(
         _bank_call_inputs, robot, robots, ctl, tip_only, score, tip_loads, base_motion, key_points, check_finite)
+    score_metric, score_radius = _score_metric(score) if score is not None else ("dtw", 1)  # (validated above)
     return _run_batch(robot._native(), ctl, dtype, "euler", return_states, tol, maxit, tip_only, True, rows, networks, None, net_of_rod,
-                      None, bnd, kp_idx, score_ref, score_point)
+                      None, bnd, kp_idx, score_ref, score_point, score_metric=score_metric, score_radius=score_radius)
 
 
 def simulate(robot, ctl, robot_reference=None):

@@ -13,11 +13,14 @@
   order (i-1, j), (i, j-1), (i-1, j-1) - the order of the package's ``min`` - which matters for the window of the next
   level.  **Parity with the package is unpinned** (nothing to run it against); ``dtw_distance`` is the exact DTW
   with the same point distance, a lower bound of it (equal whenever the coarse path contains the optimal one).
+  ``fastdtw_path`` returns the warp path with the distance.  These host functions are the normative statement of the
+  algorithm for the device kernel (``kr_fastdtw_batch``), which reproduces them bit for bit.
 * ``pos_euler_mse``: ``physics_multitrain.py:213-222`` (position + zyx Euler angles, x 1000).
-* ``euler_zyx``, ``dtw_distance_batch``, ``pos_euler_mse_batch``, ``evaluate_batch``: the same two metrics for B rods at
-  once on the MI355X (``kr_dtw_batch``, ``kr_pose_mse_batch``) - the exact DTW, not FastDTW: that needs the warp path
-  traced back on every level, and the exact distance is what it approximates.  ``evaluate_batch`` is the inner loop of
-  ``physics_multitrain.py:196-222``; nothing but two doubles per rod leaves the device.
+* ``euler_zyx``, ``dtw_distance_batch``, ``fastdtw_distance_batch``, ``pos_euler_mse_batch``, ``evaluate_batch``,
+  ``evaluate_bank``: the same metrics for B rods at once on the MI355X (``kr_dtw_batch``, ``kr_fastdtw_batch``,
+  ``kr_pose_mse_batch``).  ``metric="dtw"`` (default) scores with the exact DTW, ``metric="fastdtw"`` with FastDTW - the
+  figure the reference prints - whose warp path is traced back on every level on the device.  ``evaluate_batch`` is the
+  inner loop of ``physics_multitrain.py:196-222``; nothing but two doubles per rod leaves the device.
 * ``evaluate``: the closed-loop rollout with live weights of ``physics_train.py:136-167``; the rollout is
   ``knode.simulate`` on the MI355X with the MLP inside the shooting sweeps.
 """
@@ -139,6 +142,21 @@ def fastdtw_distance(a, b, radius=1):
     return float(_fastdtw([r for r in a], [r for r in b], int(radius))[0])
 
 
+def fastdtw_path(a, b, radius=1):
+    """``(distance, path)`` of FastDTW between a[Ta, d] and b[Tb, d]: ``fastdtw_distance`` together with the level-0 warp
+    path, a list of (i, j) pairs from (0, 0) to (Ta - 1, Tb - 1) - the pair the package's ``fastdtw(a, b)`` returns."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if a.ndim == 1:
+        a = a[:, None]
+    if b.ndim == 1:
+        b = b[:, None]
+    if len(a) == 0 or len(b) == 0:
+        raise ValueError("empty sequence")
+    dist, path = _fastdtw([r for r in a], [r for r in b], int(radius))
+    return float(dist), [(int(i), int(j)) for i, j in path]
+
+
 def pos_euler_mse(trajectory, reference):
     """physics_multitrain.py:213-222: mean of the squared position errors and the squared zyx-Euler-angle
     errors over all grid points and steps, times 1000.  trajectory, reference: [T, >=7, N]."""
@@ -182,6 +200,23 @@ def dtw_distance_batch(robot, a, b, dtype="f64"):
     return h.dtw(up(a), up(b)).cpu().numpy()
 
 
+def fastdtw_distance_batch(robot, a, b, radius=1, dtype="f64", return_path=False):
+    """``fastdtw_distance(a[r], b[r], radius)`` for every rod r in one launch on the robot's device (``kr_fastdtw_batch``):
+    a[B, Ta, 3], b[B, Tb, 3] or b[Tb, 3] (one path for all rods), host arrays, uploaded as ``dtype`` (the arithmetic is
+    fp64).  Returns float64[B], bit-identical to the host function on the same samples (NaN for a rod with a non-finite
+    sample); with ``return_path=True`` ``(dist, paths)``, ``paths[r]`` the int32 [len, 2] warp path of rod r
+    (``fastdtw_path``; empty for a NaN rod)."""
+    import torch
+    dev, tdt = f"cuda:{robot.device}", _torch_dtype(dtype)
+    h = robot._native()
+    up = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64), device=dev).to(tdt).contiguous()
+    if not return_path:
+        return h.fastdtw(up(a), up(b), radius=radius).cpu().numpy()
+    dist, steps, plen = h.fastdtw(up(a), up(b), radius=radius, path=True)
+    steps, plen = steps.cpu().numpy(), plen.cpu().numpy()
+    return dist.cpu().numpy(), [steps[r, :plen[r]].copy() for r in range(len(plen))]
+
+
 def pos_euler_mse_batch(robot, trajectories, reference, dtype="f64"):
     """``pos_euler_mse(trajectories[r], reference)`` for every rod r in one launch: trajectories[B, T, >=7, N],
     reference[T, >=7, N] (shared) or [B, T, >=7, N], N = the robot's.  Returns float64[B]."""
@@ -195,32 +230,35 @@ def pos_euler_mse_batch(robot, trajectories, reference, dtype="f64"):
     return mse.cpu().numpy()
 
 
-def evaluate_batch(robot, robots, controls, reference, per_robot_nn=False, point=-1, dtype="f64"):
+def evaluate_batch(robot, robots, controls, reference, per_robot_nn=False, point=-1, dtype="f64", metric="dtw", radius=1):
     """The inner loop of physics_multitrain.py:196-222 for B rods at once: roll every ``robots[b]`` (None: B copies of
     ``robot``) out over ``controls[b]`` in one ``knode.simulate_batch`` call and score states 0 .. Tr-1 against
     ``reference`` ([Tr, >=7, N] or [B, Tr, >=7, N]) on the device.  Returns ``(dtw[B], mse[B])``: the exact DTW of the
-    path of grid point ``point`` (-1: the tip) and the position + Euler MSE x 1000; no trajectory leaves the device."""
+    path of grid point ``point`` (-1: the tip) and the position + Euler MSE x 1000; no trajectory leaves the device.
+    ``metric="fastdtw"`` (``radius`` 1 .. 8): the first array is the FastDTW distance, the reference's own figure."""
     from knode import simulate_batch
     out = simulate_batch(robot, controls, dtype=dtype, return_states=False, robots=robots, per_robot_nn=per_robot_nn,
-                         score={"reference": reference, "point": point})
+                         score={"reference": reference, "point": point, "metric": metric, "radius": radius})
     return out["dtw"], out["mse"]
 
 
-def evaluate_bank(robot, robots, controls, reference, key_points, point=-1, dtype="f64"):
+def evaluate_bank(robot, robots, controls, reference, key_points, point=-1, dtype="f64", metric="dtw", radius=1):
     """physics_multitrain.py:180-233 for a grid of trained networks in ONE tip-only launch: rod b runs with the parameters and
     the network of ``robots[b]`` (``knode.simulate_bank``) over ``controls[b]`` on a three-state ring, the records of
     ``key_points`` are the only states stored, and states 0 .. Tr-1 are scored on the device against ``reference``
     ([Tr, >=7, N] or [B, Tr, >=7, N]).  Returns ``(dtw[B], mse_kp[B])``: the exact DTW of the path of grid point ``point``
     (-1: the tip; it must be a key point) and the pose MSE x 1000 over the key points.  Nothing but the scores leaves the
-    device."""
+    device.  ``metric="fastdtw"`` (``radius`` 1 .. 8): the first array is the FastDTW distance, the reference's own figure."""
     import knode
     import krod_native as kn
     if key_points is None:
         raise kn.KrError("evaluate_bank: key_points is required (a tip-only run keeps the states at the key points only)")
+    score = {"reference": reference, "point": point, "metric": metric, "radius": radius}
     rows, networks, net_of_rod, bnd, kp_idx, score_ref, score_point = knode._named(
-        knode._bank_call_inputs, robot, robots, controls, True, {"reference": reference, "point": point}, None, None, key_points, True)
+        knode._bank_call_inputs, robot, robots, controls, True, score, None, None, key_points, True)
+    score_metric, score_radius = knode._score_metric(score)
     out = knode._run_batch(robot._native(), controls, dtype, "euler", False, 0.0, 0, True, True, rows, networks, None, net_of_rod, None, bnd,
-                           kp_idx, score_ref, score_point, scores_only=True)
+                           kp_idx, score_ref, score_point, scores_only=True, score_metric=score_metric, score_radius=score_radius)
     return out["dtw"], out["mse_kp"]
 
 

@@ -25,6 +25,7 @@ ACT_NONE, ACT_TANH, ACT_SOFTPLUS, ACT_RELU, ACT_ELU = range(5)
 ST_CONVERGED, ST_MAXIT, ST_NONFINITE = 0, 1, 2
 KR_MAX_LAYERS = 8
 KR_DTW_MAX_LEN = 4096
+KR_FASTDTW_MAX_LEN, KR_FASTDTW_MAX_RADIUS = 1024, 8  # kr_fastdtw_batch: samples per sequence, radius
 KR_BND = 19  # p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) per rod and step (kr_simulate_batch_boundary)
 KR_KEYPOINTS_MAX = 16  # key points per call (kr_simulate_batch_keypoints)
 KR_E_ARG, KR_E_UNSUPPORTED = -1, -4
@@ -147,6 +148,8 @@ _PROTOS = {
     "kr_estimate_ws_bytes": (C.c_size_t, [_i64, _int]),
     "kr_estimate_state": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "kr_dtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp]),
+    "kr_fastdtw_ws_bytes": (C.c_size_t, [_i64, _i64, _i64, _int]),
+    "kr_fastdtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_pose_mse_batch": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
     "kr_pose_mse_points_batch": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
 }
@@ -703,6 +706,34 @@ class Handle:
         check(self.lib.kr_dtw_batch(self._h, B, C.c_void_p(a.data_ptr()), Ta, ars, ass, C.c_void_p(b.data_ptr()), Tb, brs, bss,
                                     _ptr(out), dtype_code(a.dtype), _stream()))
         return out
+
+    def fastdtw(self, a, b, radius=1, path=False, out=None):
+        """FastDTW distance (L1 point distance, ``radius``) of every rod's path ``a[b]`` to ``b[b]`` - the reference's
+        ``fastdtw(a, b)[0]`` at radius 1: the sequences are given as for ``dtw`` (views are read in place).  Returns float64
+        ``[B]`` on the device, bit-identical to ``krod_eval.fastdtw_distance`` per rod; a rod with a non-finite sample gets NaN.
+        ``path=True``: ``(dist, path, path_len)`` with ``path`` int32 ``[B, Ta + Tb - 1, 2]``, the level-0 warp path of rod b
+        in its first ``path_len[b]`` entries (``krod_eval.fastdtw_path``; the rest is zero here).  The workspace is allocated
+        here (``kr_fastdtw_ws_bytes``)."""
+        import torch
+        if a.dim() != 3:
+            raise KrError(f"fastdtw: sequence a must be [B, Ta, 3]; got {tuple(a.shape)}")
+        if a.dtype != b.dtype:
+            raise KrError(f"fastdtw: a is {a.dtype}, b {b.dtype}")
+        B = a.shape[0]
+        ars, ass, Ta = _dtw_view(a, B, "a")
+        brs, bss, Tb = _dtw_view(b, B, "b")
+        radius = int(radius)
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float64, device=a.device)
+        steps = plen = None
+        if path:
+            steps = torch.zeros((B, Ta + Tb - 1, 2), dtype=torch.int32, device=a.device)
+            plen = torch.zeros((B,), dtype=torch.int32, device=a.device)
+        nbytes = int(self.lib.kr_fastdtw_ws_bytes(B, Ta, Tb, radius))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=a.device) if nbytes else None
+        check(self.lib.kr_fastdtw_batch(self._h, B, C.c_void_p(a.data_ptr()), Ta, ars, ass, C.c_void_p(b.data_ptr()), Tb, brs, bss,
+                                        radius, _ptr(out), _ptr(steps), _ptr(plen), _ptr(ws), dtype_code(a.dtype), _stream()))
+        return (out, steps, plen) if path else out
 
     def pose_mse(self, states, ref_states):
         """Position + zyx-Euler MSE x 1000 of every rod over packed states ``[T, B, N, KR_SLOTS]`` (the first T slots of a

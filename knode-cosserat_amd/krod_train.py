@@ -618,13 +618,15 @@ class KnodeBankTrainer:
             self._eval_bank.close()
             self._eval_bank = None
 
-    def evaluate(self, controls, reference, key_points, point=-1, dtype="f64"):
+    def evaluate(self, controls, reference, key_points, point=-1, dtype="f64", metric="dtw", radius=1):
         """physics_train.py:136-167 for all ``n_nets`` live networks at once: rod k runs closed-loop over ``controls[k]``
         ([n_nets, T, 4]) with the parameters of ``robots[k]`` and network k as it lies in ``flat_p`` - a simulate bank of
         device sources, created on first use and repacked in place afterwards (``MlpBank.repack``: no host copy of a weight,
         no allocation, ordered behind the epochs queued so far) - in one tip-only launch that stores the records of
         ``key_points`` only, scored on the device against ``reference`` ([Tr, >=7, N] or [n_nets, Tr, >=7, N]).  Returns
         ``(dtw[n_nets], mse_kp[n_nets])`` as ``krod_eval.evaluate_bank`` does; ``point`` (-1: the tip) must be a key point.
+        ``metric="fastdtw"`` (``radius`` 1 .. 8) returns the FastDTW distance, the reference's own figure, in place of the
+        exact DTW.
         Everything is validated on the host before the first device call."""
         import knode
         ctl_shape = np.asarray(controls).shape
@@ -635,7 +637,9 @@ class KnodeBankTrainer:
             raise kn.KrError("KnodeBankTrainer.evaluate: key_points is required (a tip-only run keeps the states at the key points only)")
         carrier = self.robots[0]
         kp_idx = knode._key_points(key_points, int(carrier.N))
-        score_ref, score_point = knode._score_reference(carrier, {"reference": reference, "point": point}, B, T, False)
+        score = {"reference": reference, "point": point, "metric": metric, "radius": radius}
+        score_ref, score_point = knode._score_reference(carrier, score, B, T, False)
+        score_metric, score_radius = knode._score_metric(score)
         if score_point not in kp_idx.tolist():
             raise kn.KrError(f"KnodeBankTrainer.evaluate: score point {score_point} is not one of the key points {kp_idx.tolist()}")
         rows = knode._robots_rows(carrier, self.robots, B)
@@ -652,7 +656,8 @@ class KnodeBankTrainer:
         else:
             self._eval_bank.repack(nets)
         out = knode._run_batch(self.h, controls, dtype, "euler", False, 0.0, 0, True, True, rows, None, self._eval_bank,
-                               list(range(B)), None, bnd, kp_idx, score_ref, score_point, scores_only=True)
+                               list(range(B)), None, bnd, kp_idx, score_ref, score_point, scores_only=True,
+                               score_metric=score_metric, score_radius=score_radius)
         return out["dtw"], out["mse_kp"]
 
     def weights_changed(self):
