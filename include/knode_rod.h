@@ -795,6 +795,69 @@ int kr_pose_mse_batch(kr_handle* h, int64_t B, int64_t T, const void* states, co
 int kr_pose_mse_points_batch(kr_handle* h, int64_t B, int64_t T, int64_t P, const void* records, const void* ref_records,
                              int64_t ref_B, double* mse, double* parts, int dtype, void* stream);
 
+/* ---- adjoint of a solved step, backward pass over a stored rollout ------------------------------------------------- */
+/* The derivative of one pass of the loop in knode.simulate (knode.py:70-100) - BDF2 history, shooting solve of the Euler
+ * sweep (cosserat_ode.py:188-213) for the base wrench G - at its CONVERGED solution, MLP off: given the cotangent
+ * g_next[B][N][KR_SLOTS] of state_next (all 25 values of every grid point, packed like a state) it returns the gradients
+ * with respect to everything the step read.  The reference carries the differentiable sweep
+ * (CosseratRodTorch.getResidualEuler) but never takes it through the solve; this call does, by the implicit-function
+ * theorem: nothing is re-solved, the states are read from state_next as kr_step_batch / kr_simulate_batch left them
+ * (solve with tol ~1e-12: the adjoint is that of the exact root, and the distance to it enters the gradient at first order).
+ * The mathematics, with y_0 = [p0, h0, G, q0, w0], y_{j+1} = y_j + ds f(y_j, hist_j, tf), hist = c1 cur + c2 prev (the
+ * twelve leading slots q w v u; f reads nothing else of the history), tf = tensions @ tendon_dirs:
+ *   sweep      lambda_{N-1} = g_y[N-1];  lambda_j = g_y[j] + lambda_{j+1} + J_j^T [ds lambda_{j+1}; g_z[j]], J_j the complete
+ *              Jacobian of the point map (that of kr_ode_vjp_batch with cut = 0);  a = (n, m) rows of lambda_0
+ *   implicit   M = d(n, m)_{N-1} / dG from the same sweep seeded with the six unit vectors on the tip's (n, m);
+ *              M^T nu = -a;  the total adjoint is the sweep seeded with g plus nu on the tip's (n, m)
+ *   outputs    g_cur[j][0..11] = c1 ghat_j, g_prev[j][0..11] = c2 ghat_j, ghat_j = the history columns of J_j^T applied to
+ *              the total adjoint; slots 12..24 are zero (no equation reads them) and the pads are zero; v, u of the LAST
+ *              grid point of state_next are a copy of state_cur's (the z[:, N-1] the reference never writes), so
+ *              g_cur[N-1][6..11] = g_next[N-1][6..11].  When state_prev aliases state_cur (the reference's first step,
+ *              knode.py:65-66) the gradient of that one state is g_cur + g_prev.
+ *              g_tensions[B][4] = tendon_dirs . sum_j (tendon-force column of J_j^T ...)
+ *              g_bnd[B][KR_BND], in the order of kr_simulate_batch_boundary: lambda_0 rows of p0, h0, q0, w0, then the
+ *              gradient with respect to F_tip, M_tip, which is -nu (the wrench enters the tip condition only)
+ *              resid[B]: |(n, m) rows of the total adjoint's lambda_0|_inf / |a|_inf - zero in exact arithmetic, the
+ *              measure of the 6 x 6 solve (0 when a = 0)
+ * Outputs are overwritten; g_cur, g_prev, g_tensions, g_bnd, resid, status may each be NULL.  No output may overlap an
+ * input.  state_prev may alias state_cur.  Parameters: the handle's (diagonal or full Bse / Bbt, any N >= 2).
+ * Arithmetic is fp64 whatever `dtype`, which is the element type of the arrays only: the KR_F32 call returns the KR_F64
+ * call on the upcast inputs, rounded to float, bit for bit.  One wavefront per rod, no atomics, none of the handle's
+ * scratch: a rod's outputs do not depend on the batch it rides in.
+ * status[B]: KR_ST_CONVERGED; KR_ST_MAXIT when the 6 x 6 solve rejects a pivot of M (zero, or below 1e-13 of M's largest
+ * entry); KR_ST_NONFINITE when any value the step adjoint reads of that rod (the 25 used slots of state_next and g_next,
+ * the twelve leading slots of state_cur / state_prev, the tensions) or M is not finite.  Such values are ordinary input:
+ * the call returns KR_OK; a rod with a nonzero status gets NaN in every gradient value (g_cur / g_prev slots 0..11,
+ * g_tensions, g_bnd, resid; the structurally zero slots stay zero) and every other rod's outputs are bit for bit those
+ * of the clean call.  Nothing of it stays in the handle.
+ * KR_E_UNSUPPORTED, with a message, nothing launched and no output byte written: use_nn != 0 (the network's input
+ * Jacobian is not part of the per-point derivative yet), scheme == KR_RK4.  KR_E_ARG: a null handle, state or g_next or
+ * tensions pointer; B < 1; a bad dtype. */
+int kr_step_vjp_batch(kr_handle* h, int64_t B, int scheme,
+                      const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
+                      const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd,
+                      double* resid, int32_t* status, int use_nn, int dtype, void* stream);
+
+/* The backward pass over a stored rollout of kr_simulate_batch (knode.py:55-102 with the step of knode.py:70-100 and
+ * the sweep of cosserat_ode.py:188-213): ctl[B][T][4] and the FULL history states[T+1][B][N][KR_SLOTS] of that call (a
+ * ring of three slots does not hold what is needed), state_prev_init as given to it (NULL: y_prev = y before the first
+ * step).  g_states[T+1][B][N][KR_SLOTS] is in/out: on entry the direct dL/dstates[t] (a tip loss: slots 12..14 of the last
+ * record of the states it scores), on return the total adjoint of every stored state - g_states[0] is the gradient with
+ * respect to the initial condition.
+ * The result is DEFINED as this composition of kr_step_vjp_batch calls and equals it bit for bit: for t = T-1 .. 0 the
+ * step adjoint of (states[t-1], states[t], states[t+1], ctl[:, t]) with g_next = g_states[t+1]; then
+ * g_states[t] += g_cur and g_states[t-1] += g_prev, in this order, in the element type of the arrays.  Step 0's g_prev
+ * goes into g_states[0] when state_prev_init is NULL, otherwise it is written to g_prev_init[B][N][KR_SLOTS] (nullable).
+ * g_ctl[B][T][4] = g_tensions of step t; g_bnd[B][KR_BND] = the sum over the steps, t = T-1 first (the handle's
+ * boundary is constant in time); resid[B][T], status[B][T] per step.  g_prev_init, g_ctl, g_bnd, resid, status may be
+ * NULL.  A rod whose step t0 reports a nonzero status has NaN in g_ctl[b][t0] and, through g_states[t0], in every
+ * earlier step's outputs; other rods are bit for bit the clean call.
+ * One launch per step plus the accumulations; uses the handle's scratch (two state-sized buffers).
+ * Refusals as for kr_step_vjp_batch, and KR_E_ARG for T < 1 or a null ctl, states or g_states. */
+int kr_simulate_vjp_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
+                          const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
+                          double* resid, int32_t* status, int use_nn, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

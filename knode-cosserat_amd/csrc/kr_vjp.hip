@@ -17,89 +17,9 @@
 // torch.tensor([...]), i.e. as new leaves - through R, h is seen only via the factor 2 / (h . h), and h_s sees h but
 // not u.  cut = 0 differentiates everything (ODE_parallel builds both with torch.stack, so its graph is complete).
 #include "kr_internal.hpp"
+#include "kr_point_dual.hpp"
 
 namespace kr {
-
-struct Dual {
-  double v, d;
-};
-__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.d + b.d}; }
-__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.d - b.d}; }
-__device__ __forceinline__ Dual operator-(Dual a) { return {-a.v, -a.d}; }
-__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return {a.v * b.v, fma(a.v, b.d, a.d * b.v)}; }
-__device__ __forceinline__ Dual operator*(double s, Dual a) { return {s * a.v, s * a.d}; }
-__device__ __forceinline__ Dual operator+(Dual a, double s) { return {a.v + s, a.d}; }
-__device__ __forceinline__ Dual dual_rcp(Dual a) {
-  const double r = 1.0 / a.v;
-  return {r, -a.d * r * r};
-}
-__device__ __forceinline__ Dual dual_abs(Dual a) { return a.v < 0.0 ? Dual{-a.v, -a.d} : a; }  // (torch: sign(0) = 0; d = 0 then anyway for q = 0 ... kept as the value's sign)
-__device__ __forceinline__ Dual detach(Dual a) { return {a.v, 0.0}; }
-
-struct D3 {
-  Dual x, y, z;
-};
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 operator*(double s, D3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ D3 dcross(D3 a, D3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ D3 dmatvec(const double (&A)[9], D3 x) {
-  return {A[0] * x.x + A[1] * x.y + A[2] * x.z, A[3] * x.x + A[4] * x.y + A[5] * x.z, A[6] * x.x + A[7] * x.y + A[8] * x.z};
-}
-struct DMat {
-  Dual m[9];
-};
-__device__ __forceinline__ D3 rot(const DMat& R, D3 x) {
-  return {R.m[0] * x.x + R.m[1] * x.y + R.m[2] * x.z, R.m[3] * x.x + R.m[4] * x.y + R.m[5] * x.z,
-          R.m[6] * x.x + R.m[7] * x.y + R.m[8] * x.z};
-}
-__device__ __forceinline__ D3 rot_t(const DMat& R, D3 x) {
-  return {R.m[0] * x.x + R.m[3] * x.y + R.m[6] * x.z, R.m[1] * x.x + R.m[4] * x.y + R.m[7] * x.z,
-          R.m[2] * x.x + R.m[5] * x.y + R.m[8] * x.z};
-}
-
-// the point map on dual numbers: in[47] = [y(19), yh(19), zh(6), tf(3)], out[25] = [y_s(19), z(6)]
-__device__ __forceinline__ void point_map_dual(const RodConst<double>& P, const Dual (&in)[47], bool cut, Dual (&out)[25]) {
-  const Dual a = in[3], b = in[4], c = in[5], e = in[6];
-  const D3 n{in[7], in[8], in[9]}, m{in[10], in[11], in[12]}, q{in[13], in[14], in[15]}, w{in[16], in[17], in[18]};
-  const D3 yh_q{in[19 + 13], in[19 + 14], in[19 + 15]}, yh_w{in[19 + 16], in[19 + 17], in[19 + 18]};
-  const D3 vh{in[38], in[39], in[40]}, uh{in[41], in[42], in[43]};
-  const D3 tf{in[44], in[45], in[46]};
-  // R = I + (2 / h.h) quad(h); cut: the entries of quad(h) are leaves
-  const Dual aq = cut ? detach(a) : a, bq = cut ? detach(b) : b, cq = cut ? detach(c) : c, eq = cut ? detach(e) : e;
-  const Dual s = 2.0 * dual_rcp(a * a + b * b + c * c + e * e);
-  DMat R;
-  R.m[0] = s * (-(cq * cq) - eq * eq) + 1.0; R.m[1] = s * (bq * cq - eq * aq);        R.m[2] = s * (bq * eq + cq * aq);
-  R.m[3] = s * (bq * cq + eq * aq);          R.m[4] = s * (-(bq * bq) - eq * eq) + 1.0; R.m[5] = s * (cq * eq - bq * aq);
-  R.m[6] = s * (bq * eq - cq * aq);          R.m[7] = s * (cq * eq + bq * aq);        R.m[8] = s * (-(bq * bq) - cq * cq) + 1.0;
-  const D3 ksv{{P.Kse_vstar[0], 0.0}, {P.Kse_vstar[1], 0.0}, {P.Kse_vstar[2], 0.0}};
-  const D3 v = dmatvec(P.Ksei, rot_t(R, n) + ksv - dmatvec(P.Bse, vh));
-  const D3 u = dmatvec(P.Kbti, rot_t(R, m) - dmatvec(P.Bbt, uh));
-  const D3 qt = P.c0 * q + yh_q, wt = P.c0 * w + yh_w, vt = P.c0 * v + vh, ut = P.c0 * u + uh;
-  const D3 drag{P.C[0] * (q.x * dual_abs(q.x)), P.C[1] * (q.y * dual_abs(q.y)), P.C[2] * (q.z * dual_abs(q.z))};
-  const D3 rag{{P.rhoAg[0], 0.0}, {P.rhoAg[1], 0.0}, {P.rhoAg[2], 0.0}};
-  const D3 load = rag - rot(R, drag) + tf;
-  const D3 ps = rot(R, v);
-  const D3 ns = P.rhoA * rot(R, dcross(w, q) + qt) - load;
-  const D3 ms = rot(R, dcross(w, dmatvec(P.rhoJ, w)) + dmatvec(P.rhoJ, wt)) - dcross(ps, n);
-  const D3 qs = vt - dcross(u, q) + dcross(w, v);
-  const D3 ws = ut - dcross(u, w);
-  // h_s = 0.5 Omega(u) h; cut: the entries of Omega(u) are leaves
-  const Dual u0 = cut ? detach(u.x) : u.x, u1 = cut ? detach(u.y) : u.y, u2 = cut ? detach(u.z) : u.z;
-  out[0] = ps.x; out[1] = ps.y; out[2] = ps.z;
-  out[3] = 0.5 * (-(u0 * b) - u1 * c - u2 * e);
-  out[4] = 0.5 * (u0 * a + u2 * c - u1 * e);
-  out[5] = 0.5 * (u1 * a - u2 * b + u0 * e);
-  out[6] = 0.5 * (u2 * a + u1 * b - u0 * c);
-  out[7] = ns.x; out[8] = ns.y; out[9] = ns.z;
-  out[10] = ms.x; out[11] = ms.y; out[12] = ms.z;
-  out[13] = qs.x; out[14] = qs.y; out[15] = qs.z;
-  out[16] = ws.x; out[17] = ws.y; out[18] = ws.z;
-  out[19] = v.x; out[20] = v.y; out[21] = v.z;
-  out[22] = u.x; out[23] = u.y; out[24] = u.z;
-}
 
 template <typename T>
 struct VjpArgs {

@@ -152,6 +152,8 @@ _PROTOS = {
     "kr_fastdtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_pose_mse_batch": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
     "kr_pose_mse_points_batch": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
+    "kr_step_vjp_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "kr_simulate_vjp_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -686,6 +688,50 @@ class Handle:
         else:  # (a bank's networks are on: no use_nn)
             rc = lib.kr_simulate_batch_bank(h, table._t, bank._b, idx_p, *head, *mid, *end)
         check(rc)
+
+    # -- gradients -----------------------------------------------------------------
+    def step_vjp(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, use_nn=False, need_bnd=True):
+        """Adjoint of one solved step (``kr_step_vjp_batch``): the cotangent ``g_next[B, N, KR_SLOTS]`` of ``nxt`` ->
+        dict with ``g_cur``, ``g_prev`` ``[B, N, KR_SLOTS]``, ``g_tensions[B, 4]``, ``g_bnd[B, KR_BND]`` (None without
+        ``need_bnd``), ``resid[B]`` (float64) and ``status[B]`` (int32), all on the device.  ``prev`` may be ``cur``."""
+        import torch
+        B = cur.shape[0]
+        for name, t in (("prev", prev), ("cur", cur), ("nxt", nxt), ("g_next", g_next)):
+            if tuple(t.shape) != (B, self.N, KR_SLOTS) or t.dtype != cur.dtype:
+                raise KrError(f"step_vjp: {name} must be [{B}, {self.N}, {KR_SLOTS}] of {cur.dtype}; got {tuple(t.shape)} {t.dtype}")
+        if tuple(tensions.shape) != (B, 4) or tensions.dtype != cur.dtype:
+            raise KrError(f"step_vjp: tensions must be [{B}, 4] of {cur.dtype}; got {tuple(tensions.shape)} {tensions.dtype}")
+        new = lambda *shape, dtype=cur.dtype: torch.empty(shape, dtype=dtype, device=cur.device)
+        out = dict(g_cur=new(B, self.N, KR_SLOTS), g_prev=new(B, self.N, KR_SLOTS), g_tensions=new(B, 4),
+                   g_bnd=new(B, KR_BND) if need_bnd else None, resid=new(B, dtype=torch.float64), status=new(B, dtype=torch.int32))
+        check(self.lib.kr_step_vjp_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
+                                         _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
+                                         _ptr(out["resid"]), _ptr(out["status"]), int(bool(use_nn)), dtype_code(cur.dtype), _stream()))
+        return out
+
+    def simulate_vjp(self, ctl, states, g_states, prev_init=None, scheme=KR_EULER, use_nn=False, need_bnd=True):
+        """Backward pass over a stored rollout (``kr_simulate_vjp_batch``): ``ctl[B, T, 4]``, the full history
+        ``states[T + 1, B, N, KR_SLOTS]`` of the forward call (not a ring) and ``g_states`` of the same shape, in/out: the
+        direct dL/dstates on entry, the total adjoint on return.  Returns dict with ``g_ctl[B, T, 4]``, ``g_bnd[B, KR_BND]``
+        (None without ``need_bnd``), ``g_prev_init`` (None unless ``prev_init`` is given), ``resid[B, T]``, ``status[B, T]``."""
+        import torch
+        if ctl.dim() != 3 or ctl.shape[2] != 4 or ctl.shape[1] < 1:
+            raise KrError(f"simulate_vjp: ctl must be [B, T, 4] with T >= 1; got {tuple(ctl.shape)}")
+        B, T = ctl.shape[0], ctl.shape[1]
+        for name, t in (("states", states), ("g_states", g_states)):
+            if tuple(t.shape) != (T + 1, B, self.N, KR_SLOTS) or t.dtype != ctl.dtype:
+                raise KrError(f"simulate_vjp: {name} must be the full history [{T + 1}, {B}, {self.N}, {KR_SLOTS}] of {ctl.dtype} (a "
+                              f"ring of three states does not hold what the backward pass reads); got {tuple(t.shape)} {t.dtype}")
+        if prev_init is not None and (tuple(prev_init.shape) != (B, self.N, KR_SLOTS) or prev_init.dtype != ctl.dtype):
+            raise KrError(f"simulate_vjp: prev_init must be [{B}, {self.N}, {KR_SLOTS}] of {ctl.dtype}")
+        new = lambda *shape, dtype=ctl.dtype: torch.empty(shape, dtype=dtype, device=ctl.device)
+        out = dict(g_ctl=new(B, T, 4), g_bnd=new(B, KR_BND) if need_bnd else None,
+                   g_prev_init=new(B, self.N, KR_SLOTS) if prev_init is not None else None,
+                   resid=new(B, T, dtype=torch.float64), status=new(B, T, dtype=torch.int32))
+        check(self.lib.kr_simulate_vjp_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
+                                             _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["resid"]),
+                                             _ptr(out["status"]), int(bool(use_nn)), dtype_code(ctl.dtype), _stream()))
+        return out
 
     # -- evaluation metrics ------------------------------------------------------
     def dtw(self, a, b, out=None):
