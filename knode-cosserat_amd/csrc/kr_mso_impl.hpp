@@ -46,6 +46,22 @@ constexpr int MSO_LAG = KR_MSO_LAG;
 // the next grid point in front of the verifying lanes' store block, so no read waits for a store of its own trip.  The
 // merged-sweep ticks of the stamped build of it (make dbg DBGFLAGS="-DKR_MS_STAMPS -DKR_MSO_PROBE_EARLY_READS") are the
 // most that hiding the tile round trip can give (LABBOOK, "merged trip").
+// -DKR_MSO_PROBE_NO_TILE_STORES, -DKR_MSO_PROBE_ONE_TILE_STORE (compile-time probes, TIMING ONLY - the results are wrong):
+// the verifying lanes of a full trip leave their tile store out, or store the first 16 bytes of the 96, so the
+// forward-difference lanes read leading slots that are two time levels old (finite values; the event counts of a sine
+// run stay what they are).  What the merged-sweep ticks of the stamped builds lose is what the store block costs a
+// trip, and what one store of it costs (LABBOOK, "what a merged trip waits for": 200 ticks, 27 per store).
+// -DKR_MSO_TRIP_WAITS=0 (a compile-time probe; same results): the tile reads value by value, a counted wait per read.
+// -DKR_MSO_TRIP_CARRY=1 (a compile-time probe; same results): the scale 2 / h.h of a trip's rotation is formed behind
+// the Euler update of the trip before and carried in a register (rot_scale / ode_eval_s, rod_device.hpp), so that no
+// trip opens with that serial chain.  Measured: 0.4 k ticks per step off the merged sweep on its own, 0.35 k ON it
+// beside the one-wait reads, which take 0.88 k off alone - the two do not add, and the reads are what is built.
+#ifndef KR_MSO_TRIP_WAITS
+#define KR_MSO_TRIP_WAITS 1
+#endif
+#ifndef KR_MSO_TRIP_CARRY
+#define KR_MSO_TRIP_CARRY 0
+#endif
 static_assert(MSO_B0 + MS_P <= WAVE, "the verifying lanes must fit beside the forward-difference lanes");
 
 template <typename T, int HS>
@@ -66,6 +82,8 @@ __device__ __forceinline__ void wave_sync_lds() {
 // parity of a time level, and behind such a select the compiler no longer proves the address space: it fell back to
 // flat_load / flat_store (24 + 12 per pair of trips) until the accesses said so themselves.
 #define KR_LDS __attribute__((address_space(3)))
+// sched_barrier mask: everything may be scheduled across but LDS accesses (bits 7..9: all DS, DS read, DS write)
+#define KR_SCHED_ALL_BUT_DS 0x047f
 template <typename T, int NV>
 __device__ __forceinline__ void lds_load_vec(const T* src, T (&v)[NV]) {
   using V = typename Vec16<T>::type;
@@ -91,6 +109,36 @@ __device__ __forceinline__ void lds_store_vec(T* dst, const T (&v)[NV]) {
 #pragma unroll
     for (int e = 0; e < n; ++e) x[e] = v[c * n + e];
     d[c] = x;
+  }
+}
+
+// The twelve leading slots of one grid point as the 16-byte tuples the LDS reads deliver (six in fp64).
+// Read value by value, every pair of products that consumes one read gets a counted wait of its own - a staircase
+// lgkmcnt(5) .. (0) that hides nothing when the reads went out fifty instructions earlier and only takes issue slots
+// from a lone wavefront.  lead_pin() names all tuples of a tile in one empty asm in front of their first use: one wait.
+template <typename T>
+struct LeadTile {
+  using V = typename Vec16<T>::type;
+  static constexpr int NT = 12 / Vec16<T>::n;
+  V t[NT];
+};
+template <typename T>
+__device__ __forceinline__ void lds_load_lead(const T* src, LeadTile<T>& x) {
+  using V = typename Vec16<T>::type;
+  const KR_LDS V* s = (const KR_LDS V*)src;
+#pragma unroll
+  for (int c = 0; c < LeadTile<T>::NT; ++c) x.t[c] = s[c];
+}
+__device__ __forceinline__ void lead_pin(LeadTile<double>& x) {
+  asm volatile("" : "+v"(x.t[0]), "+v"(x.t[1]), "+v"(x.t[2]), "+v"(x.t[3]), "+v"(x.t[4]), "+v"(x.t[5]));
+}
+template <typename T>
+__device__ __forceinline__ void lead_unpack(const LeadTile<T>& x, T (&v)[12]) {
+  constexpr int n = Vec16<T>::n;
+#pragma unroll
+  for (int c = 0; c < LeadTile<T>::NT; ++c) {
+#pragma unroll
+    for (int e = 0; e < n; ++e) v[c * n + e] = x.t[c][e];
   }
 }
 
@@ -527,6 +575,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       // In a predicated trip past a lane's interval the clamped older read is that of the slot the lane has just written,
       // taken before the store: such a lane's record feeds an evaluation that is multiplied by dsl = 0.
       T* const lead_w = lead_of(tB + 1);               // the tile the verifying lanes write: state tB + 1 over state tB - 1
+#if KR_MSO_TRIP_CARRY
+      // (probe) 2 / h.h of the state the coming evaluation sees (behind the forward-difference perturbation), carried from trip to trip
+      T rs = rot_scale(y.h0, y.h1, y.h2, y.h3);
+#endif
       auto trip = [&](int k, auto full_tag, auto lean_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
         constexpr bool LEAN = decltype(lean_tag)::value;  // (FULL trips: the loop exists once per value; others test `lean`)
@@ -536,7 +588,20 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         const int eo = j * 12;                                       // elements in front of grid point j in a tile
         const int en = FULL ? eo + 12 : point_of(k + 1) * 12;  // ... of the grid point of the next trip
         T la[12], lb[12], pb[12];
-        if constexpr (MSO_LAG >= 2) {
+        // (one wait per tile in the fp64 kernels.  fp32 keeps the value-by-value reads: its staircase is three steps, and
+        //  with the pins the fp32 headline call measured 0.7 % SLOWER in every one of three rounds, 52.9 against 53.3 M)
+#ifdef KR_MSO_PROBE_EARLY_READS
+        constexpr bool TUPLES = false;
+#else
+        constexpr bool TUPLES = KR_MSO_TRIP_WAITS && MSO_LAG < 2 && OCC == 1 && sizeof(T) == 8;
+#endif
+        LeadTile<T> ta, tb;
+        if constexpr (TUPLES) {
+          lds_load_lead<T>(lead_o + en, tb);
+          // (the reads stay at the head of the trip: behind a pin alone the scheduler sinks them to four instructions in
+          //  front of their wait.  Only LDS accesses are held - a full barrier here cost 0.3 k ticks per step of the 0.9 k.)
+          __builtin_amdgcn_sched_barrier(KR_SCHED_ALL_BUT_DS);
+        } else if constexpr (MSO_LAG >= 2) {
           // what the next trip reads was written a trip ago - requested now, under the arithmetic of this one
           lds_load_vec<T, 12>(lead_n + en, la);
           lds_load_vec<T, 12>(lead_o + en, lb);
@@ -550,7 +615,11 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         }
         RodState<T> k1;
         V3<T> v, u;
+#if KR_MSO_TRIP_CARRY
+        ode_eval_s<T, DIAG>(Pc, y, hst, fc, k1, v, u, rs);
+#else
         ode_eval<T, DIAG>(Pc, y, hst, fc, k1, v, u);
+#endif
         // (formed in front of the verifying lanes' block: behind it the wait for the reads would also wait for its stores)
         if constexpr (MSO_LAG >= 2) {
           hst = hist_form(la, lb);
@@ -560,6 +629,13 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           asm volatile("" : "+v"(hst.av.x), "+v"(hst.av.y), "+v"(hst.av.z), "+v"(hst.au.x), "+v"(hst.au.y), "+v"(hst.au.z));
         } else {
           // (pinned: the products - and the wait for the older tile - stay in front of the block)
+          if constexpr (TUPLES) {
+            // (the one wait comes where the asm stands.  v and u need nothing from the tile: named in front of it they
+            //  are finished under the reads, which keeps the cover of the last read what the staircase's first step had)
+            asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(u.x), "v"(u.y), "v"(u.z));
+            lead_pin(tb);
+            lead_unpack<T>(tb, lb);
+          }
           hist_older(lb, pb);
           asm volatile("" : "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]), "+v"(pb[4]), "+v"(pb[5]), "+v"(pb[6]), "+v"(pb[7]),
                             "+v"(pb[8]), "+v"(pb[9]), "+v"(pb[10]), "+v"(pb[11]));
@@ -594,6 +670,17 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           // tile's: no read of the next trip waits behind it)
           //  (a live verifying lane is at grid point j = s_l + kk, 0 <= kk < len_l <= 32)
           if constexpr (KP) store_keypoint_window(kp_out, kp_marks, kp_rank0, kk, rec);
+#ifdef KR_MSO_PROBE_NO_TILE_STORES
+          if constexpr (!FULL)  // TIMING PROBE, results are wrong
+#endif
+#ifdef KR_MSO_PROBE_ONE_TILE_STORE
+          if constexpr (FULL) {  // TIMING PROBE, results are wrong
+            T l2[Vec16<T>::n];
+#pragma unroll
+            for (int c = 0; c < Vec16<T>::n; ++c) l2[c] = lead[c];
+            lds_store_vec<T, Vec16<T>::n>(lead_w + eo, l2);
+          } else
+#endif
           lds_store_vec<T, 12>(lead_w + eo, lead);
         }
         // history record of the next trip.  A forward-difference lane reads the leading slots a verifying lane wrote
@@ -603,7 +690,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #ifdef KR_MSO_PROBE_EARLY_READS
           if constexpr (!FULL)
 #endif
-          lds_load_vec<T, 12>(lead_n + en, la);
+          {
+            if constexpr (TUPLES) lds_load_lead<T>(lead_n + en, ta);
+            else lds_load_vec<T, 12>(lead_n + en, la);
+          }
           // (the reads stay right behind the block: left alone, the scheduler sinks them to ~20 instructions in front of
           //  their first use.  Two wavefronts per SIMD hide that themselves, and the barrier costs them scratch.)
           if constexpr (OCC == 1) __builtin_amdgcn_sched_barrier(0);
@@ -617,6 +707,15 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           asm volatile("" : "+v"(pb[0]), "+v"(pb[1]), "+v"(pb[2]), "+v"(pb[3]), "+v"(pb[4]), "+v"(pb[5]), "+v"(pb[6]), "+v"(pb[7]),
                             "+v"(pb[8]), "+v"(pb[9]), "+v"(pb[10]), "+v"(pb[11]), "+v"(y.p.z), "+v"(y.h3), "+v"(y.n.z), "+v"(y.m.z),
                             "+v"(y.q.z), "+v"(y.w.z));
+#if KR_MSO_TRIP_CARRY
+          // (probe) the scale of the next evaluation's rotation, from the state that evaluation will see (a predicated
+          // trip's dsl = 0 has left y as it was): its serial chain issues under the record forming below
+          rs = rot_scale(y.h0, y.h1, y.h2, y.h3);
+#endif
+          if constexpr (TUPLES) {
+            lead_pin(ta);
+            lead_unpack<T>(ta, la);
+          }
           hst = hist_newest(la, pb);
         }
       };

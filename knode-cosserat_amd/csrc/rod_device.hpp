@@ -261,10 +261,16 @@ struct Rot {
   }
 };
 
+// (the scale s = 2 / h.h apart from the entries: it is the one serial chain of the rotation - four products, the
+// estimate, two Newton steps, the doubling - and a caller that knows the quaternion of its next evaluation early can
+// form it there, under other work, and hand it to ode_eval_s)
 template <typename T>
-__device__ __forceinline__ Rot<T> make_rot(T a, T b, T c, T d) {
+__device__ __forceinline__ T rot_scale(T a, T b, T c, T d) {
+  return T(2) * fast_rcp(fma(a, a, fma(b, b, fma(c, c, d * d))));
+}
+template <typename T>
+__device__ __forceinline__ Rot<T> make_rot_s(T a, T b, T c, T d, T s) {
   Rot<T> R;
-  const T s = T(2) * fast_rcp(fma(a, a, fma(b, b, fma(c, c, d * d))));
   const T sb = s * b, sc = s * c, sd = s * d;
   R.r00 = fma(-sc, c, fma(-sd, d, T(1)));
   R.r01 = fma(sb, c, -sd * a);
@@ -277,6 +283,10 @@ __device__ __forceinline__ Rot<T> make_rot(T a, T b, T c, T d) {
   R.r22 = fma(-sb, b, fma(-sc, c, T(1)));
   return R;
 }
+template <typename T>
+__device__ __forceinline__ Rot<T> make_rot(T a, T b, T c, T d) {
+  return make_rot_s(a, b, c, d, rot_scale(a, b, c, d));
+}
 
 // a x b + c and c - a x b with the products fused
 template <typename T>
@@ -288,11 +298,11 @@ __device__ __forceinline__ V3<T> cross_sub(V3<T> c, V3<T> a, V3<T> b) {
   return {fma(-a.y, b.z, fma(a.z, b.y, c.x)), fma(-a.z, b.x, fma(a.x, b.z, c.y)), fma(-a.x, b.y, fma(a.y, b.x, c.z))};
 }
 
-// ys (same struct as the state) and z = [v u]; fconst = rhoA*g + tendon force.
+// ys (same struct as the state) and z = [v u]; fconst = rhoA*g + tendon force.  s: rot_scale of y's quaternion.
 template <typename T, bool DIAG>
-__device__ __forceinline__ void ode_eval(const RodConst<T>& P, const RodState<T>& y, const RodHist<T>& hst,
-                                         V3<T> fconst, RodState<T>& ys, V3<T>& v, V3<T>& u) {
-  const Rot<T> R = make_rot(y.h0, y.h1, y.h2, y.h3);
+__device__ __forceinline__ void ode_eval_s(const RodConst<T>& P, const RodState<T>& y, const RodHist<T>& hst,
+                                           V3<T> fconst, RodState<T>& ys, V3<T>& v, V3<T>& u, T s) {
+  const Rot<T> R = make_rot_s(y.h0, y.h1, y.h2, y.h3, s);
 
   // solved constitutive law, cosserat_ode.py:140-141
   V3<T> Rtn = R.applyT(y.n);
@@ -323,6 +333,11 @@ __device__ __forceinline__ void ode_eval(const RodConst<T>& P, const RodState<T>
   ys.h1 = fma(hu.x, y.h0, fma(hu.z, y.h2, -hu.y * y.h3));
   ys.h2 = fma(hu.y, y.h0, fma(-hu.z, y.h1, hu.x * y.h3));
   ys.h3 = fma(hu.z, y.h0, fma(hu.y, y.h1, -hu.x * y.h2));
+}
+template <typename T, bool DIAG>
+__device__ __forceinline__ void ode_eval(const RodConst<T>& P, const RodState<T>& y, const RodHist<T>& hst,
+                                         V3<T> fconst, RodState<T>& ys, V3<T>& v, V3<T>& u) {
+  ode_eval_s<T, DIAG>(P, y, hst, fconst, ys, v, u, rot_scale(y.h0, y.h1, y.h2, y.h3));
 }
 
 // y + a*k  (Euler update / RK stage argument)
