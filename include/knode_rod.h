@@ -140,6 +140,10 @@ int kr_destroy(kr_handle* h);
  *                    form of kr_simulate_batch only (Euler sweeps, a network the matrix-core evaluator serves).
  *                    "last_waves_per_rod" / "last_sim_path" (read-only) tell what the last call ran.
  *   "mlp_grad_accumulate" 0 (default) / 1: see kr_adam_step
+ *   "mlp_grad_ordered" 0 (default) / 1: kr_mlp_backward adds up its per-workgroup partial gradients in a fixed order by
+ *     plain stores instead of float atomics: the gradient is then bit for bit the same in every call on the same inputs
+ *     (the default's 32 adders per parameter arrive in any order).  Needs a network the fused training kernels serve
+ *     (KR_E_UNSUPPORTED otherwise: nothing falls back to the atomics).  krod_grad.weight_grads sets it for its calls.
  *   "keep_predictor" 0 (default) / 1: kr_simulate_batch leaves the state of its start-value predictor behind
  *                    and the next call with the same batch size resumes from it - for a simulation that is
  *                    advanced by several calls, each continuing where the previous one stopped
@@ -195,13 +199,34 @@ int kr_derive(const kr_params* p, kr_derived* out);
  * dims[n_layers+1]; W[k] is row-major [dims[k+1]][dims[k]] float32 (the dtype
  * the reference trains and stores), b[k] is [dims[k+1]]; acts[k] is applied
  * after layer k.  src_on_device: 0 = host pointers, 1 = device pointers.
- * The library keeps its own packed copies.  n_layers = 0 switches the MLP off. */
+ * The library keeps its own packed copies.  n_layers = 0 switches the MLP off.
+ * Lifetime of the sources: host sources (src_on_device = 0) are copied before the call returns.  Device sources
+ * (src_on_device = 1) are NOT: the call records their addresses and one pack launch on `stream` reads them, so every W[k]
+ * and b[k] must stay valid and unmodified until `stream` has reached that launch - free or overwrite them only by work
+ * ordered after it on the same stream (or after synchronising with it).  A caller that pushes live training weights every
+ * iteration (krod_grad.simulate_tips_nn) runs the optimizer step on the stream it gave here. */
 int kr_set_mlp(kr_handle* h, int n_layers, const int32_t* dims, const int32_t* acts,
                const float* const* W, const float* const* b, int src_on_device, void* stream);
 
 /* CosseratRod.get_nn_output (cosserat_ode.py:90-112) on Q rows:
  * x[Q][dims[0]] -> out[Q][25], row-major, f32 or f64 arithmetic. */
 int kr_mlp_eval_batch(kr_handle* h, int64_t Q, const void* x, void* out, int dtype, void* stream);
+
+/* The input Jacobian of the residual MLP (CosseratRod.get_nn_output, cosserat_ode.py:90-112; the network enters the point
+ * map as (y_s, z) = f_phys + NN(x), x = [y (19), z_phys (6), tf (3)], cosserat_ode.py:178-184; differentiating the solved
+ * step of knode.py:70-100 through it needs dNN/dx at every stored grid point): x[Q][28] -> jac[Q][25][28], row-major,
+ * jac[q][o][i] = d NN_o / d x_i at row q.  The chain W3 diag(act'(a2)) W2 diag(act'(a1)) W1 (one hidden layer: W2
+ * diag(act'(a1)) W1) is formed on the fp64 matrix cores with the weights in LDS; pre-activations, activation derivatives
+ * (tanh, softplus, relu, elu, none) and products are fp64 whatever `dtype`, which is the element type of x and jac only.
+ * Shapes served: 28 -> H -> 25 with H <= 512 and 28 -> H1 -> H2 -> 25 with H1, H2 <= 64, any widths in range (padded with
+ * zero weights), no activation on the last layer, nn_input_history = 0.
+ * One launch, no workspace of the handle, no atomics: a row's result does not depend on the batch it rides in.  A value
+ * of x that is not finite (NaN or an infinity) is ordinary input: every entry of that row comes back NaN, the call
+ * returns KR_OK.
+ * Refusals, each with a message, nothing launched and no output byte written: KR_E_STATE without a network (kr_set_mlp);
+ * KR_E_UNSUPPORTED for nn_input_history = 1, a shape outside the two families or an activation on the last layer -
+ * nothing falls back to another evaluator; KR_E_ARG for a null handle, x or jac, Q < 1, a bad dtype. */
+int kr_mlp_input_jacobian_batch(kr_handle* h, int64_t Q, const void* x, void* jac, int dtype, void* stream);
 
 /* ---- batched per-segment derivative ----------------------------------- */
 /* CosseratRodTorch.ODE_parallel (cosserat_ode_torch.py:217-322) and, row by
@@ -857,6 +882,41 @@ int kr_step_vjp_batch(kr_handle* h, int64_t B, int scheme,
 int kr_simulate_vjp_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
                           const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
                           double* resid, int32_t* status, int use_nn, int dtype, void* stream);
+
+/* ---- the adjoint with the residual MLP on ---------------------------------------------------------------------------------
+ * kr_step_vjp_batch for the KNODE model, physics plus network in every sweep (knode.py:70-100 with the point map of
+ * cosserat_ode.py:178-184 inside the sweep of cosserat_ode.py:188-213): (y_s, z) = f_phys(y, hist, tf) + NN(x),
+ * x = [y (19), z_phys (6), tf (3)].  With Jn[25][28] = dNN/dx at the stored point (kr_mlp_input_jacobian_batch) the point
+ * Jacobian of the recursion stated at kr_step_vjp_batch becomes J = Jp + Jn X, X = [identity on the y columns; rows 19..24
+ * of Jp, the z_phys tangents; identity on the tf columns]; pass 1, the 6 x 6 solve, pass 2 and every output are as there.
+ * Arguments: those of kr_step_vjp_batch without use_nn (the network is the handle's, kr_set_mlp), plus two nullable
+ * outputs nn_x[B][N-1][32], nn_g[B][N-1][32] of the arrays' element type: row (b, j) holds the network's input x_j
+ * (28 values, then zeros) and the cotangent that reaches its output at point j, c_j = [ds lambda_{j+1} (19); g_z[j] (6)]
+ * (25 values, then zeros), lambda the total adjoint.  The gradient of the loss with respect to the network's weights is
+ * the ordinary MLP backward pass over these rows (kr_mlp_forward + kr_mlp_backward), summed over points, rods and steps.
+ * Three launches (the rows x, their Jacobians on the fp64 matrix cores, the recursion with one wavefront per rod); the
+ * handle's scratch holds x and Jn: B (N-1) (32 + 700) doubles, 0.6 GB at B = 1024, N = 100.  Arithmetic is fp64 whatever
+ * `dtype`; the KR_F32 call is the KR_F64 call on the upcast inputs, rounded, bit for bit.  A rod's outputs do not depend
+ * on the batch it rides in.  status as for kr_step_vjp_batch, with the rod's x and Jn among the values read: a rod with
+ * a nonzero status gets NaN gradients and NaN in its nn_g rows (its nn_x rows keep the inputs), every other rod's
+ * outputs are bit for bit those of the clean call.
+ * Refusals, each with a message, nothing launched and no output byte written: KR_E_STATE without a network;
+ * KR_E_UNSUPPORTED for scheme == KR_RK4, nn_input_history = 1, a network outside the shapes of
+ * kr_mlp_input_jacobian_batch or with an activation on its last layer; KR_E_ARG for a null handle, state, g_next or
+ * tensions pointer, B < 1, a bad dtype. */
+int kr_step_vjp_nn_batch(kr_handle* h, int64_t B, int scheme,
+                         const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
+                         const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd,
+                         double* resid, int32_t* status, void* nn_x, void* nn_g, int dtype, void* stream);
+
+/* kr_simulate_vjp_batch for the KNODE model (knode.py:55-102 with the step of knode.py:70-100 and the sweep of
+ * cosserat_ode.py:188-213, network on, cosserat_ode.py:178-184): DEFINED as the same composition of kr_step_vjp_nn_batch
+ * calls and equal to it bit for bit; per step it launches the rows, the Jacobians, the recursion and the accumulations.
+ * nn_x, nn_g[T][B][N-1][32] (nullable): the rows of step t.  Scratch: two state-sized buffers and the step call's.
+ * Refusals as for kr_step_vjp_nn_batch, and KR_E_ARG for T < 1 or a null ctl, states or g_states. */
+int kr_simulate_vjp_nn_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
+                             const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
+                             double* resid, int32_t* status, void* nn_x, void* nn_g, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

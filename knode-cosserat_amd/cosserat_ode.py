@@ -129,15 +129,17 @@ class CosseratRod:
         self.rhoAg = np.array(d.rhoAg, dtype=np.float64)
         self.rhoJ = m3(d.rhoJ)
 
-    def _native(self) -> kn.Handle:
-        """Device handle carrying the current parameters (and MLP, if any)."""
+    def _native(self, push_mlp=True) -> kn.Handle:
+        """Device handle carrying the current parameters (and MLP, if any).  ``push_mlp=False``: the caller sets the
+        handle's network itself (krod_grad pushes live training weights from the device) and leaves ``_mlp_key`` None, so
+        the next plain call packs the robot's own weights again."""
         p = self._params()
         if self._handle is None:
             self._handle = kn.Handle(p, self.device)
             self._mlp_key = None
         else:
             self._handle.set_params(p)
-        if self.nn_path is not None:
+        if self.nn_path is not None and push_mlp:
             self._push_mlp(self.nn_model, self.param_ls)
         return self._handle
 

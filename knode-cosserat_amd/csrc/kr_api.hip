@@ -456,6 +456,8 @@ int kr_set_option(kr_handle* h, const char* name, int value) {
     h->waves_per_rod = value;
   } else if (n == "mlp_grad_accumulate") {
     h->grad_accumulate = value ? 1 : 0;
+  } else if (n == "mlp_grad_ordered") {
+    h->grad_ordered = value ? 1 : 0;
   } else if (n == "keep_predictor") {
     h->keep_predictor = value ? 1 : 0;
     if (!value) h->pred_valid_B = 0;
@@ -493,6 +495,7 @@ int kr_get_option(kr_handle* h, const char* name, int* value) {
   else if (n == "persistent") *value = h->persistent;
   else if (n == "keep_predictor") *value = h->keep_predictor;
   else if (n == "mlp_grad_accumulate") *value = h->grad_accumulate;
+  else if (n == "mlp_grad_ordered") *value = h->grad_ordered;
   else if (n == "mfma_mlp") *value = h->mfma_mlp;
   else if (n == "fused_mlp") *value = h->fused_mlp;
   else if (n == "predictor") *value = h->predictor;

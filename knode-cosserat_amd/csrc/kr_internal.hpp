@@ -71,6 +71,7 @@ struct kr_handle {
   void* ws = nullptr;
   void* pred_buf = nullptr;   // predictor images of the one-launch-per-step multiple-shooting path
   size_t pred_bytes = 0;
+  int grad_ordered = 0;       // kr_mlp_backward sums its partial gradients in a fixed order, without atomics (option "mlp_grad_ordered")
   int grad_accumulate = 0;    // kr_mlp_backward / kr_loss_rows_fwd_bwd add to dW, db, loss instead of zeroing them first
   int keep_predictor = 0;     // kr_simulate_batch resumes from / leaves behind the predictor image (option)
   int64_t pred_valid_B = 0;   // batch size the image in pred_buf was written for (0: none)
@@ -472,6 +473,7 @@ int fused_mlp_forward(int64_t Q, int n_layers, const int32_t* dims, const int32_
                       const float* const* b, const float* x, float* out, void* ws, hipStream_t s,
                       const FusedLoss* fl = nullptr, bool do_pack = true, int* n_partials = nullptr);
 // leave != nullptr: no reduction launch - the slabs of partial gradients are described there (dW, db unused)
+// ordered: the slab sum in a fixed order, without atomics (option "mlp_grad_ordered": reduce_slabs_ordered_kernel)
 struct FusedSlabs {
   const float* slab;
   int nslab, P, nparams;
@@ -479,7 +481,7 @@ struct FusedSlabs {
 };
 int fused_mlp_backward(int64_t Q, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* W,
                        const float* x, const float* dout, void* ws, float* const* dW, float* const* db, hipStream_t s,
-                       FusedSlabs* leave = nullptr);
+                       FusedSlabs* leave = nullptr, bool ordered = false);
 // kr_train_epoch: flat parameter / gradient / moment vectors in nn.Linear order (W1, b1, W2, b2, ...), g with one
 // trailing loss slot
 struct FusedEpoch {
@@ -504,6 +506,13 @@ struct FusedEpoch {
 };
 int fused_train_epoch(const FusedEpoch& E, hipStream_t s);
 void fused_set_debug(void* dev_u64x48);  // diagnostic build: where the fused kernels add their phase stamps
+
+// kr_nnjac.hip: the MLP's input Jacobian on the fp64 matrix cores.  nnjac_check: the refusals of a call that needs it
+// (no network: KR_E_STATE; a shape or input it does not serve: KR_E_UNSUPPORTED), message prefixed with `api`.
+// launch_nnjac: rows x (x_stride elements apart) -> jac[Q][700], transposed ? [28][25] : [25][28]
+int nnjac_check(const kr_handle* h, const char* api);
+template <typename T>
+int launch_nnjac(kr_handle* h, int64_t Q, const T* x, int64_t x_stride, T* jac, int transposed, hipStream_t s);
 
 // kr_ode.hip
 template <typename T>

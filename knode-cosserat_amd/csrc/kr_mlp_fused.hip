@@ -1132,6 +1132,29 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const FusedArgs A) {
   atomicAdd(&dst[i - A.poff[seg]], sum);
 }
 
+// The same sum without atomics, for callers that need the gradient bit for bit the same in every call (option
+// "mlp_grad_ordered"): ONE thread per parameter adds the slabs 0, 1, 2, ... in that order (four interleaved partial sums,
+// joined in a fixed tree) and adds the result to dW / db with a plain store.  The slabs themselves are written once per
+// workgroup in a fixed order, so the whole gradient is a function of its inputs alone.
+__global__ __launch_bounds__(256) void reduce_slabs_ordered_kernel(const FusedArgs A) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.nparams) return;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  int w = 0;
+  for (; w + 3 < A.nslab; w += 4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] += A.slab[(size_t)(w + e) * A.P + i];
+  }
+  for (int e = 0; w < A.nslab; ++w, ++e) acc[e] += A.slab[(size_t)w * A.P + i];
+  const float sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  int seg = 5;
+#pragma unroll
+  for (int k = 4; k >= 0; --k)
+    if (i < A.poff[k + 1]) seg = k;
+  float* dst = (seg & 1) ? A.db[seg >> 1] : A.dW[seg >> 1];
+  dst[i - A.poff[seg]] += sum;
+}
+
 // ---- tail of an epoch: slab sum + loss sum + Adam + clamp + plateau schedule + fragment update, ONE launch ----------
 // (physics_train.py:289-304: optimizer.step(), scheduler.step(total_loss), the weight clamp.)  A workgroup owns 64
 // consecutive parameters and does everything for them - no workgroup waits for another, no atomics, and the order of
@@ -1438,7 +1461,7 @@ int fused_mlp_forward(int64_t Q, int n_layers, const int32_t* dims, const int32_
 
 int fused_mlp_backward(int64_t Q, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* W,
                        const float* x, const float* dout, void* ws, float* const* dW, float* const* db,
-                       hipStream_t s, FusedSlabs* leave) {
+                       hipStream_t s, FusedSlabs* leave, bool ordered) {
   FusedArgs A{};
   A.Q = Q; A.x = x; A.dout = dout;
   if (!leave)
@@ -1509,7 +1532,10 @@ int fused_mlp_backward(int64_t Q, int n_layers, const int32_t* dims, const int32
     KR_HIP(hipGetLastError());
     return KR_OK;
   }
-  hipLaunchKernelGGL(reduce_slabs_kernel, dim3((P + 255) / 256, RG), dim3(256), 0, s, A);
+  if (ordered)
+    hipLaunchKernelGGL(reduce_slabs_ordered_kernel, dim3((P + 255) / 256), dim3(256), 0, s, A);
+  else
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((P + 255) / 256, RG), dim3(256), 0, s, A);
   KR_HIP(hipGetLastError());
   return KR_OK;
 }

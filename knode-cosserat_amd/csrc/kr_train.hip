@@ -534,7 +534,13 @@ int kr_mlp_backward(kr_handle* h, int64_t Q, int n_layers, const int32_t* dims, 
   KR_CHECK_PTR(x); KR_CHECK_PTR(dout);
   if (n_layers > 1) KR_CHECK_PTR(ws);
   if (acts[n_layers - 1] == KR_ACT_NONE && h->fused_mlp && fused_mlp_supported(n_layers, dims, acts, in_pad))
-    return fused_mlp_backward(Q, n_layers, dims, acts, W, x, dout, const_cast<void*>(ws), dW, db, s);
+    return fused_mlp_backward(Q, n_layers, dims, acts, W, x, dout, const_cast<void*>(ws), dW, db, s, nullptr, h->grad_ordered != 0);
+  if (h->grad_ordered) {  // (the library GEMMs below split the row sum and join it with float atomics)
+    set_error("kr_mlp_backward: option mlp_grad_ordered needs a network the fused training kernels serve (two or three layers, at "
+              "most 32 inputs and outputs, three layers: H1, H2 <= 64 with one activation; option fused_mlp on, in_pad 32); "
+              "nothing falls back to the sum with atomics");
+    return KR_E_UNSUPPORTED;
+  }
   MlpWs w = carve_ws(const_cast<void*>(ws), n_layers, dims, Q);
   const float* dz = dout;  // d loss / d (pre-activation of layer k); the last layer has no activation
   int64_t ld_dz = 32;

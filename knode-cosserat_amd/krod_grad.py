@@ -8,8 +8,11 @@ d(tension history) costs about one forward rollout instead of 4 T + 1 of them by
 * ``rollout_grad(robot, ctl, states, ...)``: the backward pass for given cotangents.
 * ``simulate_tips(robot, ctl)``: a ``torch.autograd.Function`` - ``tips[B, T, 3]`` connected to ``ctl``, so that
   ``loss.backward()`` fills ``ctl.grad``.
+* ``rollout_grad_nn`` / ``simulate_tips_nn``: the same for the KNODE model, physics plus the residual MLP in every sweep
+  (``kr_simulate_vjp_nn_batch``) - and the gradient of a rollout loss with respect to the network's weights, which the
+  reference never had (it trains one step ahead, physics_train.py:250-259).
 
-MLP off, Euler sweeps, the handle's parameters; anything else is refused by the library (no fall-back).  The adjoint is
+Euler sweeps, the handle's parameters; anything else is refused by the library (no fall-back).  The adjoint is
 that of the EXACT root of the shooting equations: solve the forward pass tightly (``tol = 1e-12``, the default of
 ``simulate_tips``) - the distance to the root enters the gradient at first order."""
 from __future__ import annotations
@@ -31,7 +34,7 @@ def _tdt(dtype):
 def _check_robot(robot):
     if getattr(robot, "_use_nn", False):
         raise kn.KrError("krod_grad: the adjoint with the MLP on is not served (kr_step_vjp_batch); nothing falls back to the "
-                         "physics alone")
+                         "physics alone - rollout_grad_nn / simulate_tips_nn differentiate the model with its network")
 
 
 def _check_ctl(ctl):
@@ -41,16 +44,16 @@ def _check_ctl(ctl):
     return shape[0], shape[1]
 
 
-def forward_states(h, ctl_t, tol=1e-12, maxit=0, prev_init=None):
+def forward_states(h, ctl_t, tol=1e-12, maxit=0, prev_init=None, use_nn=False):
     """The full history ``states[T + 1, B, N, KR_SLOTS]`` of a run from the straight rod - what the backward pass
-    reads.  Returns (states, tip, status)."""
+    reads (``use_nn``: with the handle's MLP in every sweep).  Returns (states, tip, status)."""
     B, T = ctl_t.shape[0], ctl_t.shape[1]
     states = h.new_state(B, ctl_t.dtype, n_slots=T + 1)
     h.init_straight(states[0])
     G = torch.zeros((B, 6), dtype=ctl_t.dtype, device=ctl_t.device)
     tip = torch.empty((B, T, 3), dtype=ctl_t.dtype, device=ctl_t.device)
     status = torch.zeros((B, T), dtype=torch.int32, device=ctl_t.device)
-    h.simulate(ctl_t, states, G, ring=False, tip=tip, status=status, tol=tol, maxit=maxit, prev_init=prev_init)
+    h.simulate(ctl_t, states, G, ring=False, tip=tip, status=status, tol=tol, maxit=maxit, prev_init=prev_init, use_nn=use_nn)
     return states, tip, status
 
 
@@ -119,3 +122,168 @@ def simulate_tips(robot, ctl, dtype="f64", tol=1e-12):
         raise kn.KrError("simulate_tips: ctl must be a torch tensor (it is the leaf the gradient is connected to)")
     _check_ctl(ctl)
     return _SimulateTips.apply(ctl, robot, _tdt(dtype), float(tol))
+
+
+# ---- the KNODE model: physics plus the residual MLP in every sweep ----------------------------------------------------------
+ROWS_PER_CHUNK = 1 << 20  # rows of one kr_mlp_forward + kr_mlp_backward pair (whole steps; more: "mlp_grad_accumulate")
+
+
+def _check_robot_nn(robot, who):
+    if not getattr(robot, "_use_nn", False):
+        raise kn.KrError(f"{who}: the robot has no MLP on (rollout_grad / simulate_tips differentiate the physics alone)")
+
+
+def _check_params(params, who):
+    """the network's tensors in nn.Linear order W1 [out, in], b1, W2, b2, ... -> number of layers"""
+    params = list(params)
+    if len(params) < 4 or len(params) % 2:
+        raise kn.KrError(f"{who}: params must be the network's tensors W1, b1, W2, b2, ... (nn.Linear order); got {len(params)}")
+    for k in range(0, len(params), 2):
+        W, b = params[k], params[k + 1]
+        if not (isinstance(W, torch.Tensor) and isinstance(b, torch.Tensor)) or W.dim() != 2 or tuple(b.shape) != (W.shape[0],):
+            raise kn.KrError(f"{who}: params[{k}], params[{k + 1}] must be torch tensors W [out, in], b [out]")
+        if k and W.shape[1] != params[k - 2].shape[0]:
+            raise kn.KrError(f"{who}: params[{k}] takes {W.shape[1]} inputs, the layer before gives {params[k - 2].shape[0]}")
+    return len(params) // 2
+
+
+def _acts_of(robot):
+    from cosserat_ode import mlp_from_layer_strings
+    return [int(a) for a in mlp_from_layer_strings(robot.nn_model, robot.param_ls)[2]]
+
+
+def _push_params(robot, h, params, who):
+    """params -> the handle's network (kr_set_mlp with device sources on the current stream).  Returns the float32 device
+    copies, which the caller keeps alive: the sources must stay valid and unmodified until the stream reaches the pack
+    launch, and every later use here is on that same stream."""
+    acts = _acts_of(robot)
+    if len(acts) != len(params) // 2:
+        raise kn.KrError(f"{who}: the robot's network has {len(acts)} layers, params describe {len(params) // 2}")
+    dev = f"cuda:{h.device}"
+    p32 = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
+    h.set_mlp_device(p32[0::2], p32[1::2], acts)
+    robot._mlp_key = None  # (the handle no longer holds the robot's own weights: the next _native() packs them again)
+    return p32, acts
+
+
+def weight_grads(h, p32, acts, nn_x, nn_g):
+    """dL/d(W, b) from the rows the backward pass emitted (``nn_x``, ``nn_g`` ``[T, B, N - 1, 32]``): the ordinary MLP
+    backward pass over (x, c), by kr_mlp_forward + kr_mlp_backward in fp32, in chunks of whole steps added up by the library
+    (option "mlp_grad_accumulate").  Two identical calls give identical bits at any row count: the calls run with the option
+    "mlp_grad_ordered", under which kr_mlp_backward adds up its per-workgroup partial gradients in a fixed order instead of
+    with float atomics (a network the fused training kernels do not serve - three layers with two different activations -
+    is refused by it, not summed in arbitrary order).  A rod with a nonzero status has NaN rows, and the sum over rods is
+    then NaN."""
+    import ctypes as C
+    n = len(acts)
+    Ws, bs = p32[0::2], p32[1::2]
+    dims = [Ws[0].shape[1]] + [w.shape[0] for w in Ws]
+    dims_c, acts_c = (C.c_int32 * (n + 1))(*dims), (C.c_int32 * n)(*acts)
+    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in Ws])
+    bp = (C.c_void_p * n)(*[b.data_ptr() for b in bs])
+    dW = [torch.zeros_like(w) for w in Ws]
+    db = [torch.zeros_like(b) for b in bs]
+    dWp = (C.c_void_p * n)(*[w.data_ptr() for w in dW])
+    dbp = (C.c_void_p * n)(*[b.data_ptr() for b in db])
+    T, rows_per_step = nn_x.shape[0], nn_x.shape[1] * nn_x.shape[2]
+    steps = max(1, ROWS_PER_CHUNK // rows_per_step)
+    was, was_ordered = h.get_option("mlp_grad_accumulate"), h.get_option("mlp_grad_ordered")
+    h.set_option("mlp_grad_accumulate", 1)
+    h.set_option("mlp_grad_ordered", 1)
+    try:
+        for t0 in range(0, T, steps):
+            x = nn_x[t0:t0 + steps].reshape(-1, 32).float().contiguous()
+            g = nn_g[t0:t0 + steps].reshape(-1, 32).float().contiguous()
+            Q = x.shape[0]
+            ws = torch.empty(max(h.lib.kr_mlp_ws_bytes(n, dims_c, Q), 16), dtype=torch.uint8, device=x.device)
+            out = torch.empty((Q, 32), dtype=torch.float32, device=x.device)
+            kn.check(h.lib.kr_mlp_forward(h._h, Q, n, dims_c, acts_c, Wp, bp, kn._ptr(x), 32, kn._ptr(out), kn._ptr(ws), kn._stream()))
+            kn.check(h.lib.kr_mlp_backward(h._h, Q, n, dims_c, acts_c, Wp, kn._ptr(x), 32, kn._ptr(g), kn._ptr(ws), dWp, dbp,
+                                           kn._stream()))
+    finally:
+        h.set_option("mlp_grad_accumulate", was)
+        h.set_option("mlp_grad_ordered", was_ordered)
+    grads = []
+    for a, b in zip(dW, db):
+        grads += [a, b]
+    return grads
+
+
+def rollout_grad_nn(robot, ctl, states, g_states=None, g_tips=None, prev_init=None, dtype="f64", params=None):
+    """``rollout_grad`` for a robot with its MLP on (``kr_simulate_vjp_nn_batch``): the same arguments and the same dict.
+    ``params`` (the network's tensors in nn.Linear order, the weights the stored rollout was run with): they are pushed
+    into the handle first, and the dict also holds ``params``, the list of host arrays dL/dW1, dL/db1, ... summed over
+    grid points, rods and steps (``weight_grads``).  Without ``params`` the network is the robot's own."""
+    _check_robot_nn(robot, "rollout_grad_nn")
+    B, T = _check_ctl(ctl)
+    if g_states is None and g_tips is None:
+        raise kn.KrError("rollout_grad_nn: give g_states and / or g_tips (a loss has to enter somewhere)")
+    if tuple(states.shape)[0] != T + 1:
+        raise kn.KrError(f"rollout_grad_nn: states must be the full history [{T + 1}, {B}, N, {kn.KR_SLOTS}] of the forward call, not "
+                         f"a ring; got {tuple(states.shape)}")
+    if g_tips is not None and tuple(g_tips.shape) != (B, T, 3):
+        raise kn.KrError(f"rollout_grad_nn: g_tips must be [{B}, {T}, 3]; got {tuple(g_tips.shape)}")
+    if params is not None:
+        _check_params(params, "rollout_grad_nn")
+    h = robot._native(push_mlp=params is None)  # (params: pushed from the device below, no host pack of the robot's own)
+    tdt, dev = _tdt(dtype), f"cuda:{h.device}"
+    to_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=tdt).contiguous()
+    if params is not None:
+        p32, acts = _push_params(robot, h, list(params), "rollout_grad_nn")
+    ctl_t, states_t = to_dev(ctl), to_dev(states)
+    g = to_dev(g_states).clone() if g_states is not None else torch.zeros_like(states_t)
+    if g_tips is not None:
+        g[1:, :, h.N - 1, 12:15] += to_dev(g_tips).permute(1, 0, 2)
+    out = h.simulate_vjp_nn(ctl_t, states_t, g, prev_init=to_dev(prev_init) if prev_init is not None else None,
+                            need_rows=params is not None)
+    res = {"ctl": out["g_ctl"].cpu().numpy(), "states": g.cpu().numpy(), "boundary": out["g_bnd"].cpu().numpy(),
+           "resid": out["resid"].cpu().numpy(), "status": out["status"].cpu().numpy()}
+    if prev_init is not None:
+        res["prev_init"] = out["g_prev_init"].cpu().numpy()
+    if params is not None:
+        res["params"] = [t.cpu().numpy() for t in weight_grads(h, p32, acts, out["nn_x"], out["nn_g"])]
+    return res
+
+
+class _SimulateTipsNn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, robot, tdt, tol, *params):
+        import warnings
+        h = robot._native(push_mlp=False)  # (no host pack of the robot's own weights: the live ones go in from the device)
+        dev = f"cuda:{h.device}"
+        p32, acts = _push_params(robot, h, list(params), "simulate_tips_nn")
+        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
+        states, tip, status = forward_states(h, ctl_t, tol=tol, use_nn=True)
+        bad = int((status != 0).sum())
+        if bad:  # (the adjoint is that of the exact root: say so, as knode.simulate does, instead of handing back a gradient in silence)
+            warnings.warn(f"simulate_tips_nn: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the gradient of "
+                          "those rods is not that of the solved step", RuntimeWarning)
+        ctx.robot, ctx.h, ctx.ctl_t, ctx.states, ctx.p32, ctx.acts = robot, h, ctl_t, states, p32, acts
+        ctx.like, ctx.plike = ctl, params
+        return tip.to(device=ctl.device, dtype=ctl.dtype)
+
+    @staticmethod
+    def backward(ctx, g_tips):
+        h, states = ctx.h, ctx.states
+        h.set_mlp_device(ctx.p32[0::2], ctx.p32[1::2], ctx.acts)  # (the handle may have served another network since)
+        ctx.robot._mlp_key = None  # (... and the robot must not believe its own weights are still the handle's)
+        g = torch.zeros_like(states)
+        g[1:, :, h.N - 1, 12:15] = g_tips.to(device=states.device, dtype=states.dtype).permute(1, 0, 2)
+        out = h.simulate_vjp_nn(ctx.ctl_t, states, g, need_bnd=False)
+        grads = weight_grads(h, ctx.p32, ctx.acts, out["nn_x"], out["nn_g"])
+        return (out["g_ctl"].to(device=ctx.like.device, dtype=ctx.like.dtype), None, None, None,
+                *[a.to(device=p.device, dtype=p.dtype) for a, p in zip(grads, ctx.plike)])
+
+
+def simulate_tips_nn(robot, ctl, params, dtype="f64", tol=1e-12):
+    """``simulate_tips`` for a robot with its MLP on: ``tips[B, T, 3]`` connected to ``ctl`` AND to ``params``, the network's
+    tensors in nn.Linear order - ``simulate_tips_nn(robot, ctl, params).sum().backward()`` fills ``ctl.grad`` and every
+    ``p.grad`` (one ``kr_simulate_vjp_nn_batch``, then the MLP backward pass over the rows it emits).  The forward pushes
+    ``params`` into the handle (``kr_set_mlp`` with device sources, on the stream everything else here runs on); the robot
+    supplies the architecture (its activations) and the rod."""
+    _check_robot_nn(robot, "simulate_tips_nn")
+    if not isinstance(ctl, torch.Tensor):
+        raise kn.KrError("simulate_tips_nn: ctl must be a torch tensor (it is a leaf the gradient is connected to)")
+    _check_ctl(ctl)
+    _check_params(params, "simulate_tips_nn")
+    return _SimulateTipsNn.apply(ctl, robot, _tdt(dtype), float(tol), *params)

@@ -29,6 +29,7 @@ KR_FASTDTW_MAX_LEN, KR_FASTDTW_MAX_RADIUS = 1024, 8  # kr_fastdtw_batch: samples
 KR_BND = 19  # p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) per rod and step (kr_simulate_batch_boundary)
 KR_KEYPOINTS_MAX = 16  # key points per call (kr_simulate_batch_keypoints)
 KR_E_ARG, KR_E_UNSUPPORTED = -1, -4
+KR_E_HIP, KR_E_STATE = -2, -3
 
 # reference row (0..24 of [y; z]) -> packed slot, see knode_rod.h
 ROW_TO_SLOT = np.array([12 + r for r in range(13)] + [r - 13 for r in range(13, 19)] + [6 + (r - 19) for r in range(19, 25)])
@@ -85,6 +86,7 @@ _PROTOS = {
     "kr_get_derived": (_int, [_vp, C.POINTER(KrDerived)]),
     "kr_derive": (_int, [C.POINTER(KrParams), C.POINTER(KrDerived)]),
     "kr_mlp_eval_batch": (_int, [_vp, _i64, _vp, _vp, _int, _vp]),
+    "kr_mlp_input_jacobian_batch": (_int, [_vp, _i64, _vp, _vp, _int, _vp]),
     "kr_set_mlp": (_int, [_vp, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(_vp), _int, _vp]),
     "kr_ode_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "kr_ode_vjp_batch": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp]),
@@ -152,6 +154,8 @@ _PROTOS = {
     "kr_fastdtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_pose_mse_batch": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
     "kr_pose_mse_points_batch": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
+    "kr_step_vjp_nn_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "kr_simulate_vjp_nn_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_step_vjp_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "kr_simulate_vjp_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
 }
@@ -501,6 +505,25 @@ class Handle:
         bp = (_vp * n)(*[b.ctypes.data for b in bs])
         check(self.lib.kr_set_mlp(self._h, n, dims, acts_c, Wp, bp, 0, _stream()))
 
+    def set_mlp_device(self, weights, biases, acts):
+        """``set_mlp`` from float32 CUDA tensors (``kr_set_mlp`` with device sources, packed by one launch on the current
+        stream).  The sources must stay valid and unmodified until that stream reaches the pack launch: keep the tensors
+        alive and write to them on the same stream only."""
+        import torch
+        n = len(weights)
+        for k in range(n):
+            for t in (weights[k], biases[k]):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise KrError(f"set_mlp_device: layer {k}: contiguous float32 CUDA tensors are needed")
+        dims = (C.c_int32 * (n + 1))(*([weights[0].shape[1]] + [w.shape[0] for w in weights]))
+        for k in range(n):
+            if weights[k].dim() != 2 or weights[k].shape[1] != dims[k] or tuple(biases[k].shape) != (dims[k + 1],):
+                raise KrError(f"MLP layer {k}: inconsistent shapes {tuple(weights[k].shape)} / {tuple(biases[k].shape)}")
+        acts_c = (C.c_int32 * n)(*[int(a) for a in acts])
+        Wp = (_vp * n)(*[w.data_ptr() for w in weights])
+        bp = (_vp * n)(*[b.data_ptr() for b in biases])
+        check(self.lib.kr_set_mlp(self._h, n, dims, acts_c, Wp, bp, 1, _stream()))
+
     # -- kernels -------------------------------------------------------------
     def ode_batch(self, y, yh, zh, tf, use_nn=False):
         import torch
@@ -606,6 +629,17 @@ class Handle:
         out = torch.empty((Q, 25), dtype=x.dtype, device=x.device)
         check(self.lib.kr_mlp_eval_batch(self._h, Q, _ptr(x), _ptr(out), dtype_code(x.dtype), _stream()))
         return out
+
+    def mlp_input_jacobian(self, x):
+        """``jac[Q, 25, 28]`` = dNN/dx of the handle's MLP at the rows ``x[Q, 28]`` (``kr_mlp_input_jacobian_batch``): fp64
+        arithmetic on the matrix cores whatever the dtype of ``x``, which is that of the result."""
+        import torch
+        if x.dim() != 2 or x.shape[1] != 28 or x.shape[0] < 1:
+            raise KrError(f"mlp_input_jacobian: x must be [Q, 28] with Q >= 1; got {tuple(x.shape)}")
+        x = x.contiguous()
+        jac = torch.empty((x.shape[0], 25, 28), dtype=x.dtype, device=x.device)
+        check(self.lib.kr_mlp_input_jacobian_batch(self._h, x.shape[0], _ptr(x), _ptr(jac), dtype_code(x.dtype), _stream()))
+        return jac
 
     def step(self, prev, cur, nxt, G, tensions, scheme=KR_EULER, tol=0.0, maxit=0, status=None, iters=None,
              use_nn=False, prev2=None, predictor=-1):
@@ -731,6 +765,51 @@ class Handle:
         check(self.lib.kr_simulate_vjp_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
                                              _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["resid"]),
                                              _ptr(out["status"]), int(bool(use_nn)), dtype_code(ctl.dtype), _stream()))
+        return out
+
+    def step_vjp_nn(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, need_bnd=True, need_rows=True):
+        """``step_vjp`` for the model with the handle's MLP on (``kr_step_vjp_nn_batch``): the same dict, plus ``nn_x``,
+        ``nn_g`` ``[B, N - 1, 32]`` (None without ``need_rows``) - the network's input at every stored point and the
+        cotangent that reaches its output there, the rows of the weight gradient."""
+        import torch
+        B = cur.shape[0]
+        for name, t in (("prev", prev), ("cur", cur), ("nxt", nxt), ("g_next", g_next)):
+            if tuple(t.shape) != (B, self.N, KR_SLOTS) or t.dtype != cur.dtype:
+                raise KrError(f"step_vjp_nn: {name} must be [{B}, {self.N}, {KR_SLOTS}] of {cur.dtype}; got {tuple(t.shape)} {t.dtype}")
+        if tuple(tensions.shape) != (B, 4) or tensions.dtype != cur.dtype:
+            raise KrError(f"step_vjp_nn: tensions must be [{B}, 4] of {cur.dtype}; got {tuple(tensions.shape)} {tensions.dtype}")
+        new = lambda *shape, dtype=cur.dtype: torch.empty(shape, dtype=dtype, device=cur.device)
+        out = dict(g_cur=new(B, self.N, KR_SLOTS), g_prev=new(B, self.N, KR_SLOTS), g_tensions=new(B, 4),
+                   g_bnd=new(B, KR_BND) if need_bnd else None, resid=new(B, dtype=torch.float64), status=new(B, dtype=torch.int32),
+                   nn_x=new(B, self.N - 1, 32) if need_rows else None, nn_g=new(B, self.N - 1, 32) if need_rows else None)
+        check(self.lib.kr_step_vjp_nn_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
+                                            _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
+                                            _ptr(out["resid"]), _ptr(out["status"]), _ptr(out["nn_x"]), _ptr(out["nn_g"]),
+                                            dtype_code(cur.dtype), _stream()))
+        return out
+
+    def simulate_vjp_nn(self, ctl, states, g_states, prev_init=None, scheme=KR_EULER, need_bnd=True, need_rows=True):
+        """``simulate_vjp`` for the model with the handle's MLP on (``kr_simulate_vjp_nn_batch``): the same dict, plus
+        ``nn_x``, ``nn_g`` ``[T, B, N - 1, 32]`` (None without ``need_rows``), the rows of the weight gradient per step."""
+        import torch
+        if ctl.dim() != 3 or ctl.shape[2] != 4 or ctl.shape[1] < 1:
+            raise KrError(f"simulate_vjp_nn: ctl must be [B, T, 4] with T >= 1; got {tuple(ctl.shape)}")
+        B, T = ctl.shape[0], ctl.shape[1]
+        for name, t in (("states", states), ("g_states", g_states)):
+            if tuple(t.shape) != (T + 1, B, self.N, KR_SLOTS) or t.dtype != ctl.dtype:
+                raise KrError(f"simulate_vjp_nn: {name} must be the full history [{T + 1}, {B}, {self.N}, {KR_SLOTS}] of {ctl.dtype} (a "
+                              f"ring of three states does not hold what the backward pass reads); got {tuple(t.shape)} {t.dtype}")
+        if prev_init is not None and (tuple(prev_init.shape) != (B, self.N, KR_SLOTS) or prev_init.dtype != ctl.dtype):
+            raise KrError(f"simulate_vjp_nn: prev_init must be [{B}, {self.N}, {KR_SLOTS}] of {ctl.dtype}")
+        new = lambda *shape, dtype=ctl.dtype: torch.empty(shape, dtype=dtype, device=ctl.device)
+        out = dict(g_ctl=new(B, T, 4), g_bnd=new(B, KR_BND) if need_bnd else None,
+                   g_prev_init=new(B, self.N, KR_SLOTS) if prev_init is not None else None,
+                   resid=new(B, T, dtype=torch.float64), status=new(B, T, dtype=torch.int32),
+                   nn_x=new(T, B, self.N - 1, 32) if need_rows else None, nn_g=new(T, B, self.N - 1, 32) if need_rows else None)
+        check(self.lib.kr_simulate_vjp_nn_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
+                                                _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["resid"]),
+                                                _ptr(out["status"]), _ptr(out["nn_x"]), _ptr(out["nn_g"]), dtype_code(ctl.dtype),
+                                                _stream()))
         return out
 
     # -- evaluation metrics ------------------------------------------------------
