@@ -173,6 +173,43 @@ __device__ __forceinline__ T quad_pick(int kp, T v0, T v1, T v2, T v3) {
   return v;
 }
 
+// wave_sum_f64 of K independent values, stage by stage: the K moves of a stage stand between a sum's addition and the
+// DPP move that reads it, where one sum after the other pays the wait states of every move.  Each sum keeps
+// wave_sum_f64's order of additions.
+template <int K>
+__device__ __forceinline__ void wave_sum_f64_staged(double (&v)[K]) {
+  auto stage = [&](auto ctrl) {
+    double o[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) o[k] = quad_xor<decltype(ctrl)::value>(v[k]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] += o[k];
+  };
+  stage(std::integral_constant<int, 0xB1>{});
+  stage(std::integral_constant<int, 0x4E>{});
+  stage(std::integral_constant<int, 0x141>{});  // row_half_mirror
+  stage(std::integral_constant<int, 0x140>{});  // row_mirror
+  int lo[K], hi[K];
+  double s[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const long long b = __double_as_longlong(v[k]);
+    lo[k] = (int)(b & 0xFFFFFFFFll);
+    hi[k] = (int)(b >> 32);
+    s[k] = 0.0;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int l = __builtin_amdgcn_readlane(lo[k], 16 * r), h = __builtin_amdgcn_readlane(hi[k], 16 * r);
+      s[k] += __longlong_as_double(((long long)h << 32) | (unsigned int)l);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = s[k];
+}
+
 // ms_pred_update for this kernel (every step it hands over has converged).  While the fitted recurrence is in use and
 // predicted the step to better than 1e-3 (ms_pred_update's poly_eval == false) no polynomial order is measured: every
 // em[p] is 3.0e38f there, the order-choice loop ends at nxt = pmax and eb = 3.0e38f.  That case is written out straight -
@@ -226,8 +263,12 @@ __device__ __forceinline__ void mso_pred_update(MsPred<T, NC>& Q, int order, int
         lp_accumulate<NC>(Sn, b, x, w);
       }
     }
+    if constexpr (sizeof(T) == 8) {
+      wave_sum_f64_staged(Sn);
+    } else {
 #pragma unroll
-    for (int k = 0; k < lp_nsum<NC>(); ++k) Sn[k] = wave_sum_f64(Sn[k]);
+      for (int k = 0; k < lp_nsum<NC>(); ++k) Sn[k] = wave_sum_f64(Sn[k]);
+    }
     double a[NC];
     if (lp_solve<NC>(Sn, a)) {
 #pragma unroll
@@ -301,6 +342,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   // key-point records (PSRC = RodTableBndKp<T>): pointer, K and the mask of the marked grid points are kernel arguments
   using KPSRC = rod_src_keypoints<T, PSRC>;
   constexpr bool KP = KPSRC::value;
+  // the forms of the step's ends that only the fp64 kernels at one wavefront per SIMD take (the others keep their text)
+  constexpr bool TRIM = OCC == 1 && sizeof(T) == 8 && MSO_LAG == 1;
   const unsigned long long kp_lo = KPSRC::lo(Pa), kp_hi = KPSRC::hi(Pa);
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * mso_lds_elems<T, HS>(N), N, true, false);
   T* const Es = L.Es;
@@ -580,13 +623,18 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       T rs = rot_scale(y.h0, y.h1, y.h2, y.h3);
 #endif
       auto trip = [&](int k, auto full_tag, auto lean_tag) __attribute__((always_inline)) {
-        constexpr bool FULL = decltype(full_tag)::value;
+        constexpr int FORM = decltype(full_tag)::value;  // 0: predicated, 1: FULL, 2: trip 0
+        constexpr bool FULL = FORM == 1;
+        constexpr bool FIRST = TRIM && FORM == 2;
         constexpr bool LEAN = decltype(lean_tag)::value;  // (FULL trips: the loop exists once per value; others test `lean`)
         const int kk = k - lag;
-        const bool live = FULL ? act : (act && kk >= 0 && kk < len_l);
-        const int j = FULL ? s_l + kk : point_of(k);
+        // (trip 0: no forward-difference lane is live - kk = -1 - and every lane stands at the start of its interval; the
+        //  verifying lanes move on to their second grid point, the others read the records of their first again: functions
+        //  of isB alone, not of the clamps)
+        const bool live = FIRST ? isB : FULL ? act : (act && kk >= 0 && kk < len_l);
+        const int j = FIRST ? s_l : FULL ? s_l + kk : point_of(k);
         const int eo = j * 12;                                       // elements in front of grid point j in a tile
-        const int en = FULL ? eo + 12 : point_of(k + 1) * 12;  // ... of the grid point of the next trip
+        const int en = FIRST ? (s_l + ((isB && len_l > 1) ? 1 : 0)) * 12 : FULL ? eo + 12 : point_of(k + 1) * 12;  // ... of the grid point of the next trip
         T la[12], lb[12], pb[12];
         // (one wait per tile in the fp64 kernels.  fp32 keeps the value-by-value reads: its staircase is three steps, and
         //  with the pins the fp32 headline call measured 0.7 % SLOWER in every one of three rounds, 52.9 against 53.3 M)
@@ -720,7 +768,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         }
       };
       int k = 0;
-      for (; k < MSO_LAG && k < trips; ++k) trip(k, std::false_type{}, std::false_type{});
+      for (; k < MSO_LAG && k < trips; ++k) trip(k, std::integral_constant<int, 2>{}, std::false_type{});
       // (the loop of full trips once for ring-lean steps and once for complete records: no test of `lean` inside a trip)
       // (two trips per pass written out: the pins are convergent operations, and a loop that holds one is not unrolled
       //  with a remainder by the compiler)
@@ -736,7 +784,20 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       };
       if (lean) full_trips(std::true_type{});
       else full_trips(std::false_type{});
-      for (; k < trips; ++k) trip(k, std::false_type{}, std::false_type{});
+      // The FINAL trip of a sweep that also runs step tA (k = lmax): no verifying lane is live (theirs ended a trip ago),
+      // nobody reads a record again in this sweep and hst is dead behind it - the evaluation and the Euler update of
+      // the forward-difference lanes whose interval has lmax segments, nothing else: no tile read, no record, no store
+      // block.  (Without step tA the last trip is the verifying lanes' own and stays the generic one.)
+      const bool own_final = TRIM && runA;
+      for (; k < trips - (own_final ? 1 : 0); ++k) trip(k, std::false_type{}, std::false_type{});
+      if (own_final) {
+        const bool live = isA && R.lmax - 1 < len_l;  // (kk = lmax - 1: the last segment of a longest interval)
+        RodState<T> k1;
+        V3<T> v, u;
+        ode_eval<T, DIAG>(Pc, y, hst, fc, k1, v, u);
+        const T dsl = live ? Pc.ds : T(0);
+        y = state_axpy(y, dsl, k1);
+      }
     }
 #ifdef KR_MS_STAMPS
     KR_STAMP_ADD(st.t_sweep, tq);
@@ -927,8 +988,11 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         dYb = XB + MS_YP * 8;
         T areg[MS_P - 1];
         areg[0] = EsB[0 * MS_YP + r] - XsB[1 * MS_YP + r];  // a_1 = c_0
-        if (kp == 0) ach[1 * MS_YP + r] = areg[0];
-        wave_sync_lds();
+        constexpr bool HOP = TRIM;
+        if constexpr (!HOP) {
+          if (kp == 0) ach[1 * MS_YP + r] = areg[0];
+          wave_sync_lds();
+        }
 #pragma unroll
         for (int g = 1; g < MS_P; ++g) {
           const int l0 = 7 + 17 * (g - 1);
@@ -936,7 +1000,10 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #pragma unroll
           for (int cc = 0; cc < 4; ++cc) {
             av[cc] = Es[(l0 + 1 + 4 * kp + cc) * MS_YP + r];
-            xv[cc] = ach[g * MS_YP + 3 + 4 * kp + cc];
+            // (the first hop: the lanes of step 1 form the elements of a_1 = c_0 they need themselves - the subtraction
+            //  above on the same operands - so that nothing goes through ach behind a fence)
+            if (HOP && g == 1) xv[cc] = EsB[0 * MS_YP + 3 + 4 * kp + cc] - XsB[1 * MS_YP + 3 + 4 * kp + cc];
+            else xv[cc] = ach[g * MS_YP + 3 + 4 * kp + cc];
           }
           const T e0 = EsB[g * MS_YP + r];
           const T ynext = g < MS_P - 1 ? XsB[(g + 1) * MS_YP + r] : T(0);
@@ -951,7 +1018,17 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           }
           wave_sync_lds();
         }
-        {
+        if constexpr (HOP) {
+          // d = T^-1 rt, one component per lane (lanes 0 .. 5; the others form component 0 again) and six broadcasts, as
+          // the Newton path hands out x6: 6 multiply-adds and 6 reads of T^-1 per lane where every lane had 36 of each.
+          // The chain of a component is the same, j ascending from zero.
+          const int di = ln < 6 ? ln : 0;
+          T acc = T(0);
+#pragma unroll
+          for (int j = 0; j < 6; ++j) acc = fma(L.Ti[di * 6 + j], rt[j], acc);
+          d[0] = lane_bcast<0>(acc); d[1] = lane_bcast<1>(acc); d[2] = lane_bcast<2>(acc);
+          d[3] = lane_bcast<3>(acc); d[4] = lane_bcast<4>(acc); d[5] = lane_bcast<5>(acc);
+        } else {
           T rtv[6];
 #pragma unroll
           for (int j = 0; j < 6; ++j) rtv[j] = rt[j];
