@@ -918,6 +918,47 @@ int kr_simulate_vjp_nn_batch(kr_handle* h, int64_t B, int64_t T, int scheme, con
                              const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
                              double* resid, int32_t* status, void* nn_x, void* nn_g, int dtype, void* stream);
 
+/* ---- the adjoint with the gradient of the rod's material parameters ----------------------------------------------------
+ * kr_step_vjp_batch (MLP off, Euler sweep, the handle's parameters, diagonal or full Bse / Bbt, any N >= 2, fp64
+ * arithmetic whatever `dtype`, one wavefront per rod, no atomics, a rod's outputs independent of the batch it rides in)
+ * with one more nullable output, g_par[B][KR_PAR]: the gradient with respect to the parameters kr_derive starts from,
+ * in the order and row-major layout of struct kr_params -
+ *   E [0], r [1], rho [2], L [3], vstar [4..6], g [7..9], Bse [10..18], Bbt [19..27], C [28..30], tendon_dirs [31..42]
+ * (del_t and N are not differentiated).  With lambda the total adjoint of the recursion stated at kr_step_vjp_batch (the
+ * sweep seeded with g plus nu on the tip's (n, m)) and c_j = [ds lambda_{j+1}; g_z[j]]:
+ *   g_par[k] = sum_{j = 0..N-2} c_j . d(y_s, z)_j / d theta_k  +  (d ds / d theta_k) sum_j lambda_{j+1} . y_s,j
+ * d(y_s, z)_j / d theta_k is the TOTAL derivative of the point map through kr_derive (G = E / 2.6, A = pi r^2, J ~ r^4,
+ * Kse, Kbt, the two inverses (K + c0 B)^-1, Kse vstar, rho A, rho A g, rho J) at fixed inputs; each of the nine entries of
+ * Bse and of Bbt is an independent variable (a symmetric parametrisation sums the two mirrored entries); d ds / d L =
+ * 1 / (N - 1) and zero for every other parameter; tendon_dirs enters tf = tensions @ tendon_dirs alone, so
+ * g_par[31 + 3 i + c] = tensions[i] * (the tendon-force cotangent)[c] - exactly zero for a tendon without tension.  No
+ * parameter enters the base state or the tip condition: the 6 x 6 solve and nu are those of kr_step_vjp_batch.
+ * Every other output is bit for bit that of kr_step_vjp_batch (use_nn = 0) on the same inputs - it is written by that
+ * call's kernel, launched first; a second launch repeats the recursion and writes g_par alone - and with g_par == NULL the
+ * call IS that call.  A rod with a nonzero status gets NaN in all KR_PAR values; every other rod's outputs
+ * are bit for bit those of the clean call.  The KR_F32 call is the KR_F64 call on the upcast inputs, rounded to float.
+ * Refusals as for kr_step_vjp_batch (KR_E_UNSUPPORTED for scheme == KR_RK4; KR_E_ARG for a null handle, state, g_next or
+ * tensions pointer, B < 1, a bad dtype), each with a message, nothing launched and no output byte written.
+ * Not served: the MLP-on form (kr_step_vjp_nn_batch has no g_par); per-rod parameters (table, loads, boundary, bank: every
+ * rod of a call shares the handle's parameters, and g_par is per rod only because the states are); RK4; del_t. */
+#define KR_PAR 43
+int kr_step_vjp_par_batch(kr_handle* h, int64_t B, int scheme,
+                          const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
+                          const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd, void* g_par,
+                          double* resid, int32_t* status, int dtype, void* stream);
+
+/* kr_simulate_vjp_batch (MLP off) with g_par[B][KR_PAR] (nullable): DEFINED as the same composition of
+ * kr_step_vjp_par_batch calls and equal to it bit for bit; g_par = the sum over the steps of the step's g_par, t = T-1
+ * first, from zero, in the element type of the arrays (the parameters are constant in time).  The initial state adds no
+ * parameter term: no step reads p of an earlier state (the only slots that scale with L), and v = e3 of the straight rod
+ * is a constant - the caller's states[0] is an input like any other, its gradient is g_states[0].  A rod whose step t0
+ * reports a nonzero status has NaN in all of its g_par.  With g_par == NULL the call IS kr_simulate_vjp_batch.
+ * Scratch: that call's plus B * KR_PAR values.  Refusals as for kr_step_vjp_par_batch, and KR_E_ARG for T < 1 or a null
+ * ctl, states or g_states. */
+int kr_simulate_vjp_par_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
+                              const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
+                              void* g_par, double* resid, int32_t* status, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

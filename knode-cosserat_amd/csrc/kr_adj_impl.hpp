@@ -1,6 +1,8 @@
 // kr_adj_impl.hpp - what the step adjoint's kernels share: the argument block, the lane helpers, the per-point tangents
-// of the physics on dual numbers, the 6 x 6 solve and the accumulation kernel of the rollout.  Used by kr_adj.hip (MLP off)
-// and kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative); the mapping is described in kr_adj.hip.
+// of the physics on dual numbers, the 6 x 6 solve, the composition over a stored
+// rollout and its accumulation kernel.  Used by kr_adj.hip (MLP off), kr_adj_par.hip (MLP off, with the gradient of the
+// material parameters) and kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative); the mapping is
+// described in kr_adj.hip.  The recursion of one rod, the body of both step kernels, is kr_adj_body.inc.
 #pragma once
 #include "kr_internal.hpp"
 #include "kr_point_dual.hpp"
@@ -123,6 +125,110 @@ __device__ __forceinline__ bool adj_solve6(const double (&m)[6][6], const double
   return ok;
 }
 
+// ---- the gradient of the material parameters (kr_adj_par.hip) ----
+// What the parameter kernel takes beside AdjArgs: the output and the parameters that kr_derive turns into the constants of
+// the point map (Bse, Bbt, C and c0 are in RodConst as they are).
+template <typename T>
+struct AdjPar {
+  T* g_par;  // [B][KR_PAR]
+  double E, r, rho, vstar[3], g[3];
+};
+constexpr int ADJ_PAR_LANE0 = 34;  // lane ADJ_PAR_LANE0 + k: direction k of E, r, rho, vstar[3], g[3], Bse[9], Bbt[9], C[3]
+constexpr int ADJ_PAR_DIRS = 30;
+
+// The constants the point map reads, as dual numbers (point_map_dual's PC)
+struct RodConstDual {
+  double c0;
+  Dual rhoA;
+  Dual Ksei[9], Kbti[9], Bse[9], Bbt[9], rhoJ[9];
+  Dual Kse_vstar[3], rhoAg[3], C[3];
+};
+
+// d(M^-1) = -M^-1 dM M^-1 with dM = diag(dk) + c0 sel (sel: the unit tangent of a B entry, or zero)
+__device__ __forceinline__ void adj_dinv3(const double (&Mi)[9], const double (&dk)[3], double c0, const double (&sel)[9], double (&o)[9]) {
+  double t[9];  // dM M^-1
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      double a = dk[i] * Mi[3 * i + j];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) a = fma(c0 * sel[3 * i + l], Mi[3 * l + j], a);
+      t[3 * i + j] = a;
+    }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[3 * i + j] = -(Mi[3 * i] * t[j] + Mi[3 * i + 1] * t[3 + j] + Mi[3 * i + 2] * t[6 + j]);
+}
+
+// The constants with their tangents along direction k (k outside 0..29: no tangent): the chain of kr_derive
+// (cosserat_ode.py:58-78) - G = E / 2.6, A = pi r^2, J = pi r^4 (1/4, 1/4, 1/2), Kse = (G A, G A, E A), Kbt = (E J, E J, G J),
+// the inverses of Kse + c0 Bse and Kbt + c0 Bbt, Kse vstar, rho A, rho A g, rho J.  The VALUES are those of P.
+template <typename T>
+__device__ __forceinline__ void adj_par_consts(const RodConst<double>& P, const AdjPar<T>& Q, int k, RodConstDual& D) {
+  const double pi = 3.14159265358979323846;
+  const double sE = k == 0 ? 1.0 : 0.0, sr = k == 1 ? 1.0 : 0.0, srho = k == 2 ? 1.0 : 0.0;
+  const double r2 = Q.r * Q.r, r3 = r2 * Q.r, r4 = r2 * r2;
+  const double A = pi * r2, G = Q.E / 2.6, dA = sr * 2.0 * pi * Q.r, dG = sE / 2.6;
+  const double J[3] = {pi * r4 / 4, pi * r4 / 4, pi * r4 / 2};
+  const double dJ[3] = {sr * pi * r3, sr * pi * r3, sr * 2.0 * pi * r3};
+  const double Kse[3] = {G * A, G * A, Q.E * A};
+  const double dKse[3] = {dG * A + G * dA, dG * A + G * dA, sE * A + Q.E * dA};
+  const double dKbt[3] = {sE * J[0] + Q.E * dJ[0], sE * J[1] + Q.E * dJ[1], dG * J[2] + G * dJ[2]};
+  double sBse[9], sBbt[9], dKsei[9], dKbti[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    sBse[e] = k == 9 + e ? 1.0 : 0.0;
+    sBbt[e] = k == 18 + e ? 1.0 : 0.0;
+  }
+  adj_dinv3(P.Ksei, dKse, P.c0, sBse, dKsei);
+  adj_dinv3(P.Kbti, dKbt, P.c0, sBbt, dKbti);
+  const double drhoA = srho * A + Q.rho * dA;
+  D.c0 = P.c0;
+  D.rhoA = {P.rhoA, drhoA};
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    D.Ksei[e] = {P.Ksei[e], dKsei[e]};
+    D.Kbti[e] = {P.Kbti[e], dKbti[e]};
+    D.Bse[e] = {P.Bse[e], sBse[e]};
+    D.Bbt[e] = {P.Bbt[e], sBbt[e]};
+    D.rhoJ[e] = {P.rhoJ[e], e % 4 == 0 ? srho * J[e / 4] + Q.rho * dJ[e / 4] : 0.0};
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    D.Kse_vstar[i] = {P.Kse_vstar[i], dKse[i] * Q.vstar[i] + (k == 3 + i ? Kse[i] : 0.0)};
+    D.rhoAg[i] = {P.rhoAg[i], drhoA * Q.g[i] + (k == 6 + i ? P.rhoA : 0.0)};
+    D.C[i] = {P.C[i], k == 27 + i ? 1.0 : 0.0};
+  }
+}
+
+// One grid point along a parameter direction: the tangents d[25] of (y_s, z) with the INPUTS held fixed and the constants
+// carrying the tangent, and the values val[25] of (y_s, z) themselves (what d ds / d L multiplies).
+template <typename T>
+__device__ __forceinline__ void adj_point_par(const RodConstDual& D, double c1, double c2, const AdjArgs<T>& A, int64_t rec,
+                                              const double (&tf)[3], double (&d)[25], double (&val)[25]) {
+  double in[47];  // (plain inputs: the tangent runs along the constants alone)
+  Dual out[25];
+  const T* y = A.next + rec * KR_SLOTS;
+  const T* c = A.cur + rec * KR_SLOTS;
+  const T* p = A.prev + rec * KR_SLOTS;
+#pragma unroll
+  for (int k = 0; k < 19; ++k) in[k] = (double)y[adj_yslot(k)];
+#pragma unroll
+  for (int k = 19; k < 32; ++k) in[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) in[32 + k] = c1 * (double)c[k] + c2 * (double)p[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) in[44 + k] = tf[k];
+  point_map_dual(D, in, false, out);
+#pragma unroll
+  for (int o = 0; o < 25; ++o) {
+    d[o] = out[o].d;
+    val[o] = out[o].v;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void adj_add_kernel(T* dst, const T* src, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,5 +242,58 @@ static int launch_add(T* dst, const T* src, int64_t n, hipStream_t s) {
   KR_HIP(hipGetLastError());
   return KR_OK;
 }
+
+int launch_step_vjp_plain(kr_handle* h, const AdjArgs<float>& A, hipStream_t s);   // (kr_adj.hip: step_vjp_kernel)
+int launch_step_vjp_plain(kr_handle* h, const AdjArgs<double>& A, hipStream_t s);
+
+// The backward pass over a stored rollout, DEFINED as this composition of step adjoints (t = T - 1 .. 0):
+//   step adjoint of (states[t - 1], states[t], states[t + 1], ctl[:, t]) with g_next = g_states[t + 1]
+//   g_states[t] += g_cur;  g_states[t - 1] += g_prev  (in this order, in the element type of the arrays)
+//   g_bnd += the step's, g_par += the step's (from zero, t = T - 1 first)
+// launch(h, A, w_par, s): one step adjoint, its parameter gradient into w_par[B][KR_PAR] (null when g_par is)
+template <typename T, typename Launch>
+static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T* ctl, const T* states, const T* prev_init, T* g_states,
+                              T* g_prev_init, T* g_ctl, T* g_bnd, T* g_par, double* resid, int32_t* status, hipStream_t s, Launch launch) {
+  const int64_t slot = B * h->params.N * KR_SLOTS;
+  const size_t bnd_off = (size_t)2 * slot * sizeof(T);
+  const size_t par_off = bnd_off + (size_t)B * KR_BND * sizeof(T);
+  if (int rc = ensure_ws(h, par_off + (g_par ? (size_t)B * KR_PAR * sizeof(T) : 0))) return rc;
+  T* w_cur = static_cast<T*>(h->ws);
+  T* w_prev = w_cur + slot;
+  T* w_bnd = w_prev + slot;
+  T* w_par = w_bnd + B * KR_BND;
+  if (g_bnd) KR_HIP(hipMemsetAsync(g_bnd, 0, (size_t)B * KR_BND * sizeof(T), s));
+  if (g_par) KR_HIP(hipMemsetAsync(g_par, 0, (size_t)B * KR_PAR * sizeof(T), s));
+  for (int64_t t = T_steps - 1; t >= 0; --t) {
+    const bool into_init = t == 0 && prev_init != nullptr;
+    AdjArgs<T> A{};
+    A.B = B;
+    A.prev = t > 0 ? states + (t - 1) * slot : (prev_init ? prev_init : states);
+    A.cur = states + t * slot;
+    A.next = states + (t + 1) * slot;
+    A.tens = ctl + t * 4;
+    A.tens_stride = T_steps * 4;
+    A.g_next = g_states + (t + 1) * slot;
+    A.g_cur = w_cur;
+    A.g_prev = into_init ? g_prev_init : w_prev;
+    A.g_tens = g_ctl ? g_ctl + t * 4 : nullptr;
+    A.g_tens_stride = T_steps * 4;
+    A.g_bnd = g_bnd ? w_bnd : nullptr;
+    A.resid = resid ? resid + t : nullptr;
+    A.status = status ? status + t : nullptr;
+    A.st_stride = T_steps;
+    if (int rc = launch(h, A, g_par ? w_par : nullptr, s)) return rc;
+    if (int rc = launch_add<T>(g_states + t * slot, w_cur, slot, s)) return rc;
+    if (!into_init)
+      if (int rc = launch_add<T>(g_states + (t > 0 ? t - 1 : 0) * slot, w_prev, slot, s)) return rc;
+    if (g_bnd)
+      if (int rc = launch_add<T>(g_bnd, w_bnd, B * KR_BND, s)) return rc;
+    if (g_par)
+      if (int rc = launch_add<T>(g_par, w_par, B * KR_PAR, s)) return rc;
+  }
+  return KR_OK;
+}
+
+int adj_refuse(const char* api, int scheme, int use_nn);  // (kr_adj.hip)
 
 }  // namespace kr

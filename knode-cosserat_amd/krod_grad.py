@@ -8,6 +8,9 @@ d(tension history) costs about one forward rollout instead of 4 T + 1 of them by
 * ``rollout_grad(robot, ctl, states, ...)``: the backward pass for given cotangents.
 * ``simulate_tips(robot, ctl)``: a ``torch.autograd.Function`` - ``tips[B, T, 3]`` connected to ``ctl``, so that
   ``loss.backward()`` fills ``ctl.grad``.
+* ``rollout_grad(..., physical=True)`` / ``simulate_tips_physical(robot, ctl, theta)``: also the gradient of the rod's
+  material parameters E, r, rho, L, vstar, g, Bse, Bbt, C, tendon_dirs (``kr_simulate_vjp_par_batch``) - what a calibration
+  of the rod against a recorded run needs, in place of 2 x 43 forward rollouts by finite differences.
 * ``rollout_grad_nn`` / ``simulate_tips_nn``: the same for the KNODE model, physics plus the residual MLP in every sweep
   (``kr_simulate_vjp_nn_batch``) - and the gradient of a rollout loss with respect to the network's weights, which the
   reference never had (it trains one step ahead, physics_train.py:250-259).
@@ -57,7 +60,7 @@ def forward_states(h, ctl_t, tol=1e-12, maxit=0, prev_init=None, use_nn=False):
     return states, tip, status
 
 
-def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None, dtype="f64"):
+def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None, dtype="f64", physical=False):
     """Backward pass over a stored rollout of ``robot`` (MLP off): ``ctl[B, T, 4]`` and the FULL history
     ``states[T + 1, B, N, KR_SLOTS]`` of the forward call (host arrays or device tensors; a ring of three states does not
     hold what is needed and is refused).  The loss enters through ``g_states[T + 1, B, N, KR_SLOTS]`` = dL/dstates and / or
@@ -67,7 +70,10 @@ def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None,
     Returns a dict of host arrays: ``ctl`` [B, T, 4] = dL/dctl; ``states`` [T + 1, B, N, KR_SLOTS] = the total adjoint of
     every stored state (entry 0: the gradient with respect to the initial condition); ``boundary`` [B, KR_BND] = dL/d(p0,
     h0, q0, w0, F_tip, M_tip); ``prev_init`` (with one given); ``resid`` [B, T], the relative residual of each step's
-    6 x 6 adjoint solve; ``status`` [B, T] (nonzero: that rod's gradients are NaN from that step back)."""
+    6 x 6 adjoint solve; ``status`` [B, T] (nonzero: that rod's gradients are NaN from that step back).
+    ``physical``: the dict also holds ``physical``, a dict of host arrays dL/d(material parameter) per rod, keyed ``E``,
+    ``r``, ``rho``, ``L`` [B], ``vstar``, ``g``, ``C`` [B, 3], ``Bse``, ``Bbt`` [B, 3, 3] (every entry an independent
+    variable), ``tendon_dirs`` [B, 4, 3] (``kr_simulate_vjp_par_batch``; a rod with a nonzero status has NaN in all)."""
     _check_robot(robot)
     B, T = _check_ctl(ctl)
     if g_states is None and g_tips is None:
@@ -84,11 +90,14 @@ def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None,
     g = to_dev(g_states).clone() if g_states is not None else torch.zeros_like(states_t)
     if g_tips is not None:
         g[1:, :, h.N - 1, 12:15] += to_dev(g_tips).permute(1, 0, 2)
-    out = h.simulate_vjp(ctl_t, states_t, g, prev_init=to_dev(prev_init) if prev_init is not None else None)
+    out = h.simulate_vjp(ctl_t, states_t, g, prev_init=to_dev(prev_init) if prev_init is not None else None,
+                         need_par=bool(physical))
     res = {"ctl": out["g_ctl"].cpu().numpy(), "states": g.cpu().numpy(), "boundary": out["g_bnd"].cpu().numpy(),
            "resid": out["resid"].cpu().numpy(), "status": out["status"].cpu().numpy()}
     if prev_init is not None:
         res["prev_init"] = out["g_prev_init"].cpu().numpy()
+    if physical:
+        res["physical"] = {k: np.ascontiguousarray(v) for k, v in kn.split_par(out["g_par"].cpu().numpy()).items()}
     return res
 
 
@@ -122,6 +131,77 @@ def simulate_tips(robot, ctl, dtype="f64", tol=1e-12):
         raise kn.KrError("simulate_tips: ctl must be a torch tensor (it is the leaf the gradient is connected to)")
     _check_ctl(ctl)
     return _SimulateTips.apply(ctl, robot, _tdt(dtype), float(tol))
+
+
+# ---- the rod's material parameters as leaves -----------------------------------------------------------------------------
+PHYSICAL_SHAPES = {name: shape for name, shape, _ in kn.PAR_BLOCKS}
+
+
+def _check_theta(theta, who):
+    if not isinstance(theta, dict) or not theta:
+        raise kn.KrError(f"{who}: theta must be a non-empty dict of torch tensors keyed by parameter name ({', '.join(PHYSICAL_SHAPES)})")
+    for k, v in theta.items():
+        if k not in PHYSICAL_SHAPES:
+            raise kn.KrError(f"{who}: unknown parameter {k!r}; the differentiable ones are {', '.join(PHYSICAL_SHAPES)}")
+        if not isinstance(v, torch.Tensor):
+            raise kn.KrError(f"{who}: theta[{k!r}] must be a torch tensor (it is a leaf the gradient is connected to)")
+        if tuple(v.shape) != PHYSICAL_SHAPES[k]:
+            raise kn.KrError(f"{who}: theta[{k!r}] must have shape {PHYSICAL_SHAPES[k]}; got {tuple(v.shape)}")
+
+
+def _write_theta(robot, names, values):
+    """values -> the robot's attributes, then the dependent terms (and with them the vstar the device derives from)"""
+    for k, v in zip(names, values):
+        a = v.detach().to(device="cpu", dtype=torch.float64).numpy().copy()
+        setattr(robot, k, float(a) if a.ndim == 0 else a)
+    robot.compute_intermediate_terms()
+
+
+class _SimulateTipsPhysical(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, robot, tdt, tol, names, *values):
+        import warnings
+        _write_theta(robot, names, values)
+        h = robot._native()
+        dev = f"cuda:{h.device}"
+        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
+        states, tip, status = forward_states(h, ctl_t, tol=tol)
+        bad = int((status != 0).sum())
+        if bad:
+            warnings.warn(f"simulate_tips_physical: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the "
+                          "gradient of those rods is not that of the solved step", RuntimeWarning)
+        ctx.robot, ctx.names, ctx.values = robot, names, [v.detach().clone() for v in values]
+        ctx.ctl_t, ctx.states = ctl_t, states
+        ctx.like, ctx.vlike = ctl, values
+        return tip.to(device=ctl.device, dtype=ctl.dtype)
+
+    @staticmethod
+    def backward(ctx, g_tips):
+        _write_theta(ctx.robot, ctx.names, ctx.values)  # (the robot may have carried other values since)
+        h, states = ctx.robot._native(), ctx.states
+        g = torch.zeros_like(states)
+        g[1:, :, h.N - 1, 12:15] = g_tips.to(device=states.device, dtype=states.dtype).permute(1, 0, 2)
+        out = h.simulate_vjp(ctx.ctl_t, states, g, need_bnd=False, need_par=True)
+        by_name = kn.split_par(out["g_par"].sum(dim=0))  # one robot, one parameter set: summed over the batch
+        return (out["g_ctl"].to(device=ctx.like.device, dtype=ctx.like.dtype), None, None, None, None,
+                *[by_name[k].to(device=v.device, dtype=v.dtype) for k, v in zip(ctx.names, ctx.vlike)])
+
+
+def simulate_tips_physical(robot, ctl, theta, dtype="f64", tol=1e-12):
+    """``simulate_tips`` with the rod's material parameters as leaves: ``theta`` is a dict of torch tensors under the names
+    ``E``, ``r``, ``rho``, ``L`` (scalars), ``vstar``, ``g``, ``C`` [3], ``Bse``, ``Bbt`` [3, 3], ``tendon_dirs`` [4, 3] - any
+    subset.  The values are written into ``robot`` (which keeps them), its dependent terms are recomputed, the forward call
+    runs, and ``tips[B, T, 3]`` comes back connected to ``ctl`` and to every tensor of ``theta``: ``loss.backward()`` fills
+    ``ctl.grad`` and ``theta[k].grad`` by one ``kr_simulate_vjp_par_batch``, the latter summed over the batch (one robot is one
+    parameter set).  Every entry of ``Bse`` / ``Bbt`` is an independent variable.  MLP off only; unknown names, wrong shapes
+    or a robot with its MLP on raise ``KrError`` before anything runs."""
+    _check_robot(robot)
+    if not isinstance(ctl, torch.Tensor):
+        raise kn.KrError("simulate_tips_physical: ctl must be a torch tensor (it is a leaf the gradient is connected to)")
+    _check_ctl(ctl)
+    _check_theta(theta, "simulate_tips_physical")
+    names = tuple(theta)
+    return _SimulateTipsPhysical.apply(ctl, robot, _tdt(dtype), float(tol), names, *[theta[k] for k in names])
 
 
 # ---- the KNODE model: physics plus the residual MLP in every sweep ----------------------------------------------------------

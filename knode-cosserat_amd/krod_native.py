@@ -27,6 +27,10 @@ KR_MAX_LAYERS = 8
 KR_DTW_MAX_LEN = 4096
 KR_FASTDTW_MAX_LEN, KR_FASTDTW_MAX_RADIUS = 1024, 8  # kr_fastdtw_batch: samples per sequence, radius
 KR_BND = 19  # p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) per rod and step (kr_simulate_batch_boundary)
+KR_PAR = 43  # material parameters a step adjoint can differentiate (kr_step_vjp_par_batch), in the order of PAR_BLOCKS
+# name, shape, offset into g_par[..., KR_PAR]: the order and row-major layout of struct kr_params (del_t and N are not differentiated)
+PAR_BLOCKS = (("E", (), 0), ("r", (), 1), ("rho", (), 2), ("L", (), 3), ("vstar", (3,), 4), ("g", (3,), 7), ("Bse", (3, 3), 10),
+              ("Bbt", (3, 3), 19), ("C", (3,), 28), ("tendon_dirs", (4, 3), 31))
 KR_KEYPOINTS_MAX = 16  # key points per call (kr_simulate_batch_keypoints)
 KR_E_ARG, KR_E_UNSUPPORTED = -1, -4
 KR_E_HIP, KR_E_STATE = -2, -3
@@ -158,6 +162,8 @@ _PROTOS = {
     "kr_simulate_vjp_nn_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_step_vjp_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "kr_simulate_vjp_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "kr_step_vjp_par_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "kr_simulate_vjp_par_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -196,6 +202,16 @@ def check(rc: int):
         err = KrError(f"libknode_rod error {rc}: {msg.decode() if msg else '?'}")
         err.code = rc
         raise err
+
+
+def split_par(g_par):
+    """``g_par[..., KR_PAR]`` (array or tensor) -> dict of views by parameter name, shaped ``[..., *shape]`` (``PAR_BLOCKS``)."""
+    lead = tuple(g_par.shape[:-1])
+    out = {}
+    for name, shape, off in PAR_BLOCKS:
+        n = int(np.prod(shape)) if shape else 1
+        out[name] = g_par[..., off:off + n].reshape(lead + shape)
+    return out
 
 
 def dtype_code(t) -> int:
@@ -724,10 +740,12 @@ class Handle:
         check(rc)
 
     # -- gradients -----------------------------------------------------------------
-    def step_vjp(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, use_nn=False, need_bnd=True):
+    def step_vjp(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, use_nn=False, need_bnd=True, need_par=False):
         """Adjoint of one solved step (``kr_step_vjp_batch``): the cotangent ``g_next[B, N, KR_SLOTS]`` of ``nxt`` ->
         dict with ``g_cur``, ``g_prev`` ``[B, N, KR_SLOTS]``, ``g_tensions[B, 4]``, ``g_bnd[B, KR_BND]`` (None without
-        ``need_bnd``), ``resid[B]`` (float64) and ``status[B]`` (int32), all on the device.  ``prev`` may be ``cur``."""
+        ``need_bnd``), ``resid[B]`` (float64) and ``status[B]`` (int32), all on the device.  ``prev`` may be ``cur``.
+        ``need_par``: the call goes through ``kr_step_vjp_par_batch`` (MLP off only) and the dict gains ``g_par[B, KR_PAR]``,
+        the gradient of the rod's material parameters (``PAR_BLOCKS``; ``split_par``)."""
         import torch
         B = cur.shape[0]
         for name, t in (("prev", prev), ("cur", cur), ("nxt", nxt), ("g_next", g_next)):
@@ -738,16 +756,27 @@ class Handle:
         new = lambda *shape, dtype=cur.dtype: torch.empty(shape, dtype=dtype, device=cur.device)
         out = dict(g_cur=new(B, self.N, KR_SLOTS), g_prev=new(B, self.N, KR_SLOTS), g_tensions=new(B, 4),
                    g_bnd=new(B, KR_BND) if need_bnd else None, resid=new(B, dtype=torch.float64), status=new(B, dtype=torch.int32))
+        if need_par:
+            if use_nn:
+                raise KrError("step_vjp: need_par is served with the MLP off only (kr_step_vjp_par_batch)")
+            out["g_par"] = new(B, KR_PAR)
+            check(self.lib.kr_step_vjp_par_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
+                                                 _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
+                                                 _ptr(out["g_par"]), _ptr(out["resid"]), _ptr(out["status"]), dtype_code(cur.dtype),
+                                                 _stream()))
+            return out
         check(self.lib.kr_step_vjp_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
                                          _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
                                          _ptr(out["resid"]), _ptr(out["status"]), int(bool(use_nn)), dtype_code(cur.dtype), _stream()))
         return out
 
-    def simulate_vjp(self, ctl, states, g_states, prev_init=None, scheme=KR_EULER, use_nn=False, need_bnd=True):
+    def simulate_vjp(self, ctl, states, g_states, prev_init=None, scheme=KR_EULER, use_nn=False, need_bnd=True, need_par=False):
         """Backward pass over a stored rollout (``kr_simulate_vjp_batch``): ``ctl[B, T, 4]``, the full history
         ``states[T + 1, B, N, KR_SLOTS]`` of the forward call (not a ring) and ``g_states`` of the same shape, in/out: the
         direct dL/dstates on entry, the total adjoint on return.  Returns dict with ``g_ctl[B, T, 4]``, ``g_bnd[B, KR_BND]``
-        (None without ``need_bnd``), ``g_prev_init`` (None unless ``prev_init`` is given), ``resid[B, T]``, ``status[B, T]``."""
+        (None without ``need_bnd``), ``g_prev_init`` (None unless ``prev_init`` is given), ``resid[B, T]``, ``status[B, T]``.
+        ``need_par``: the call goes through ``kr_simulate_vjp_par_batch`` (MLP off only) and the dict gains
+        ``g_par[B, KR_PAR]``, the gradient of the rod's material parameters summed over the steps."""
         import torch
         if ctl.dim() != 3 or ctl.shape[2] != 4 or ctl.shape[1] < 1:
             raise KrError(f"simulate_vjp: ctl must be [B, T, 4] with T >= 1; got {tuple(ctl.shape)}")
@@ -762,6 +791,14 @@ class Handle:
         out = dict(g_ctl=new(B, T, 4), g_bnd=new(B, KR_BND) if need_bnd else None,
                    g_prev_init=new(B, self.N, KR_SLOTS) if prev_init is not None else None,
                    resid=new(B, T, dtype=torch.float64), status=new(B, T, dtype=torch.int32))
+        if need_par:
+            if use_nn:
+                raise KrError("simulate_vjp: need_par is served with the MLP off only (kr_simulate_vjp_par_batch)")
+            out["g_par"] = new(B, KR_PAR)
+            check(self.lib.kr_simulate_vjp_par_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
+                                                     _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["g_par"]),
+                                                     _ptr(out["resid"]), _ptr(out["status"]), dtype_code(ctl.dtype), _stream()))
+            return out
         check(self.lib.kr_simulate_vjp_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
                                              _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["resid"]),
                                              _ptr(out["status"]), int(bool(use_nn)), dtype_code(ctl.dtype), _stream()))
