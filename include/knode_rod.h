@@ -320,7 +320,9 @@ int kr_step_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, c
  * cyclically (slot (t+1)%3) for tip-only runs: on return they hold the complete
  * last three states of the call (states T, T-1, T-2); what passes through them
  * before that is scratch of the library (the persistent kernels write interior
- * states only as far as they may have to re-read them: the twelve leading slots).  tip[B][T][3] may be NULL.
+ * states only as far as they may have to re-read them: records at the starts of
+ * their sub-intervals, and the twelve leading slots when a rod is handed from one
+ * kernel to the next).  tip[B][T][3] may be NULL.
  * status[B][T] may be NULL.  Replaces knode.simulate (knode.py:55-102).
  * state_prev_init: NULL = the reference's start (y_prev = y before the first
  * step, knode.py:65-66); otherwise the packed state one step before states[0],
@@ -529,8 +531,8 @@ int kr_simulate_batch_boundary(kr_handle* h, const kr_param_table* t, int64_t T,
 
 /* ---- key-point records: states at chosen grid points from a tip-only run -- */
 /* A simulate call returns the full history (states[T + 1][B][N][KR_SLOTS]: 22.9 MB per step at B = 1024, N = 100, fp64)
- * or, on a 3-slot ring, the tip positions and the last three states; interior steps of a ring run store only the twelve
- * leading slots of each record.  What is computed from a trajectory - the metrics below (kr_dtw_batch,
+ * or, on a 3-slot ring, the tip positions and the last three states; interior steps of a ring run leave only the records
+ * at the starts of the kernel's sub-intervals (leading slots are written when a rod is handed over).  What is computed from a trajectory - the metrics below (kr_dtw_batch,
  * kr_pose_mse_points_batch), the reference's key points ([3, 5, 7, 9], [2, 6, 9], markers [1, 3, 6, 9]), a tip
  * orientation - needs the states at a few grid points for every step.
  *

@@ -21,9 +21,14 @@
 //
 // Acceptance of step t is still a measured quantity of a sweep at the stored unknowns: the residual test, else the
 // chord update through the factors of step t's last condensation (which are only overwritten afterwards).  If
-// neither accepts, the Jacobian work for step t + 1 is thrown away, the chord update is applied, the tiles are
-// rebuilt from the two previous states in HBM (an accepted state's leading slots go there in one pass of the wavefront,
-// the rest of a record that must be complete during its trip) and step t continues with plain forward-difference sweeps.
+// neither accepts, the Jacobian work for step t + 1 is thrown away, the chord update is applied, the tile the rejected
+// sweep wrote over is put back and step t continues with plain forward-difference sweeps.  Put back from where: the
+// fp64 kernels at one wavefront per SIMD PARK that tile in registers before every merged sweep (one generation of one
+// tile is all a roll-back needs - the other tile is not written by the sweep) and store an accepted state's leading
+// slots only where the state has a reader: the last three states of a ring call, every state of a full trajectory.
+// Interior steps of a ring run then leave only the interval-start records in HBM, and a rod that gives up flushes its
+// two tiles on the way out.  The other kernels (fp32, two wavefronts per SIMD) copy every accepted tile to HBM in one
+// pass of the wavefront and rebuild both tiles from there.
 // Everything beyond that - a step that does not converge from the predicted or from the warm start - is left to
 // kr_ms_impl.hpp's kernel, launched behind this one: a rod that gives up writes the step it stopped at to
 // SimArgs::resume and the second kernel resumes there with the full ladder (warm start, damped single shooting).
@@ -56,6 +61,16 @@ constexpr int MSO_LAG = KR_MSO_LAG;
 // the Euler update of the trip before and carried in a register (rot_scale / ode_eval_s, rod_device.hpp), so that no
 // trip opens with that serial chain.  Measured: 0.4 k ticks per step off the merged sweep on its own, 0.35 k ON it
 // beside the one-wait reads, which take 0.88 k off alone - the two do not add, and the reads are what is built.
+// -DKR_MSO_PROBE_NO_TILE_PASS (a compile-time probe, TIMING ONLY): a lean ring step leaves out the pass that copies the
+// accepted tile of leading slots to HBM, whatever the kernel.  Right only while no verification is rejected and no rod
+// gives up - true of the headline run, whose event counts say so - and WRONG in general: without the park (below) a
+// roll-back and the take-over kernel read those slots back from HBM.  With -DKR_MSO_PARK=0 on the fp64 kernels it is the
+// price of the pass alone: what the verdict's ticks of the stamped build lose (LABBOOK, "the roll-back tile in registers").
+// -DKR_MSO_PARK=0 (a compile-time switch; same results): no park - every accepted step copies its tile to HBM and a
+// roll-back reads both tiles back from there, as the fp32 kernels and two wavefronts per SIMD still do.
+#ifndef KR_MSO_PARK
+#define KR_MSO_PARK 1
+#endif
 #ifndef KR_MSO_TRIP_WAITS
 #define KR_MSO_TRIP_WAITS 1
 #endif
@@ -297,6 +312,31 @@ __device__ __forceinline__ void mso_pred_update(MsPred<T, NC>& Q, int order, int
   if (Q.avail < MS_HLEV - 1) ++Q.avail;
 }
 
+// The park of the fp64 kernels at one wavefront per SIMD (mso_sim_kernel, PARK): one tile of leading slots in registers,
+// lane per grid point like the plain persistent kernel's regP.  Free functions, called from discarded-or-not
+// `if constexpr` branches only, so that the kernels without a park do not even see a closure of them.
+template <typename T>
+struct MsoPark { T v[MS_NPL][12]; };
+struct MsoNoPark { };
+// (every lane reads: a lane past the last grid point takes that one again, and no read stands under a mask)
+template <typename T>
+__device__ __forceinline__ void mso_park_take(MsoPark<T>& park, const T* lt, int lane, int N) {
+#pragma unroll
+  for (int q = 0; q < MS_NPL; ++q) {
+    const int j = lane + q * WAVE;
+    lds_load_vec<T, 12>(lt + (size_t)(j < N ? j : N - 1) * 12, park.v[q]);
+  }
+}
+template <typename T>
+__device__ __forceinline__ void mso_park_restore(const MsoPark<T>& park, T* lt, int lane, int N) {
+#pragma unroll
+  for (int q = 0; q < MS_NPL; ++q) {
+    const int j = lane + q * WAVE;
+    if (j < N) lds_store_vec<T, 12>(lt + (size_t)j * 12, park.v[q]);
+  }
+  wave_sync_lds();
+}
+
 #ifdef KR_MS_STAMPS
 struct MsoStats { unsigned long long total = 0, sweeps = 0, merged = 0, quick = 0, chord = 0, rejects = 0, retries = 0, rebuilds = 0, t_sweep = 0, t_alg = 0, t_pred = 0, t_verdict = 0, t_cond = 0, t_fin = 0, t_upd = 0, t_v1 = 0, t_v2 = 0, t_c1 = 0, t_c2 = 0, t_copy = 0; };
 #endif
@@ -344,6 +384,8 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
   constexpr bool KP = KPSRC::value;
   // the forms of the step's ends that only the fp64 kernels at one wavefront per SIMD take (the others keep their text)
   constexpr bool TRIM = OCC == 1 && sizeof(T) == 8 && MSO_LAG == 1;
+  // ... and that keep the tile a verification overwrites in registers instead of copying every accepted tile to HBM
+  constexpr bool PARK = TRIM && KR_MSO_PARK != 0;
   const unsigned long long kp_lo = KPSRC::lo(Pa), kp_hi = KPSRC::hi(Pa);
   const MsLds<T> L = ms_carve<T, HS>(reinterpret_cast<T*>(smem_raw) + (size_t)wv * mso_lds_elems<T, HS>(N), N, true, false);
   T* const Es = L.Es;
@@ -402,6 +444,21 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     }
     wave_sync();
   };
+  // The park (PARK): what a roll-back needs is ONE generation of ONE tile.  The merged sweep that verifies step tB
+  // writes level tB + 1 over level tB - 1 in lead_of(tB + 1), grid point by grid point (the trips' store blocks and the
+  // verdict's block for the last grid point), and nothing else in either tile: level tB in lead_of(tB) stands.  So the
+  // tile that is about to be overwritten is taken into registers, lane per grid point like the plain persistent
+  // kernel's regP, at the hand-over that makes the coming sweep a merged one; a rejected verification writes it back,
+  // and no accepted state of a lean step goes to HBM at all.  The values are the raw copies rebuild() would have read.
+  std::conditional_t<PARK, MsoPark<T>, MsoNoPark> park;
+  static_assert(!PARK || MS_NPL * WAVE >= 128, "the park holds every grid point the planner serves (one_wave_range)");
+  if constexpr (PARK) {
+#pragma unroll
+    for (int q = 0; q < MS_NPL; ++q) {
+#pragma unroll
+      for (int c = 0; c < 12; ++c) park.v[q][c] = T(0);
+    }
+  }
   // the cold slots a step rewrites: [W0, W0 + WN) - the wrench (loads), the whole boundary (bnd) or none
   using WSRC = rod_src_step_slots<T, PSRC>;
   constexpr int W0 = WSRC::first, WN = WSRC::count;
@@ -701,7 +758,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           // slots of every record (v and u of the last grid point, which no sweep touches, are among them) plus the full
           // records at the interval starts (predictor).  The leading slots are what this sweep leaves in its tile: once the step is accepted
           // the whole tile goes out in one pass of the wavefront (below, 2 x 6 stores from all lanes instead of 6 stores
-          // from four lanes in every trip); interior records of interior steps store nothing here (an interval start is
+          // from four lanes in every trip; with the park not even that - the tiles are flushed when a rod gives up); interior records of interior steps store nothing here (an interval start is
           // the grid point of trip 0, the last grid point's record is the verdict's and as lean as these: the trailing
           // predicated trips are interior too), all others only their remaining sixteen slots or, in a predicated trip, the whole record.
           if constexpr (FULL) {
@@ -939,7 +996,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         if (ib == MS_P - 1) {  // the last grid point: y from the sweep, z untouched
           T rec[KR_SLOTS];
           record_from(y, vlast, ulast, rec);
-          // (a lean ring step: the leading slots go out with the tile once the step is accepted, and slots 12.. of this
+          // (a lean ring step: the leading slots go out with the tile - at once, or with the park when the rod gives up - and slots 12.. of this
           //  record have no reader - rebuild and the take-over kernel read q w v u here, full records at interval starts)
           if (!lean) store_record(out_rod + (size_t)(N - 1) * KR_SLOTS, rec);
           if constexpr (KP) store_keypoint(kp_out, kp_lo, kp_hi, N - 1, rec);
@@ -1058,7 +1115,17 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
       }
       if (accepted) {
-        {  // leading slots of the accepted state: tile -> HBM, every grid point in one pass of the wavefront
+        // leading slots of the accepted state: tile -> HBM, every grid point in one pass of the wavefront.  With the
+        // park a lean ring step has no reader for them (a roll-back restores from registers, a rod that gives up
+        // flushes its two tiles behind the loop): only the states that stay complete - the last three of a ring call,
+        // every one of a full trajectory - take the pass.
+        bool tile_pass = true;
+#ifdef KR_MSO_PROBE_NO_TILE_PASS
+        tile_pass = !lean;  // TIMING PROBE, wrong as soon as a verification is rejected or a rod gives up
+#else
+        if constexpr (PARK) tile_pass = !lean;
+#endif
+        if (tile_pass) {
           const T* const lt = lead_of(tB + 1);
           for (int j = ln; j < N; j += WAVE) {
             T lv[12];
@@ -1090,7 +1157,7 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         if (ok && !reverify && itB + 2 <= maxit) {
           // First rejection of this step, and the chord update is a proper Newton-type correction (its factors are one
           // iteration old): verify AGAIN in a merged sweep instead of falling back to two plain ones.  The history of
-          // step tB comes back from HBM, the forward-difference lanes repeat their sweep of step tA from the same
+          // step tB comes back (from the park, else from HBM), the forward-difference lanes repeat their sweep of step tA from the same
           // start (what they computed above used a history that was off by this correction) - everything else is as
           // it was when the rejected sweep began, so a rejection costs one merged sweep instead of two plain sweeps
           // plus the restart of step tA.  In a short launch the slowest rod sets the time, and the slowest rod is the
@@ -1098,8 +1165,14 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
           reverify = true;
           itB += 1;
           dnB = (T)dnv;
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");  // the records streamed out above are re-read below
-          rebuild(tB);
+          if constexpr (PARK) {
+            // lead_of(tB) holds level tB: the rejected sweep wrote lead_of(tB + 1) only.  The park holds level tB - 1 as
+            // taken at the hand-over of step tB, and stays valid for the sweep that verifies again.
+            mso_park_restore<T>(park, lead_of(tB + 1), lane, N);
+          } else {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");  // the records streamed out above are re-read below
+            rebuild(tB);
+          }
 #ifdef KR_MS_STAMPS
           st.rebuilds += 1;
           KR_STAMP_ADD(st.t_alg, tq);
@@ -1123,12 +1196,20 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
         below = false;
         pred_skip = true;
         merged = false;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");  // the records streamed out above are re-read below
-        rebuild(tA);
+        if constexpr (PARK) {
+          // (tA is the rejected step again.)  lead_of(tA) holds level tA - a rejected sweep, first or second, writes
+          // lead_of(tA + 1) only, and a first rejection's restore went there too; the park still holds level tA - 1 from
+          // the hand-over of this step (no hand-over since): the plain sweeps below find step tA's history.
+          mso_park_restore<T>(park, lead_of(tA + 1), lane, N);
+        } else {
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");  // the records streamed out above are re-read below
+          rebuild(tA);
+        }
 #ifdef KR_MS_STAMPS
         st.rebuilds += 1;
         KR_STAMP_ADD(st.t_alg, tq);
 #endif
+        // (giving up here: level tA in lead_of(tA), level tA - 1 just restored in lead_of(tA - 1) - the flush behind the loop)
         if (it >= maxit) { resume_at = tA; break; }
         continue;
       }
@@ -1302,6 +1383,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
 #endif
         continue;
       }
+      // (giving up here: behind a plain sweep of step tA both tiles are its history as they were - a plain sweep writes
+      //  no tile; behind a merged sweep the verdict has ACCEPTED step tA - 1, whose sweep left level tA complete in
+      //  lead_of(tA) and never touched level tA - 1 in lead_of(tA - 1).  Either way lead_of(t) holds level t for both.)
       resume_at = tA;
       break;
     }
@@ -1314,6 +1398,9 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
       { unsigned long long t_; KR_STAMP(t_); st.t_copy += t_ - tq; }
 #endif
       dnB = dn; ampB = amp; belowB = below; itB = it; orderB = order;
+      // the coming sweep verifies step tA and writes level tA + 1 over level tA - 1: that tile into the park (requested
+      // here, in front of the predictor's algebra, which does not touch the tiles)
+      if constexpr (PARK) mso_park_take<T>(park, lead_of(tA + 1), lane, N);
       if (!pred_skip) {
         // (two wavefronts per SIMD: the second copy of the refit cost the fp32 instantiation 12 B more scratch)
         if constexpr (OCC == 1) mso_pred_update<T>(Q, order, a_predictor, lane, XsB, stamps);
@@ -1351,6 +1438,27 @@ __global__ __launch_bounds__(WAVE * MS_WPB, OCC) void mso_sim_kernel(const PSRC 
     }
   }
 
+  if constexpr (PARK) {
+    // A rod that gives up hands the take-over kernel the leading slots of levels resume_at and resume_at - 1 (its
+    // history of the step it resumes; kr_ms_impl.hpp, regP): lean steps have not stored them.  Tile lead_of(t) holds
+    // level t for both (see the two places that set resume_at).  At step 0 the older level is the caller's prev_init,
+    // which stays the caller's.
+    if (resume_at < T_steps) {
+      const T* const lc = lead_of(resume_at);
+      const T* const lp = lead_of(resume_at - 1);
+      T* const oc = state_ptr(resume_at);
+      T* const op = resume_at > 0 ? state_ptr(resume_at - 1) : nullptr;
+      for (int j = lane; j < N; j += WAVE) {
+        T lv[12];
+        lds_load_vec<T, 12>(lc + (size_t)j * 12, lv);
+        store_vec<T, 12>(oc + (size_t)j * KR_SLOTS, lv);
+        if (op) {
+          lds_load_vec<T, 12>(lp + (size_t)j * 12, lv);
+          store_vec<T, 12>(op + (size_t)j * KR_SLOTS, lv);
+        }
+      }
+    }
+  }
   if (lane < 6) A.G[rod * 6 + lane] = Gguess;
   if (lane == 0 && A.resume) A.resume[rod] = (int32_t)resume_at;
   // A rod handed over to the take-over kernel does not save: that kernel rebuilds the predictor from the stored states
