@@ -69,20 +69,21 @@ def mlp_on_matrix_cores(mlp):
     return True
 
 
-def expected_path(mode, N, mlp=None, scheme="euler"):
-    """The kernel kr_simulate_batch uses for this problem in this mode (mirror of ms_eligible /
-    launch_sim_persistent in kr_ms_impl.hpp)."""
+def expected_path(mode, N, mlp=None, scheme="euler", diag=True):
+    """The kernel kr_simulate_batch uses for this problem in this mode (mirror of plan_simulate in kr_plan.hip).
+    ``diag=False``: a rod with full material matrices (RodConst::diag cleared) - the overlapped kernel steps aside for
+    the plain persistent one, and with the MLP on the persistent kernels for one launch per step."""
     ms_ok = (N - 1 >= 2 * MS_P) and mlp_on_matrix_cores(mlp)
     if mode == "single" or not ms_ok:
         return 0
     if mode == "multi":
         return 1
-    if N > PERSIST_MAX_N or (mlp is not None and scheme != "euler"):
+    if N > PERSIST_MAX_N or (mlp is not None and (scheme != "euler" or not diag)):
         return 1
     if mlp is not None and len(mlp.weights) == 3 and mlp.weights[1].shape[0] > 192:
         return 1  # (the persistent kernels carry the base + JVP evaluator only: mlp_jvp.hpp, MJ_ACT_SLOTS)
     if mode == "overlap":  # Euler sweeps, MLP off, diagonal material matrices (every preset)
-        return 3 if (mlp is None and scheme == "euler") else 2
+        return 3 if (mlp is None and scheme == "euler" and diag) else 2
     return 2
 
 

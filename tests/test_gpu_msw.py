@@ -80,26 +80,27 @@ def test_other_grids_vs_oracle(torch_cuda, waves, N, mod):
     assert rel_l2(out["tip"][0], tip_c) < 1e-8
 
 
-def test_full_matrices(torch_cuda, waves):
-    """Off-diagonal material matrices (the DIAG = false instantiation): a rod whose Bse / Bbt are full."""
-    import cosserat_oracle as orc
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_full_matrices(torch_cuda, waves, dtype):
+    """Off-diagonal material matrices (the DIAG = false instantiation): the parameter set "full-asym" of
+    tests/full_matrix_cases.py - asymmetric Bse / Bbt, with a Bse large enough to be felt - against the C oracle, tips and
+    every stored state block by block (fp64: 1e-8 / 1e-7 per block, fp32: 1e-5 / 1e-4 per block, where only Bbt is held:
+    tests/test_full_matrices_cpu.py).  The other kernels and shapes: tests/test_gpu_full_matrices.py."""
+    import full_matrix_cases as fm
     from knode import simulate_batch
-    r = make_robot(None, 60)
-    rng = np.random.default_rng(5)
-    S = rng.standard_normal((3, 3)) * 0.05
-    r.Bbt = r.Bbt @ (np.eye(3) + S + S.T)
-    r.Bse = r.Bse + 1e-3 * (S + S.T)
-    r.compute_intermediate_terms()
-    T = 8
-    ctl = np.array(orc.calc_controls("sine", 1.0, r.del_t, T))
-    out = simulate_batch(r, ctl[None], dtype="f64")
+    N, T, kind = 60, 16, "sine"
+    assert (N, T, kind) in fm.SIM_CASES  # (the mutants of the set are known to be seen on this case)
+    r = fm.apply_to_rod(make_robot(None, N), "full-asym")
+    out = simulate_batch(r, fm.controls(T, kind)[None], dtype=dtype, tol=1e-12 if dtype == "f64" else 0.0)
     assert_path(r, 1, waves)
     assert np.all(out["status"] == 0)
-    P = orc.params_for(None, 60)
-    P.Bbt = np.array(r.Bbt)
-    P.Bse = np.array(r.Bse)
-    ref = orc.simulate(P.derived(), np.vstack([ctl, ctl[-1:]]), solver="newton")[1:, :3, -1]
-    assert rel_l2(out["tip"][0], ref) < 1e-8
+    ref_tips, ref_states = fm.oracle_run(N, T, kind, "full-asym")
+    tip_tol, state_tol = fm.TOL[dtype]
+    te = fm.tip_error(out["tip"][0], ref_tips[0, 1:])
+    be = fm.block_errors(out["traj"][0, 1:], ref_states[0, 1:])
+    print(f"W={waves} {dtype}: tips {te:.1e} | {fm.fmt_blocks(be)}")
+    assert te < tip_tol
+    assert all(v < state_tol for v in be.values()), be
 
 
 def test_batch_properties(torch_cuda, waves):

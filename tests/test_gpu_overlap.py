@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, rel_l2
-from gpu_helpers import assert_path, make_robot, set_mode_env
+from gpu_helpers import assert_path, expected_path, make_robot, set_mode_env
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -208,18 +208,34 @@ def test_presets_and_other_grids(torch_cuda, monkeypatch, mod):
 
 
 def test_full_matrices_fall_back(torch_cuda, monkeypatch):
-    """Non-diagonal damping matrices are not served by the overlapped kernel: the plain persistent kernel runs."""
+    """Non-diagonal damping matrices are not served by the overlapped kernel: the plain persistent kernel runs, and
+    computes that rod - one asymmetric off-diagonal pair in Bbt (a transposed index is another rod: the tips move by
+    4e-2), tips against the C oracle.  Every kernel on full Bse and Bbt: tests/test_gpu_full_matrices.py."""
     torch = torch_cuda
+    import cosserat_oracle as orc
+    import cosserat_oracle_c as oc
     set_mode_env(monkeypatch, "overlap")
     r = make_robot(None, 40)
     Bbt = np.array(r.Bbt, dtype=np.float64)
-    Bbt[0, 1] = Bbt[1, 0] = 0.1 * Bbt[0, 0]
+    Bbt[0, 1], Bbt[1, 0] = 0.3 * Bbt[0, 0], -0.1 * Bbt[0, 0]
     r.Bbt = Bbt
     r.compute_intermediate_terms()
     h = r._native()
-    ctl = torch.as_tensor(_sine(3, 6, r.del_t, 4), device=DEV).contiguous()
+    ctl_np = _sine(3, 6, r.del_t, 4)
+    ctl = torch.as_tensor(ctl_np, device=DEV).contiguous()
     a = _run(torch, h, ctl, torch.float64, 1)
     assert a["ran"] == 0 and h.get_option("last_sim_path") == 2 and np.all(a["status"] == 0)
+    assert_path(h, expected_path("overlap", 40, diag=False))
+    P = orc.params_for(None, 40)
+    P.Bbt = Bbt
+    Pt = orc.params_for(None, 40)
+    Pt.Bbt = Bbt.T.copy()
+    for b in range(3):
+        tip_c, _, bad = oc.simulate(P, ctl_np[b])
+        tip_t, _, bad_t = oc.simulate(Pt, ctl_np[b])
+        assert bad == 0 and bad_t == 0
+        assert rel_l2(tip_t, tip_c) > 1e-3  # (the transposed matrix would not pass below)
+        assert rel_l2(a["tip"][b], tip_c) < 1e-8
 
 
 @pytest.mark.parametrize("mode", ["persistent", "overlap", "multi"])
