@@ -26,14 +26,20 @@
 // cotangent vector in a register; the dot product fetches the others lane by lane (v_readlane with a constant lane).
 // The recursion is serial in j and the rods are independent: no atomics, no cross-wavefront traffic, and a rod's result
 // does not depend on the batch it rides in.
+//
+// The recursion is written once, in kr_adj_body.inc, and compiled into this unit's kernel with both of its forms off, into
+// kr_adj_par.hip's with PAR and into kr_adj_nn.hip's with NNON.  The rollout loop (simulate_vjp_steps) and the path from a C
+// entry point to a launch (adj_step_entry, adj_simulate_entry) are likewise written once, in kr_adj_impl.hpp; a unit
+// supplies its refusals and its launch.
 #include "kr_adj_impl.hpp"
 
 namespace kr {
 
 template <typename T>
 __global__ __launch_bounds__(64 * ADJ_RODS_PER_WG) void step_vjp_kernel(const RodConst<double> P, const AdjArgs<T> A) {
-  constexpr bool PAR = false;
-  const AdjPar<T> Q{};  // (named in the discarded PAR statements only)
+  constexpr bool PAR = false, NNON = false;
+  const AdjPar<T> Q{};  // (Q, NN: named in the discarded PAR and NNON statements only)
+  const AdjNn<T> NN{};
 #include "kr_adj_body.inc"
 }
 
@@ -47,14 +53,6 @@ static int launch_step_vjp(kr_handle* h, const AdjArgs<T>& A, hipStream_t s) {
 
 int launch_step_vjp_plain(kr_handle* h, const AdjArgs<float>& A, hipStream_t s) { return launch_step_vjp<float>(h, A, s); }
 int launch_step_vjp_plain(kr_handle* h, const AdjArgs<double>& A, hipStream_t s) { return launch_step_vjp<double>(h, A, s); }
-
-// The backward pass over a stored rollout: the composition of step adjoints stated at simulate_vjp_steps (kr_adj_impl.hpp)
-template <typename T>
-static int simulate_vjp(kr_handle* h, int64_t B, int64_t T_steps, const T* ctl, const T* states, const T* prev_init, T* g_states,
-                        T* g_prev_init, T* g_ctl, T* g_bnd, double* resid, int32_t* status, hipStream_t s) {
-  return simulate_vjp_steps<T>(h, B, T_steps, ctl, states, prev_init, g_states, g_prev_init, g_ctl, g_bnd, (T*)nullptr, resid, status, s,
-                               [](kr_handle* hh, const AdjArgs<T>& A, T*, hipStream_t ss) { return launch_step_vjp<T>(hh, A, ss); });
-}
 
 int adj_refuse(const char* api, int scheme, int use_nn) {
   if (use_nn != 0) {
@@ -77,46 +75,19 @@ int adj_refuse(const char* api, int scheme, int use_nn) {
 
 using namespace kr;
 
-#define KR_ADJ_ARG(cond, msg) \
-  if (cond) {                 \
-    set_error(msg);           \
-    return KR_E_ARG;          \
-  }
-
 extern "C" int kr_step_vjp_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, const void* state_cur,
                                  const void* state_next, const void* tensions, const void* g_next, void* g_cur, void* g_prev,
                                  void* g_tensions, void* g_bnd, double* resid, int32_t* status, int use_nn, int dtype, void* stream) {
-  KR_ADJ_ARG(!h, "null handle");
-  KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
-  KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, "kr_step_vjp_batch: B must be in [1, 2^31 - 1]");
-  KR_ADJ_ARG(!state_prev || !state_cur || !state_next || !tensions || !g_next, "kr_step_vjp_batch: null pointer argument");
-  if (int rc = adj_refuse("kr_step_vjp_batch", scheme, use_nn)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = order_stream(h, s)) return rc;
-  if (dtype == KR_F32) {
-    AdjArgs<float> A{B, (const float*)state_prev, (const float*)state_cur, (const float*)state_next, (const float*)tensions, 4,
-                     (const float*)g_next, (float*)g_cur, (float*)g_prev, (float*)g_tensions, 4, (float*)g_bnd, resid, status, 1};
-    return launch_step_vjp<float>(h, A, s);
-  }
-  AdjArgs<double> A{B, (const double*)state_prev, (const double*)state_cur, (const double*)state_next, (const double*)tensions, 4,
-                    (const double*)g_next, (double*)g_cur, (double*)g_prev, (double*)g_tensions, 4, (double*)g_bnd, resid, status, 1};
-  return launch_step_vjp<double>(h, A, s);
+  return adj_step_entry("kr_step_vjp_batch", h, B, state_prev, state_cur, state_next, tensions, g_next, g_cur, g_prev, g_tensions, g_bnd,
+                        resid, status, dtype, stream, [=](const char* api) { return adj_refuse(api, scheme, use_nn); },
+                        [](kr_handle* hh, const auto& A, hipStream_t s) { return launch_step_vjp(hh, A, s); });
 }
 
+// The backward pass over a stored rollout: the composition of step adjoints stated at simulate_vjp_steps (kr_adj_impl.hpp)
 extern "C" int kr_simulate_vjp_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
                                      const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
                                      double* resid, int32_t* status, int use_nn, int dtype, void* stream) {
-  KR_ADJ_ARG(!h, "null handle");
-  KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
-  KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, "kr_simulate_vjp_batch: B must be in [1, 2^31 - 1]");
-  KR_ADJ_ARG(T < 1, "kr_simulate_vjp_batch: T < 1");
-  KR_ADJ_ARG(!ctl || !states || !g_states, "kr_simulate_vjp_batch: null pointer argument");
-  if (int rc = adj_refuse("kr_simulate_vjp_batch", scheme, use_nn)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = order_stream(h, s)) return rc;
-  if (dtype == KR_F32)
-    return simulate_vjp<float>(h, B, T, (const float*)ctl, (const float*)states, (const float*)state_prev_init, (float*)g_states,
-                               (float*)g_prev_init, (float*)g_ctl, (float*)g_bnd, resid, status, s);
-  return simulate_vjp<double>(h, B, T, (const double*)ctl, (const double*)states, (const double*)state_prev_init, (double*)g_states,
-                              (double*)g_prev_init, (double*)g_ctl, (double*)g_bnd, resid, status, s);
+  return adj_simulate_entry("kr_simulate_vjp_batch", h, B, T, ctl, states, state_prev_init, g_states, g_prev_init, g_ctl, g_bnd, nullptr,
+                            resid, status, dtype, stream, [=](const char* api) { return adj_refuse(api, scheme, use_nn); }, 0,
+                            [](kr_handle* hh, const auto& A, void*, int64_t, hipStream_t s) { return launch_step_vjp(hh, A, s); });
 }

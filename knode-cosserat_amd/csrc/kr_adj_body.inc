@@ -1,13 +1,20 @@
-// kr_adj_body.inc - the step adjoint of one rod per wavefront: the body of step_vjp_kernel (kr_adj.hip, where the mapping
-// is described) and of step_vjp_par_kernel (kr_adj_par.hip).  Included INSIDE the kernel, as text, so that step_vjp_kernel
-// is compiled from the statements it always had: in scope are the kernel's arguments P (RodConst<double>) and A
-// (AdjArgs<T>), a `constexpr bool PAR`, and - read only where PAR holds - Q (AdjPar<T>): with PAR the gradient of the
-// material parameters goes into Q.g_par.
+// kr_adj_body.inc - the step adjoint of one rod per wavefront: the ONE text of the recursion, the body of step_vjp_kernel
+// (kr_adj.hip, where the mapping is described), of step_vjp_par_kernel (kr_adj_par.hip) and of step_vjp_nn_kernel
+// (kr_adj_nn.hip).  Included INSIDE the kernel, as text, so that each kernel is compiled from the statements it always had.
+// In scope are the kernel's arguments P (RodConst<double>) and A (AdjArgs<T>), and two forms:
+//   constexpr bool PAR   the gradient of the material parameters goes into Q.g_par; Q (AdjPar<T>) is read only where PAR holds
+//   constexpr bool NNON  the network's input Jacobian joins the per-point derivative and pass 2 emits the rows of the weight
+//                        gradient; NN (AdjNn<T>) is read only where NNON holds
+// A kernel without a form declares an empty Q / NN.  PAR and NNON are not dependent on T, so a discarded branch is still
+// type-checked (jc exists in every form), and whatever a form alone needs folds to a constant without it (q0, own): a
+// live declaration moves the register allocation of the kernels that never read it.
   const int lane = threadIdx.x & 63;
   const int64_t rod = (int64_t)blockIdx.x * ADJ_RODS_PER_WG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (rod >= A.B) return;  // (the whole wavefront: nothing below crosses wavefronts)
   const int N = P.N;
   const int64_t rec0 = rod * N;
+  const int64_t q0 = NNON ? rod * (N - 1) : 0;  // first row of this rod in the network arrays
+  const bool own = NNON && (lane < 19 || (lane >= 31 && lane < 34));
   const int dir = lane < 19 ? lane : lane + 13;  // lanes 19..30 -> 32..43 (history q w v u), 31..33 -> 44..46 (tendon force)
   const int yslot = adj_yslot(lane < 19 ? lane : 0);
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -43,18 +50,42 @@
   for (int j = N - 2; j >= 0; --j) {
     double d[25];
     adj_point(P, A, rec0 + j, dir, tf, d, bad);
+    double jc[25];
+    if constexpr (NNON) {
+      adj_nn_column(NN, q0 + j, lane, jc, bad);
+      if (lane < NNA_IN) bad = bad || !isfinite(NN.xrows[(q0 + j) * NNA_ROW + lane]);
+    }
     const T* g = A.g_next + (rec0 + j) * KR_SLOTS;
     double gz[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) gz[k] = (double)g[SL_V + k];
 #pragma unroll
     for (int k = 0; k < SL_USED; ++k) bad |= !isfinite((double)g[k]);
-    double acc = P.ds * adj_dot19(lam[0], d, 0.0);
+    if constexpr (NNON) {
+      double acc = 0.0, un = 0.0;
+      adj_dot19_nn(lam[0], d, jc, acc, un);
+      acc *= P.ds;
+      un *= P.ds;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) acc = fma(gz[k], d[19 + k], acc);
-    lam[0] = ((double)g[yslot] + lam[0]) + acc;
+      for (int k = 0; k < 6; ++k) {
+        acc = fma(gz[k], d[19 + k], acc);
+        un = fma(gz[k], jc[19 + k], un);
+      }
+      lam[0] = ((double)g[yslot] + lam[0]) + (acc + adj_nn_term(un, own, d));
 #pragma unroll
-    for (int s = 1; s < ADJ_SEEDS; ++s) lam[s] = lam[s] + P.ds * adj_dot19(lam[s], d, 0.0);
+      for (int s = 1; s < ADJ_SEEDS; ++s) {
+        double as = 0.0, us = 0.0;
+        adj_dot19_nn(lam[s], d, jc, as, us);
+        lam[s] = (lam[s] + P.ds * as) + adj_nn_term(P.ds * us, own, d);  // (the physics sum first, as without the network)
+      }
+    } else {
+      double acc = P.ds * adj_dot19(lam[0], d, 0.0);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = fma(gz[k], d[19 + k], acc);
+      lam[0] = ((double)g[yslot] + lam[0]) + acc;
+#pragma unroll
+      for (int s = 1; s < ADJ_SEEDS; ++s) lam[s] = lam[s] + P.ds * adj_dot19(lam[s], d, 0.0);
+    }
   }
   double a[6], m[6][6], nu[6];
   a[0] = adj_bcast<7>(lam[0]); a[1] = adj_bcast<8>(lam[0]); a[2] = adj_bcast<9>(lam[0]);
@@ -72,7 +103,7 @@
 #pragma unroll
     for (int l = 0; l < 6; ++l) bad |= !isfinite(m[k][l]);
   }
-  bad = __any(bad);  // (uniform already: every lane read the same values)
+  bad = __any(bad);  // (uniform already without the network; with it lanes read different columns of Jn and entries of x)
   const bool solved = adj_solve6(m, a, nu);
   const int st = bad ? KR_ST_NONFINITE : (solved ? KR_ST_CONVERGED : KR_ST_MAXIT);
   if (A.status && lane == 0) A.status[rod * A.st_stride] = st;
@@ -82,7 +113,15 @@
   T* ot = A.g_tens ? A.g_tens + rod * A.g_tens_stride : nullptr;
   T* ob = A.g_bnd ? A.g_bnd + rod * KR_BND : nullptr;
 
+  T* ox = NN.nn_x ? NN.nn_x + q0 * NNA_ROW : nullptr;
+  T* og = NN.nn_g ? NN.nn_g + q0 * NNA_ROW : nullptr;
   if (st != KR_ST_CONVERGED) {  // no gradient: NaN in every value that carries one, zero where the structure is zero
+    if constexpr (NNON)
+      if (lane < NNA_ROW)
+        for (int j = 0; j < N - 1; ++j) {  // (the rows keep their inputs; their cotangents carry no gradient)
+          if (ox) ox[(int64_t)j * NNA_ROW + lane] = lane < NNA_IN ? (T)NN.xrows[(q0 + j) * NNA_ROW + lane] : (T)0;
+          if (og) og[(int64_t)j * NNA_ROW + lane] = lane < 25 ? (T)nan : (T)0;
+        }
     if (lane < KR_SLOTS) {
       const T fill = lane < 12 ? (T)nan : (T)0;
       for (int j = 0; j < N; ++j) {
@@ -121,10 +160,33 @@
     double d[25];
     bool unused = false;
     adj_point(P, A, rec0 + j, dir, tf, d, unused);
+    double jc[25];
+    if constexpr (NNON) adj_nn_column(NN, q0 + j, lane, jc, unused);
     const T* g = A.g_next + (rec0 + j) * KR_SLOTS;
-    double acc = P.ds * adj_dot19(lm, d, 0.0);
+    double acc;
+    if constexpr (NNON) {
+      if (lane < NNA_ROW) {  // the row of the weight gradient: the network's input and the cotangent that reaches its output
+        const int zs = lane >= 19 && lane < 25 ? SL_V + lane - 19 : 0;
+        const double cz = (double)g[zs];
+        if (ox) ox[(int64_t)j * NNA_ROW + lane] = lane < NNA_IN ? (T)NN.xrows[(q0 + j) * NNA_ROW + lane] : (T)0;
+        if (og) og[(int64_t)j * NNA_ROW + lane] = lane < 19 ? (T)(P.ds * lm) : (lane < 25 ? (T)cz : (T)0);
+      }
+      double un = 0.0;
+      acc = 0.0;
+      adj_dot19_nn(lm, d, jc, acc, un);
+      acc *= P.ds;
+      un *= P.ds;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) acc = fma((double)g[SL_V + k], d[19 + k], acc);
+      for (int k = 0; k < 6; ++k) {
+        acc = fma((double)g[SL_V + k], d[19 + k], acc);
+        un = fma((double)g[SL_V + k], jc[19 + k], un);
+      }
+      acc += adj_nn_term(un, own, d);
+    } else {
+      acc = P.ds * adj_dot19(lm, d, 0.0);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = fma((double)g[SL_V + k], d[19 + k], acc);
+    }
     if constexpr (PAR) {
       double dp[25], val[25];
       adj_point_par(PD, c1, c2, A, rec0 + j, tf, dp, val);
@@ -162,16 +224,16 @@
   if constexpr (PAR) {
     // KR_PAR order: E, r, rho, L, vstar, g, Bse, Bbt, C, tendon_dirs.  L enters ds = L / (N - 1) alone; tendon_dirs enters
     // tf = tensions @ tendon_dirs alone
-    T* og = Q.g_par + rod * KR_PAR;
+    T* opar = Q.g_par + rod * KR_PAR;
     const double t0 = adj_bcast<31>(gtf), t1 = adj_bcast<32>(gtf), t2 = adj_bcast<33>(gtf);
     if (lane >= ADJ_PAR_LANE0) {
       const int k = lane - ADJ_PAR_LANE0;
-      og[k < 3 ? k : k + 1] = (T)gpar;
+      opar[k < 3 ? k : k + 1] = (T)gpar;
     }
-    if (lane == 0) og[3] = (T)(gL / (double)(N - 1));
+    if (lane == 0) opar[3] = (T)(gL / (double)(N - 1));
     if (lane < 12) {
       const int i = lane / 3, c = lane - 3 * i;
       const double ti = i == 0 ? tens[0] : (i == 1 ? tens[1] : (i == 2 ? tens[2] : tens[3]));
-      og[31 + lane] = (T)(ti * (c == 0 ? t0 : (c == 1 ? t1 : t2)));
+      opar[31 + lane] = (T)(ti * (c == 0 ? t0 : (c == 1 ? t1 : t2)));
     }
   }

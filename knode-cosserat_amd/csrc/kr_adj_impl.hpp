@@ -1,8 +1,9 @@
-// kr_adj_impl.hpp - what the step adjoint's kernels share: the argument block, the lane helpers, the per-point tangents
-// of the physics on dual numbers, the 6 x 6 solve, the composition over a stored
-// rollout and its accumulation kernel.  Used by kr_adj.hip (MLP off), kr_adj_par.hip (MLP off, with the gradient of the
-// material parameters) and kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative); the mapping is
-// described in kr_adj.hip.  The recursion of one rod, the body of both step kernels, is kr_adj_body.inc.
+// kr_adj_impl.hpp - what the three forms of the step adjoint share: the argument blocks, the lane helpers, the per-point
+// tangents of the physics on dual numbers, the network's and the parameters' additions to them, the 6 x 6 solve, the ONE
+// composition over a stored rollout with its accumulation kernel, and the ONE path from a C entry point to a launch
+// (adj_step_entry, adj_simulate_entry).  The forms are kr_adj.hip (MLP off), kr_adj_par.hip (MLP off, with the gradient of
+// the material parameters) and kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative); the mapping
+// is described in kr_adj.hip.  The recursion of one rod, the body of all three step kernels, is kr_adj_body.inc.
 #pragma once
 #include "kr_internal.hpp"
 #include "kr_point_dual.hpp"
@@ -229,12 +230,53 @@ __device__ __forceinline__ void adj_point_par(const RodConstDual& D, double c1, 
   }
 }
 
+// ---- the network's input Jacobian in the per-point derivative (kr_adj_nn.hip) ----
+constexpr int NNA_IN = 28, NNA_ROW = 32, NNA_JAC = 25 * 28;
+
+template <typename T>
+struct AdjNn {
+  const double* xrows;  // [B (N - 1)][NNA_ROW]: the network's input at every stored point
+  const double* jt;     // [B (N - 1)][28][25]: Jn, a column contiguous
+  T *nn_x, *nn_g;       // [B][N - 1][NNA_ROW], nullable
+};
+
+// The network's part of J^T w, w = [ds lambda; g_z] (25 values), without ever forming the lane's 25 network tangents:
+//   sum_o w_o (Jn X)[o][lane's direction] = own u[col] + sum_k d[19 + k] u[19 + k],      u = Jn^T w  (28 values)
+// Lane c < 25 forms u[c] from column c of Jn (lanes 19..24, the history lanes, hold the six z columns for everybody), lanes
+// 31..33 the tf columns 25..27: 25 loads of the lane's own contiguous column per point, and six broadcasts per cotangent.
+// `own`: lanes 0..18 and 31..33, whose input direction IS an input of the network.
+template <typename T>
+__device__ __forceinline__ void adj_nn_column(const AdjNn<T>& NN, int64_t q, int lane, double (&jc)[25], bool& bad) {
+  const int col = lane < 25 ? lane : (lane >= 31 && lane < 34 ? lane - 6 : 0);  // (an index, not a choice between pointers)
+  const double* __restrict__ J = NN.jt + q * NNA_JAC + col * 25;
+#pragma unroll
+  for (int o = 0; o < 25; ++o) {
+    jc[o] = J[o];
+    bad = bad || !isfinite(jc[o]);
+  }
+}
+// acc += sum_{o < 19} x_o d[o], un += sum_{o < 19} x_o jc[o]  (adj_dot19 with the network's column riding on its broadcasts)
+template <int O = 0>
+__device__ __forceinline__ void adj_dot19_nn(double x, const double (&d)[25], const double (&jc)[25], double& acc, double& un) {
+  if constexpr (O < 19) {
+    const double b = adj_bcast<O>(x);
+    acc = fma(b, d[O], acc);
+    un = fma(b, jc[O], un);
+    adj_dot19_nn<O + 1>(x, d, jc, acc, un);
+  }
+}
+__device__ __forceinline__ double adj_nn_term(double u, bool own, const double (&d)[25]) {
+  double r = own ? u : 0.0;
+  r = fma(d[19], adj_bcast<19>(u), r); r = fma(d[20], adj_bcast<20>(u), r); r = fma(d[21], adj_bcast<21>(u), r);
+  r = fma(d[22], adj_bcast<22>(u), r); r = fma(d[23], adj_bcast<23>(u), r); r = fma(d[24], adj_bcast<24>(u), r);
+  return r;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void adj_add_kernel(T* dst, const T* src, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = dst[i] + src[i];
 }
-
 
 template <typename T>
 static int launch_add(T* dst, const T* src, int64_t n, hipStream_t s) {
@@ -250,18 +292,21 @@ int launch_step_vjp_plain(kr_handle* h, const AdjArgs<double>& A, hipStream_t s)
 //   step adjoint of (states[t - 1], states[t], states[t + 1], ctl[:, t]) with g_next = g_states[t + 1]
 //   g_states[t] += g_cur;  g_states[t - 1] += g_prev  (in this order, in the element type of the arrays)
 //   g_bnd += the step's, g_par += the step's (from zero, t = T - 1 first)
-// launch(h, A, w_par, s): one step adjoint, its parameter gradient into w_par[B][KR_PAR] (null when g_par is)
+// The workspace is a T-typed head (w_cur, w_prev, w_bnd) and, at the next 256-byte boundary, the tail_bytes the form asks
+// for: w_par[B][KR_PAR] of T with g_par, the network's rows and Jacobians (doubles) with the MLP on.
+// launch(h, A, tail, t, s): the step adjoint of step t (tail: null when tail_bytes is 0)
 template <typename T, typename Launch>
 static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T* ctl, const T* states, const T* prev_init, T* g_states,
-                              T* g_prev_init, T* g_ctl, T* g_bnd, T* g_par, double* resid, int32_t* status, hipStream_t s, Launch launch) {
+                              T* g_prev_init, T* g_ctl, T* g_bnd, T* g_par, double* resid, int32_t* status, size_t tail_bytes,
+                              hipStream_t s, Launch launch) {
   const int64_t slot = B * h->params.N * KR_SLOTS;
-  const size_t bnd_off = (size_t)2 * slot * sizeof(T);
-  const size_t par_off = bnd_off + (size_t)B * KR_BND * sizeof(T);
-  if (int rc = ensure_ws(h, par_off + (g_par ? (size_t)B * KR_PAR * sizeof(T) : 0))) return rc;
+  const size_t head = ((size_t)(2 * slot + B * KR_BND) * sizeof(T) + 255) / 256 * 256;
+  if (int rc = ensure_ws(h, head + tail_bytes)) return rc;
   T* w_cur = static_cast<T*>(h->ws);
   T* w_prev = w_cur + slot;
   T* w_bnd = w_prev + slot;
-  T* w_par = w_bnd + B * KR_BND;
+  void* tail = tail_bytes ? static_cast<char*>(h->ws) + head : nullptr;
+  T* w_par = static_cast<T*>(tail);  // (read with g_par only)
   if (g_bnd) KR_HIP(hipMemsetAsync(g_bnd, 0, (size_t)B * KR_BND * sizeof(T), s));
   if (g_par) KR_HIP(hipMemsetAsync(g_par, 0, (size_t)B * KR_PAR * sizeof(T), s));
   for (int64_t t = T_steps - 1; t >= 0; --t) {
@@ -282,7 +327,7 @@ static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T*
     A.resid = resid ? resid + t : nullptr;
     A.status = status ? status + t : nullptr;
     A.st_stride = T_steps;
-    if (int rc = launch(h, A, g_par ? w_par : nullptr, s)) return rc;
+    if (int rc = launch(h, A, tail, t, s)) return rc;
     if (int rc = launch_add<T>(g_states + t * slot, w_cur, slot, s)) return rc;
     if (!into_init)
       if (int rc = launch_add<T>(g_states + (t > 0 ? t - 1 : 0) * slot, w_prev, slot, s)) return rc;
@@ -294,6 +339,57 @@ static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T*
   return KR_OK;
 }
 
+// The refusals of the MLP-off forms: use_nn, then the scheme (the scheme half is the MLP-on form's too)
 int adj_refuse(const char* api, int scheme, int use_nn);  // (kr_adj.hip)
+
+// ---- from a C entry point to its launch ----
+// What a caller with two mistakes hears of first: handle, dtype, B, (T,) null pointers, the form's refusal, stream ordering.
+#define KR_ADJ_ARG(cond, msg) \
+  if (cond) {                 \
+    set_error(msg);           \
+    return KR_E_ARG;          \
+  }
+
+// A step call.  refuse(api): the form's refusals; launch(h, A, s): the form's step adjoint of AdjArgs<float or double>.
+template <typename Refuse, typename Launch>
+static int adj_step_entry(const char* api, kr_handle* h, int64_t B, const void* state_prev, const void* state_cur, const void* state_next,
+                          const void* tensions, const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd,
+                          double* resid, int32_t* status, int dtype, void* stream, Refuse refuse, Launch launch) {
+  KR_ADJ_ARG(!h, "null handle");
+  KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
+  KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, std::string(api) + ": B must be in [1, 2^31 - 1]");
+  KR_ADJ_ARG(!state_prev || !state_cur || !state_next || !tensions || !g_next, std::string(api) + ": null pointer argument");
+  if (int rc = refuse(api)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = order_stream(h, s)) return rc;
+  auto run = [&](auto* elem) {
+    using T = std::remove_pointer_t<decltype(elem)>;
+    const AdjArgs<T> A{B, (const T*)state_prev, (const T*)state_cur, (const T*)state_next, (const T*)tensions, 4,
+                       (const T*)g_next, (T*)g_cur, (T*)g_prev, (T*)g_tensions, 4, (T*)g_bnd, resid, status, 1};
+    return launch(h, A, s);
+  };
+  return dtype == KR_F32 ? run((float*)nullptr) : run((double*)nullptr);
+}
+
+// A rollout call: simulate_vjp_steps in the element type of the arrays.  tail_bytes, launch: as there.
+template <typename Refuse, typename Launch>
+static int adj_simulate_entry(const char* api, kr_handle* h, int64_t B, int64_t T_steps, const void* ctl, const void* states,
+                              const void* prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd, void* g_par,
+                              double* resid, int32_t* status, int dtype, void* stream, Refuse refuse, size_t tail_bytes, Launch launch) {
+  KR_ADJ_ARG(!h, "null handle");
+  KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
+  KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, std::string(api) + ": B must be in [1, 2^31 - 1]");
+  KR_ADJ_ARG(T_steps < 1, std::string(api) + ": T < 1");
+  KR_ADJ_ARG(!ctl || !states || !g_states, std::string(api) + ": null pointer argument");
+  if (int rc = refuse(api)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = order_stream(h, s)) return rc;
+  auto run = [&](auto* elem) {
+    using T = std::remove_pointer_t<decltype(elem)>;
+    return simulate_vjp_steps<T>(h, B, T_steps, (const T*)ctl, (const T*)states, (const T*)prev_init, (T*)g_states, (T*)g_prev_init,
+                                 (T*)g_ctl, (T*)g_bnd, (T*)g_par, resid, status, tail_bytes, s, launch);
+  };
+  return dtype == KR_F32 ? run((float*)nullptr) : run((double*)nullptr);
+}
 
 }  // namespace kr

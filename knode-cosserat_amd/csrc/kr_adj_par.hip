@@ -20,6 +20,7 @@
 // everything was measured first: the recursion's statements are the same text, but compiled beside the second evaluation
 // they are contracted into fused multiply-adds differently, and at B = 1024, N = 100, T = 64 g_ctl differed in its last
 // bits.)  With g_par == NULL only the first launch happens: the call IS the existing call.
+// The rollout call is kr_adj.hip's composition, simulate_vjp_steps, whose workspace tail holds the step's g_par.
 #include "kr_adj_impl.hpp"
 
 namespace kr {
@@ -28,12 +29,13 @@ namespace kr {
 // the allocator use the whole file, and the fp32 instantiation then keeps no scratch slot behind its SGPR spills.
 template <typename T>
 __global__ __launch_bounds__(64 * ADJ_RODS_PER_WG) __attribute__((amdgpu_waves_per_eu(1, 1))) void step_vjp_par_kernel(const RodConst<double> P, const AdjArgs<T> A, const AdjPar<T> Q) {
-  constexpr bool PAR = true;
+  constexpr bool PAR = true, NNON = false;
+  const AdjNn<T> NN{};  // (named in the discarded NNON statements only)
 #include "kr_adj_body.inc"
 }
 
 template <typename T>
-static int launch_step_vjp_par(kr_handle* h, const AdjArgs<T>& A, T* g_par, hipStream_t s) {
+static int launch_step_vjp_par(kr_handle* h, const AdjArgs<T>& A, void* g_par, hipStream_t s) {
   if (int rc = launch_step_vjp_plain(h, A, s)) return rc;  // every output but g_par: the existing kernel, bit for bit
   if (!g_par) return KR_OK;
   AdjArgs<T> Ap = A;  // (reads only; g_par is all this launch writes)
@@ -41,7 +43,7 @@ static int launch_step_vjp_par(kr_handle* h, const AdjArgs<T>& A, T* g_par, hipS
   Ap.resid = nullptr;
   Ap.status = nullptr;
   AdjPar<T> Q{};
-  Q.g_par = g_par;
+  Q.g_par = static_cast<T*>(g_par);
   const kr_params& p = h->params;
   Q.E = p.E; Q.r = p.r; Q.rho = p.rho;
   for (int i = 0; i < 3; ++i) {
@@ -58,54 +60,21 @@ static int launch_step_vjp_par(kr_handle* h, const AdjArgs<T>& A, T* g_par, hipS
 
 using namespace kr;
 
-#define KR_ADJ_ARG(cond, msg) \
-  if (cond) {                 \
-    set_error(msg);           \
-    return KR_E_ARG;          \
-  }
-
 extern "C" int kr_step_vjp_par_batch(kr_handle* h, int64_t B, int scheme, const void* state_prev, const void* state_cur,
                                      const void* state_next, const void* tensions, const void* g_next, void* g_cur, void* g_prev,
                                      void* g_tensions, void* g_bnd, void* g_par, double* resid, int32_t* status, int dtype,
                                      void* stream) {
-  KR_ADJ_ARG(!h, "null handle");
-  KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
-  KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, "kr_step_vjp_par_batch: B must be in [1, 2^31 - 1]");
-  KR_ADJ_ARG(!state_prev || !state_cur || !state_next || !tensions || !g_next, "kr_step_vjp_par_batch: null pointer argument");
-  if (int rc = adj_refuse("kr_step_vjp_par_batch", scheme, 0)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = order_stream(h, s)) return rc;
-  if (dtype == KR_F32) {
-    AdjArgs<float> A{B, (const float*)state_prev, (const float*)state_cur, (const float*)state_next, (const float*)tensions, 4,
-                     (const float*)g_next, (float*)g_cur, (float*)g_prev, (float*)g_tensions, 4, (float*)g_bnd, resid, status, 1};
-    return launch_step_vjp_par<float>(h, A, (float*)g_par, s);
-  }
-  AdjArgs<double> A{B, (const double*)state_prev, (const double*)state_cur, (const double*)state_next, (const double*)tensions, 4,
-                    (const double*)g_next, (double*)g_cur, (double*)g_prev, (double*)g_tensions, 4, (double*)g_bnd, resid, status, 1};
-  return launch_step_vjp_par<double>(h, A, (double*)g_par, s);
+  return adj_step_entry("kr_step_vjp_par_batch", h, B, state_prev, state_cur, state_next, tensions, g_next, g_cur, g_prev, g_tensions,
+                        g_bnd, resid, status, dtype, stream, [=](const char* api) { return adj_refuse(api, scheme, 0); },
+                        [=](kr_handle* hh, const auto& A, hipStream_t s) { return launch_step_vjp_par(hh, A, g_par, s); });
 }
 
-template <typename T>
-static int simulate_vjp_par(kr_handle* h, int64_t B, int64_t T_steps, const void* ctl, const void* states, const void* prev_init,
-                            void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd, void* g_par, double* resid, int32_t* status,
-                            hipStream_t s) {
-  return simulate_vjp_steps<T>(h, B, T_steps, (const T*)ctl, (const T*)states, (const T*)prev_init, (T*)g_states, (T*)g_prev_init,
-                               (T*)g_ctl, (T*)g_bnd, (T*)g_par, resid, status, s,
-                               [](kr_handle* hh, const AdjArgs<T>& A, T* w_par, hipStream_t ss) { return launch_step_vjp_par<T>(hh, A, w_par, ss); });
-}
-
+// (the rollout's tail is w_par[B][KR_PAR], the step's parameter gradient that simulate_vjp_steps adds to g_par)
 extern "C" int kr_simulate_vjp_par_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
                                          const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
                                          void* g_par, double* resid, int32_t* status, int dtype, void* stream) {
-  KR_ADJ_ARG(!h, "null handle");
-  KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
-  KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, "kr_simulate_vjp_par_batch: B must be in [1, 2^31 - 1]");
-  KR_ADJ_ARG(T < 1, "kr_simulate_vjp_par_batch: T < 1");
-  KR_ADJ_ARG(!ctl || !states || !g_states, "kr_simulate_vjp_par_batch: null pointer argument");
-  if (int rc = adj_refuse("kr_simulate_vjp_par_batch", scheme, 0)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = order_stream(h, s)) return rc;
-  if (dtype == KR_F32)
-    return simulate_vjp_par<float>(h, B, T, ctl, states, state_prev_init, g_states, g_prev_init, g_ctl, g_bnd, g_par, resid, status, s);
-  return simulate_vjp_par<double>(h, B, T, ctl, states, state_prev_init, g_states, g_prev_init, g_ctl, g_bnd, g_par, resid, status, s);
+  const size_t tail = g_par ? (size_t)B * KR_PAR * (dtype == KR_F32 ? sizeof(float) : sizeof(double)) : 0;
+  return adj_simulate_entry("kr_simulate_vjp_par_batch", h, B, T, ctl, states, state_prev_init, g_states, g_prev_init, g_ctl, g_bnd, g_par,
+                            resid, status, dtype, stream, [=](const char* api) { return adj_refuse(api, scheme, 0); }, tail,
+                            [](kr_handle* hh, const auto& A, void* w_par, int64_t, hipStream_t s) { return launch_step_vjp_par(hh, A, w_par, s); });
 }

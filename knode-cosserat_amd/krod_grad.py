@@ -60,6 +60,44 @@ def forward_states(h, ctl_t, tol=1e-12, maxit=0, prev_init=None, use_nn=False):
     return states, tip, status
 
 
+def _seed_tips(h, g, g_tips, add=False):
+    """dL/d(tip of step t) -> slots 12..14 of the last record of g[t + 1] (``add``: on top of what g holds)"""
+    tips = g_tips.to(device=g.device, dtype=g.dtype).permute(1, 0, 2)
+    if add:
+        g[1:, :, h.N - 1, 12:15] += tips
+    else:
+        g[1:, :, h.N - 1, 12:15] = tips
+
+
+def _check_rollout(who, ctl, states, g_states, g_tips):
+    B, T = _check_ctl(ctl)
+    if g_states is None and g_tips is None:
+        raise kn.KrError(f"{who}: give g_states and / or g_tips (a loss has to enter somewhere)")
+    if tuple(states.shape)[0] != T + 1:
+        raise kn.KrError(f"{who}: states must be the full history [{T + 1}, {B}, N, {kn.KR_SLOTS}] of the forward call, not a "
+                         f"ring; got {tuple(states.shape)}")
+    if g_tips is not None and tuple(g_tips.shape) != (B, T, 3):
+        raise kn.KrError(f"{who}: g_tips must be [{B}, {T}, 3]; got {tuple(g_tips.shape)}")
+
+
+def _rollout(h, vjp, ctl, states, g_states, g_tips, prev_init, dtype, **kw):
+    """What rollout_grad and rollout_grad_nn share after their checks: the arguments on the device, the seeded ``g``, the
+    call ``vjp`` (``h.simulate_vjp`` or ``h.simulate_vjp_nn``), and the part of the result dict both have.  Returns
+    (the handle's output dict, the result dict)."""
+    tdt, dev = _tdt(dtype), f"cuda:{h.device}"
+    to_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=tdt).contiguous()
+    ctl_t, states_t = to_dev(ctl), to_dev(states)
+    g = to_dev(g_states).clone() if g_states is not None else torch.zeros_like(states_t)
+    if g_tips is not None:
+        _seed_tips(h, g, to_dev(g_tips), add=True)
+    out = vjp(ctl_t, states_t, g, prev_init=to_dev(prev_init) if prev_init is not None else None, **kw)
+    res = {"ctl": out["g_ctl"].cpu().numpy(), "states": g.cpu().numpy(), "boundary": out["g_bnd"].cpu().numpy(),
+           "resid": out["resid"].cpu().numpy(), "status": out["status"].cpu().numpy()}
+    if prev_init is not None:
+        res["prev_init"] = out["g_prev_init"].cpu().numpy()
+    return out, res
+
+
 def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None, dtype="f64", physical=False):
     """Backward pass over a stored rollout of ``robot`` (MLP off): ``ctl[B, T, 4]`` and the FULL history
     ``states[T + 1, B, N, KR_SLOTS]`` of the forward call (host arrays or device tensors; a ring of three states does not
@@ -75,50 +113,48 @@ def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None,
     ``r``, ``rho``, ``L`` [B], ``vstar``, ``g``, ``C`` [B, 3], ``Bse``, ``Bbt`` [B, 3, 3] (every entry an independent
     variable), ``tendon_dirs`` [B, 4, 3] (``kr_simulate_vjp_par_batch``; a rod with a nonzero status has NaN in all)."""
     _check_robot(robot)
-    B, T = _check_ctl(ctl)
-    if g_states is None and g_tips is None:
-        raise kn.KrError("rollout_grad: give g_states and / or g_tips (a loss has to enter somewhere)")
-    if tuple(states.shape)[0] != T + 1:
-        raise kn.KrError(f"rollout_grad: states must be the full history [{T + 1}, {B}, N, {kn.KR_SLOTS}] of the forward call, not a "
-                         f"ring; got {tuple(states.shape)}")
-    if g_tips is not None and tuple(g_tips.shape) != (B, T, 3):
-        raise kn.KrError(f"rollout_grad: g_tips must be [{B}, {T}, 3]; got {tuple(g_tips.shape)}")
+    _check_rollout("rollout_grad", ctl, states, g_states, g_tips)
     h = robot._native()
-    tdt, dev = _tdt(dtype), f"cuda:{h.device}"
-    to_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=tdt).contiguous()
-    ctl_t, states_t = to_dev(ctl), to_dev(states)
-    g = to_dev(g_states).clone() if g_states is not None else torch.zeros_like(states_t)
-    if g_tips is not None:
-        g[1:, :, h.N - 1, 12:15] += to_dev(g_tips).permute(1, 0, 2)
-    out = h.simulate_vjp(ctl_t, states_t, g, prev_init=to_dev(prev_init) if prev_init is not None else None,
-                         need_par=bool(physical))
-    res = {"ctl": out["g_ctl"].cpu().numpy(), "states": g.cpu().numpy(), "boundary": out["g_bnd"].cpu().numpy(),
-           "resid": out["resid"].cpu().numpy(), "status": out["status"].cpu().numpy()}
-    if prev_init is not None:
-        res["prev_init"] = out["g_prev_init"].cpu().numpy()
+    out, res = _rollout(h, h.simulate_vjp, ctl, states, g_states, g_tips, prev_init, dtype, need_par=bool(physical))
     if physical:
         res["physical"] = {k: np.ascontiguousarray(v) for k, v in kn.split_par(out["g_par"].cpu().numpy()).items()}
     return res
+
+
+# ---- what the three autograd.Functions share: the forward run from ctl, the backward's seeded cotangent ----
+def _forward_tips(who, h, ctl, tdt, tol, use_nn=False):
+    """ctl on the handle's device, the stored rollout under it, and its tips as ``ctl`` wants them.  ``who``: warn under
+    this name about steps that did not converge (None: no warning)."""
+    ctl_t = ctl.detach().to(device=f"cuda:{h.device}", dtype=tdt).contiguous()
+    states, tip, status = forward_states(h, ctl_t, tol=tol, use_nn=use_nn)
+    bad = int((status != 0).sum()) if who else 0
+    if bad:  # (the adjoint is that of the exact root: say so, as knode.simulate does, instead of handing back a gradient in silence)
+        import warnings
+        warnings.warn(f"{who}: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the gradient of those rods is "
+                      "not that of the solved step", RuntimeWarning)
+    return ctl_t, states, status, tip.to(device=ctl.device, dtype=ctl.dtype)
+
+
+def _tip_cotangent(h, states, g_tips):
+    g = torch.zeros_like(states)
+    _seed_tips(h, g, g_tips)
+    return g
 
 
 class _SimulateTips(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctl, robot, tdt, tol):
         h = robot._native()
-        dev = f"cuda:{h.device}"
-        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
-        states, tip, status = forward_states(h, ctl_t, tol=tol)
+        ctl_t, states, status, tip = _forward_tips(None, h, ctl, tdt, tol)
         ctx.h, ctx.ctl_t, ctx.states = h, ctl_t, states
         ctx.like = ctl
         ctx.status = status
-        return tip.to(device=ctl.device, dtype=ctl.dtype)
+        return tip
 
     @staticmethod
     def backward(ctx, g_tips):
         h, states = ctx.h, ctx.states
-        g = torch.zeros_like(states)
-        g[1:, :, h.N - 1, 12:15] = g_tips.to(device=states.device, dtype=states.dtype).permute(1, 0, 2)
-        out = h.simulate_vjp(ctx.ctl_t, states, g, need_bnd=False)
+        out = h.simulate_vjp(ctx.ctl_t, states, _tip_cotangent(h, states, g_tips), need_bnd=False)
         return out["g_ctl"].to(device=ctx.like.device, dtype=ctx.like.dtype), None, None, None
 
 
@@ -160,28 +196,18 @@ def _write_theta(robot, names, values):
 class _SimulateTipsPhysical(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctl, robot, tdt, tol, names, *values):
-        import warnings
         _write_theta(robot, names, values)
-        h = robot._native()
-        dev = f"cuda:{h.device}"
-        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
-        states, tip, status = forward_states(h, ctl_t, tol=tol)
-        bad = int((status != 0).sum())
-        if bad:
-            warnings.warn(f"simulate_tips_physical: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the "
-                          "gradient of those rods is not that of the solved step", RuntimeWarning)
+        ctl_t, states, _, tip = _forward_tips("simulate_tips_physical", robot._native(), ctl, tdt, tol)
         ctx.robot, ctx.names, ctx.values = robot, names, [v.detach().clone() for v in values]
         ctx.ctl_t, ctx.states = ctl_t, states
         ctx.like, ctx.vlike = ctl, values
-        return tip.to(device=ctl.device, dtype=ctl.dtype)
+        return tip
 
     @staticmethod
     def backward(ctx, g_tips):
         _write_theta(ctx.robot, ctx.names, ctx.values)  # (the robot may have carried other values since)
         h, states = ctx.robot._native(), ctx.states
-        g = torch.zeros_like(states)
-        g[1:, :, h.N - 1, 12:15] = g_tips.to(device=states.device, dtype=states.dtype).permute(1, 0, 2)
-        out = h.simulate_vjp(ctx.ctl_t, states, g, need_bnd=False, need_par=True)
+        out = h.simulate_vjp(ctx.ctl_t, states, _tip_cotangent(h, states, g_tips), need_bnd=False, need_par=True)
         by_name = kn.split_par(out["g_par"].sum(dim=0))  # one robot, one parameter set: summed over the batch
         return (out["g_ctl"].to(device=ctx.like.device, dtype=ctx.like.dtype), None, None, None, None,
                 *[by_name[k].to(device=v.device, dtype=v.dtype) for k, v in zip(ctx.names, ctx.vlike)])
@@ -295,31 +321,14 @@ def rollout_grad_nn(robot, ctl, states, g_states=None, g_tips=None, prev_init=No
     into the handle first, and the dict also holds ``params``, the list of host arrays dL/dW1, dL/db1, ... summed over
     grid points, rods and steps (``weight_grads``).  Without ``params`` the network is the robot's own."""
     _check_robot_nn(robot, "rollout_grad_nn")
-    B, T = _check_ctl(ctl)
-    if g_states is None and g_tips is None:
-        raise kn.KrError("rollout_grad_nn: give g_states and / or g_tips (a loss has to enter somewhere)")
-    if tuple(states.shape)[0] != T + 1:
-        raise kn.KrError(f"rollout_grad_nn: states must be the full history [{T + 1}, {B}, N, {kn.KR_SLOTS}] of the forward call, not "
-                         f"a ring; got {tuple(states.shape)}")
-    if g_tips is not None and tuple(g_tips.shape) != (B, T, 3):
-        raise kn.KrError(f"rollout_grad_nn: g_tips must be [{B}, {T}, 3]; got {tuple(g_tips.shape)}")
+    _check_rollout("rollout_grad_nn", ctl, states, g_states, g_tips)
     if params is not None:
         _check_params(params, "rollout_grad_nn")
     h = robot._native(push_mlp=params is None)  # (params: pushed from the device below, no host pack of the robot's own)
-    tdt, dev = _tdt(dtype), f"cuda:{h.device}"
-    to_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=tdt).contiguous()
+    _tdt(dtype)  # (an unsupported dtype is refused before anything is pushed)
     if params is not None:
         p32, acts = _push_params(robot, h, list(params), "rollout_grad_nn")
-    ctl_t, states_t = to_dev(ctl), to_dev(states)
-    g = to_dev(g_states).clone() if g_states is not None else torch.zeros_like(states_t)
-    if g_tips is not None:
-        g[1:, :, h.N - 1, 12:15] += to_dev(g_tips).permute(1, 0, 2)
-    out = h.simulate_vjp_nn(ctl_t, states_t, g, prev_init=to_dev(prev_init) if prev_init is not None else None,
-                            need_rows=params is not None)
-    res = {"ctl": out["g_ctl"].cpu().numpy(), "states": g.cpu().numpy(), "boundary": out["g_bnd"].cpu().numpy(),
-           "resid": out["resid"].cpu().numpy(), "status": out["status"].cpu().numpy()}
-    if prev_init is not None:
-        res["prev_init"] = out["g_prev_init"].cpu().numpy()
+    out, res = _rollout(h, h.simulate_vjp_nn, ctl, states, g_states, g_tips, prev_init, dtype, need_rows=params is not None)
     if params is not None:
         res["params"] = [t.cpu().numpy() for t in weight_grads(h, p32, acts, out["nn_x"], out["nn_g"])]
     return res
@@ -328,28 +337,19 @@ def rollout_grad_nn(robot, ctl, states, g_states=None, g_tips=None, prev_init=No
 class _SimulateTipsNn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctl, robot, tdt, tol, *params):
-        import warnings
         h = robot._native(push_mlp=False)  # (no host pack of the robot's own weights: the live ones go in from the device)
-        dev = f"cuda:{h.device}"
         p32, acts = _push_params(robot, h, list(params), "simulate_tips_nn")
-        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
-        states, tip, status = forward_states(h, ctl_t, tol=tol, use_nn=True)
-        bad = int((status != 0).sum())
-        if bad:  # (the adjoint is that of the exact root: say so, as knode.simulate does, instead of handing back a gradient in silence)
-            warnings.warn(f"simulate_tips_nn: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the gradient of "
-                          "those rods is not that of the solved step", RuntimeWarning)
+        ctl_t, states, _, tip = _forward_tips("simulate_tips_nn", h, ctl, tdt, tol, use_nn=True)
         ctx.robot, ctx.h, ctx.ctl_t, ctx.states, ctx.p32, ctx.acts = robot, h, ctl_t, states, p32, acts
         ctx.like, ctx.plike = ctl, params
-        return tip.to(device=ctl.device, dtype=ctl.dtype)
+        return tip
 
     @staticmethod
     def backward(ctx, g_tips):
         h, states = ctx.h, ctx.states
         h.set_mlp_device(ctx.p32[0::2], ctx.p32[1::2], ctx.acts)  # (the handle may have served another network since)
         ctx.robot._mlp_key = None  # (... and the robot must not believe its own weights are still the handle's)
-        g = torch.zeros_like(states)
-        g[1:, :, h.N - 1, 12:15] = g_tips.to(device=states.device, dtype=states.dtype).permute(1, 0, 2)
-        out = h.simulate_vjp_nn(ctx.ctl_t, states, g, need_bnd=False)
+        out = h.simulate_vjp_nn(ctx.ctl_t, states, _tip_cotangent(h, states, g_tips), need_bnd=False)
         grads = weight_grads(h, ctx.p32, ctx.acts, out["nn_x"], out["nn_g"])
         return (out["g_ctl"].to(device=ctx.like.device, dtype=ctx.like.dtype), None, None, None,
                 *[a.to(device=p.device, dtype=p.dtype) for a, p in zip(grads, ctx.plike)])

@@ -740,34 +740,67 @@ class Handle:
         check(rc)
 
     # -- gradients -----------------------------------------------------------------
+    def _step_vjp_out(self, who, prev, cur, nxt, tensions, g_next, need_bnd, need_par=False, use_nn=False, need_rows=None):
+        """The shape checks of a step adjoint (``who``: the method named in the messages) -> (B, the argument list the three C
+        calls share, up to ``g_bnd``, and the dict of fresh outputs - with ``g_par`` under ``need_par``, with ``nn_x`` and
+        ``nn_g`` where ``need_rows`` is not None)."""
+        import torch
+        B = cur.shape[0]
+        for name, t in (("prev", prev), ("cur", cur), ("nxt", nxt), ("g_next", g_next)):
+            if tuple(t.shape) != (B, self.N, KR_SLOTS) or t.dtype != cur.dtype:
+                raise KrError(f"{who}: {name} must be [{B}, {self.N}, {KR_SLOTS}] of {cur.dtype}; got {tuple(t.shape)} {t.dtype}")
+        if tuple(tensions.shape) != (B, 4) or tensions.dtype != cur.dtype:
+            raise KrError(f"{who}: tensions must be [{B}, 4] of {cur.dtype}; got {tuple(tensions.shape)} {tensions.dtype}")
+        new = lambda *shape, dtype=cur.dtype: torch.empty(shape, dtype=dtype, device=cur.device)
+        out = dict(g_cur=new(B, self.N, KR_SLOTS), g_prev=new(B, self.N, KR_SLOTS), g_tensions=new(B, 4),
+                   g_bnd=new(B, KR_BND) if need_bnd else None, resid=new(B, dtype=torch.float64), status=new(B, dtype=torch.int32))
+        if need_par:
+            if use_nn:
+                raise KrError(f"{who}: need_par is served with the MLP off only (kr_{who}_par_batch)")
+            out["g_par"] = new(B, KR_PAR)
+        if need_rows is not None:
+            out["nn_x"], out["nn_g"] = (new(B, self.N - 1, 32), new(B, self.N - 1, 32)) if need_rows else (None, None)
+        head = (_ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next), _ptr(out["g_cur"]), _ptr(out["g_prev"]),
+                _ptr(out["g_tensions"]), _ptr(out["g_bnd"]))
+        return B, head, out
+
+    def _simulate_vjp_out(self, who, ctl, states, g_states, prev_init, need_bnd, need_par=False, use_nn=False, need_rows=None):
+        """The same for a rollout adjoint -> (B, T, the shared argument list up to ``g_bnd``, the dict of fresh outputs)."""
+        import torch
+        if ctl.dim() != 3 or ctl.shape[2] != 4 or ctl.shape[1] < 1:
+            raise KrError(f"{who}: ctl must be [B, T, 4] with T >= 1; got {tuple(ctl.shape)}")
+        B, T = ctl.shape[0], ctl.shape[1]
+        for name, t in (("states", states), ("g_states", g_states)):
+            if tuple(t.shape) != (T + 1, B, self.N, KR_SLOTS) or t.dtype != ctl.dtype:
+                raise KrError(f"{who}: {name} must be the full history [{T + 1}, {B}, {self.N}, {KR_SLOTS}] of {ctl.dtype} (a "
+                              f"ring of three states does not hold what the backward pass reads); got {tuple(t.shape)} {t.dtype}")
+        if prev_init is not None and (tuple(prev_init.shape) != (B, self.N, KR_SLOTS) or prev_init.dtype != ctl.dtype):
+            raise KrError(f"{who}: prev_init must be [{B}, {self.N}, {KR_SLOTS}] of {ctl.dtype}")
+        new = lambda *shape, dtype=ctl.dtype: torch.empty(shape, dtype=dtype, device=ctl.device)
+        out = dict(g_ctl=new(B, T, 4), g_bnd=new(B, KR_BND) if need_bnd else None,
+                   g_prev_init=new(B, self.N, KR_SLOTS) if prev_init is not None else None,
+                   resid=new(B, T, dtype=torch.float64), status=new(B, T, dtype=torch.int32))
+        if need_par:
+            if use_nn:
+                raise KrError(f"{who}: need_par is served with the MLP off only (kr_{who}_par_batch)")
+            out["g_par"] = new(B, KR_PAR)
+        if need_rows is not None:
+            out["nn_x"], out["nn_g"] = (new(T, B, self.N - 1, 32), new(T, B, self.N - 1, 32)) if need_rows else (None, None)
+        head = (_ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states), _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]))
+        return B, T, head, out
+
     def step_vjp(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, use_nn=False, need_bnd=True, need_par=False):
         """Adjoint of one solved step (``kr_step_vjp_batch``): the cotangent ``g_next[B, N, KR_SLOTS]`` of ``nxt`` ->
         dict with ``g_cur``, ``g_prev`` ``[B, N, KR_SLOTS]``, ``g_tensions[B, 4]``, ``g_bnd[B, KR_BND]`` (None without
         ``need_bnd``), ``resid[B]`` (float64) and ``status[B]`` (int32), all on the device.  ``prev`` may be ``cur``.
         ``need_par``: the call goes through ``kr_step_vjp_par_batch`` (MLP off only) and the dict gains ``g_par[B, KR_PAR]``,
         the gradient of the rod's material parameters (``PAR_BLOCKS``; ``split_par``)."""
-        import torch
-        B = cur.shape[0]
-        for name, t in (("prev", prev), ("cur", cur), ("nxt", nxt), ("g_next", g_next)):
-            if tuple(t.shape) != (B, self.N, KR_SLOTS) or t.dtype != cur.dtype:
-                raise KrError(f"step_vjp: {name} must be [{B}, {self.N}, {KR_SLOTS}] of {cur.dtype}; got {tuple(t.shape)} {t.dtype}")
-        if tuple(tensions.shape) != (B, 4) or tensions.dtype != cur.dtype:
-            raise KrError(f"step_vjp: tensions must be [{B}, 4] of {cur.dtype}; got {tuple(tensions.shape)} {tensions.dtype}")
-        new = lambda *shape, dtype=cur.dtype: torch.empty(shape, dtype=dtype, device=cur.device)
-        out = dict(g_cur=new(B, self.N, KR_SLOTS), g_prev=new(B, self.N, KR_SLOTS), g_tensions=new(B, 4),
-                   g_bnd=new(B, KR_BND) if need_bnd else None, resid=new(B, dtype=torch.float64), status=new(B, dtype=torch.int32))
+        B, head, out = self._step_vjp_out("step_vjp", prev, cur, nxt, tensions, g_next, need_bnd, need_par, use_nn)
+        tail = (_ptr(out["resid"]), _ptr(out["status"]))
         if need_par:
-            if use_nn:
-                raise KrError("step_vjp: need_par is served with the MLP off only (kr_step_vjp_par_batch)")
-            out["g_par"] = new(B, KR_PAR)
-            check(self.lib.kr_step_vjp_par_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
-                                                 _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
-                                                 _ptr(out["g_par"]), _ptr(out["resid"]), _ptr(out["status"]), dtype_code(cur.dtype),
-                                                 _stream()))
-            return out
-        check(self.lib.kr_step_vjp_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
-                                         _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
-                                         _ptr(out["resid"]), _ptr(out["status"]), int(bool(use_nn)), dtype_code(cur.dtype), _stream()))
+            check(self.lib.kr_step_vjp_par_batch(self._h, B, scheme, *head, _ptr(out["g_par"]), *tail, dtype_code(cur.dtype), _stream()))
+        else:
+            check(self.lib.kr_step_vjp_batch(self._h, B, scheme, *head, *tail, int(bool(use_nn)), dtype_code(cur.dtype), _stream()))
         return out
 
     def simulate_vjp(self, ctl, states, g_states, prev_init=None, scheme=KR_EULER, use_nn=False, need_bnd=True, need_par=False):
@@ -777,76 +810,30 @@ class Handle:
         (None without ``need_bnd``), ``g_prev_init`` (None unless ``prev_init`` is given), ``resid[B, T]``, ``status[B, T]``.
         ``need_par``: the call goes through ``kr_simulate_vjp_par_batch`` (MLP off only) and the dict gains
         ``g_par[B, KR_PAR]``, the gradient of the rod's material parameters summed over the steps."""
-        import torch
-        if ctl.dim() != 3 or ctl.shape[2] != 4 or ctl.shape[1] < 1:
-            raise KrError(f"simulate_vjp: ctl must be [B, T, 4] with T >= 1; got {tuple(ctl.shape)}")
-        B, T = ctl.shape[0], ctl.shape[1]
-        for name, t in (("states", states), ("g_states", g_states)):
-            if tuple(t.shape) != (T + 1, B, self.N, KR_SLOTS) or t.dtype != ctl.dtype:
-                raise KrError(f"simulate_vjp: {name} must be the full history [{T + 1}, {B}, {self.N}, {KR_SLOTS}] of {ctl.dtype} (a "
-                              f"ring of three states does not hold what the backward pass reads); got {tuple(t.shape)} {t.dtype}")
-        if prev_init is not None and (tuple(prev_init.shape) != (B, self.N, KR_SLOTS) or prev_init.dtype != ctl.dtype):
-            raise KrError(f"simulate_vjp: prev_init must be [{B}, {self.N}, {KR_SLOTS}] of {ctl.dtype}")
-        new = lambda *shape, dtype=ctl.dtype: torch.empty(shape, dtype=dtype, device=ctl.device)
-        out = dict(g_ctl=new(B, T, 4), g_bnd=new(B, KR_BND) if need_bnd else None,
-                   g_prev_init=new(B, self.N, KR_SLOTS) if prev_init is not None else None,
-                   resid=new(B, T, dtype=torch.float64), status=new(B, T, dtype=torch.int32))
+        B, T, head, out = self._simulate_vjp_out("simulate_vjp", ctl, states, g_states, prev_init, need_bnd, need_par, use_nn)
+        tail = (_ptr(out["resid"]), _ptr(out["status"]))
         if need_par:
-            if use_nn:
-                raise KrError("simulate_vjp: need_par is served with the MLP off only (kr_simulate_vjp_par_batch)")
-            out["g_par"] = new(B, KR_PAR)
-            check(self.lib.kr_simulate_vjp_par_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
-                                                     _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["g_par"]),
-                                                     _ptr(out["resid"]), _ptr(out["status"]), dtype_code(ctl.dtype), _stream()))
-            return out
-        check(self.lib.kr_simulate_vjp_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
-                                             _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["resid"]),
-                                             _ptr(out["status"]), int(bool(use_nn)), dtype_code(ctl.dtype), _stream()))
+            check(self.lib.kr_simulate_vjp_par_batch(self._h, B, T, scheme, *head, _ptr(out["g_par"]), *tail, dtype_code(ctl.dtype),
+                                                     _stream()))
+        else:
+            check(self.lib.kr_simulate_vjp_batch(self._h, B, T, scheme, *head, *tail, int(bool(use_nn)), dtype_code(ctl.dtype), _stream()))
         return out
 
     def step_vjp_nn(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, need_bnd=True, need_rows=True):
         """``step_vjp`` for the model with the handle's MLP on (``kr_step_vjp_nn_batch``): the same dict, plus ``nn_x``,
         ``nn_g`` ``[B, N - 1, 32]`` (None without ``need_rows``) - the network's input at every stored point and the
         cotangent that reaches its output there, the rows of the weight gradient."""
-        import torch
-        B = cur.shape[0]
-        for name, t in (("prev", prev), ("cur", cur), ("nxt", nxt), ("g_next", g_next)):
-            if tuple(t.shape) != (B, self.N, KR_SLOTS) or t.dtype != cur.dtype:
-                raise KrError(f"step_vjp_nn: {name} must be [{B}, {self.N}, {KR_SLOTS}] of {cur.dtype}; got {tuple(t.shape)} {t.dtype}")
-        if tuple(tensions.shape) != (B, 4) or tensions.dtype != cur.dtype:
-            raise KrError(f"step_vjp_nn: tensions must be [{B}, 4] of {cur.dtype}; got {tuple(tensions.shape)} {tensions.dtype}")
-        new = lambda *shape, dtype=cur.dtype: torch.empty(shape, dtype=dtype, device=cur.device)
-        out = dict(g_cur=new(B, self.N, KR_SLOTS), g_prev=new(B, self.N, KR_SLOTS), g_tensions=new(B, 4),
-                   g_bnd=new(B, KR_BND) if need_bnd else None, resid=new(B, dtype=torch.float64), status=new(B, dtype=torch.int32),
-                   nn_x=new(B, self.N - 1, 32) if need_rows else None, nn_g=new(B, self.N - 1, 32) if need_rows else None)
-        check(self.lib.kr_step_vjp_nn_batch(self._h, B, scheme, _ptr(prev), _ptr(cur), _ptr(nxt), _ptr(tensions), _ptr(g_next),
-                                            _ptr(out["g_cur"]), _ptr(out["g_prev"]), _ptr(out["g_tensions"]), _ptr(out["g_bnd"]),
-                                            _ptr(out["resid"]), _ptr(out["status"]), _ptr(out["nn_x"]), _ptr(out["nn_g"]),
-                                            dtype_code(cur.dtype), _stream()))
+        B, head, out = self._step_vjp_out("step_vjp_nn", prev, cur, nxt, tensions, g_next, need_bnd, need_rows=bool(need_rows))
+        check(self.lib.kr_step_vjp_nn_batch(self._h, B, scheme, *head, _ptr(out["resid"]), _ptr(out["status"]), _ptr(out["nn_x"]),
+                                            _ptr(out["nn_g"]), dtype_code(cur.dtype), _stream()))
         return out
 
     def simulate_vjp_nn(self, ctl, states, g_states, prev_init=None, scheme=KR_EULER, need_bnd=True, need_rows=True):
         """``simulate_vjp`` for the model with the handle's MLP on (``kr_simulate_vjp_nn_batch``): the same dict, plus
         ``nn_x``, ``nn_g`` ``[T, B, N - 1, 32]`` (None without ``need_rows``), the rows of the weight gradient per step."""
-        import torch
-        if ctl.dim() != 3 or ctl.shape[2] != 4 or ctl.shape[1] < 1:
-            raise KrError(f"simulate_vjp_nn: ctl must be [B, T, 4] with T >= 1; got {tuple(ctl.shape)}")
-        B, T = ctl.shape[0], ctl.shape[1]
-        for name, t in (("states", states), ("g_states", g_states)):
-            if tuple(t.shape) != (T + 1, B, self.N, KR_SLOTS) or t.dtype != ctl.dtype:
-                raise KrError(f"simulate_vjp_nn: {name} must be the full history [{T + 1}, {B}, {self.N}, {KR_SLOTS}] of {ctl.dtype} (a "
-                              f"ring of three states does not hold what the backward pass reads); got {tuple(t.shape)} {t.dtype}")
-        if prev_init is not None and (tuple(prev_init.shape) != (B, self.N, KR_SLOTS) or prev_init.dtype != ctl.dtype):
-            raise KrError(f"simulate_vjp_nn: prev_init must be [{B}, {self.N}, {KR_SLOTS}] of {ctl.dtype}")
-        new = lambda *shape, dtype=ctl.dtype: torch.empty(shape, dtype=dtype, device=ctl.device)
-        out = dict(g_ctl=new(B, T, 4), g_bnd=new(B, KR_BND) if need_bnd else None,
-                   g_prev_init=new(B, self.N, KR_SLOTS) if prev_init is not None else None,
-                   resid=new(B, T, dtype=torch.float64), status=new(B, T, dtype=torch.int32),
-                   nn_x=new(T, B, self.N - 1, 32) if need_rows else None, nn_g=new(T, B, self.N - 1, 32) if need_rows else None)
-        check(self.lib.kr_simulate_vjp_nn_batch(self._h, B, T, scheme, _ptr(ctl), _ptr(states), _ptr(prev_init), _ptr(g_states),
-                                                _ptr(out["g_prev_init"]), _ptr(out["g_ctl"]), _ptr(out["g_bnd"]), _ptr(out["resid"]),
-                                                _ptr(out["status"]), _ptr(out["nn_x"]), _ptr(out["nn_g"]), dtype_code(ctl.dtype),
-                                                _stream()))
+        B, T, head, out = self._simulate_vjp_out("simulate_vjp_nn", ctl, states, g_states, prev_init, need_bnd, need_rows=bool(need_rows))
+        check(self.lib.kr_simulate_vjp_nn_batch(self._h, B, T, scheme, *head, _ptr(out["resid"]), _ptr(out["status"]), _ptr(out["nn_x"]),
+                                                _ptr(out["nn_g"]), dtype_code(ctl.dtype), _stream()))
         return out
 
     # -- evaluation metrics ------------------------------------------------------

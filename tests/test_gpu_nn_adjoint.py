@@ -286,6 +286,44 @@ def test_simulate_vjp_nn_against_the_oracle_and_the_step_calls(torch_cuda, fx, p
             o += n
 
 
+def test_rollout_forms_share_one_workspace(torch_cuda, fx):
+    """The rollout calls carve one workspace: a typed head, then the tail the form asks for (the network's rows and
+    Jacobians, or the step's parameter gradient).  On one handle with a network set (N = 9, T = 3, fp64): simulate_vjp_nn at
+    B = 5, then simulate_vjp(need_par=True) with the MLP off at B = 2 - the same allocation at another carving - then the
+    first call again.  The third call is the first in every output bit, the second is the same call on a fresh handle."""
+    torch = torch_cuda
+    import krod_grad as kg
+    import krod_native as kn
+    N, T = 9, 3
+    r = robot_for("bc", N, fixture_mlp(fx, "elu64x64"), "elu64x64")
+    h = r._native()
+    ctl0 = fx["roll_bc_N10_T3_elu64x64_ctl"]
+    ctl5 = _dev(torch, np.stack([ctl0 * (1 + 0.01 * b) for b in range(5)]))
+    ctl2 = ctl5[:2].contiguous()
+    st5, _, status5 = kg.forward_states(h, ctl5, tol=1e-12, use_nn=True)
+    st2, _, status2 = kg.forward_states(h, ctl2, tol=1e-12)
+    assert (status5 == 0).all() and (status2 == 0).all()
+    rng = np.random.default_rng(9)
+    g5, g2 = _dev(torch, rng.standard_normal(tuple(st5.shape))), _dev(torch, rng.standard_normal(tuple(st2.shape)))
+
+    def call(vjp, ctl, states, g0, **kw):
+        g = g0.clone()
+        out = vjp(ctl, states, g, **kw)
+        assert (out["status"] == 0).all()
+        return dict(out, g_states=g)
+
+    first = call(h.simulate_vjp_nn, ctl5, st5, g5)
+    par = call(h.simulate_vjp, ctl2, st2, g2, need_par=True)
+    third = call(h.simulate_vjp_nn, ctl5, st5, g5)
+    fresh = kn.Handle(r._params(), r.device)
+    alone = call(fresh.simulate_vjp, ctl2, st2, g2, need_par=True)
+    fresh.close()
+    for n in ("g_states", "g_ctl", "g_bnd", "resid", "status", "nn_x", "nn_g"):
+        assert torch.equal(third[n], first[n]), n
+    for n in ("g_states", "g_ctl", "g_bnd", "g_par", "resid", "status"):
+        assert torch.equal(par[n], alone[n]), n
+
+
 def test_simulate_tips_nn_backward_is_the_direct_call(torch_cuda, fx):
     """simulate_tips_nn(...).sum().backward() fills ctl.grad and every p.grad with what rollout_grad_nn returns for a unit
     tip cotangent."""
