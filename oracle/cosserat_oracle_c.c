@@ -4,6 +4,7 @@
  * Second, independent restatement beside oracle/cosserat_oracle.py, physics only (no MLP):
  *   ode()            cosserat_ode.py:114-166   per-segment spatial derivative
  *   residual_euler() cosserat_ode.py:188-213   explicit-Euler shooting sweep, mutating y, z; z[:, N-1] never written
+ *   residual_rk4()   cosserat_ode.py:215-255   classical RK4 sweep (restated from cosserat_oracle.residual_rk4)
  *   simulate()       knode.py:55-102           BDF2 time loop, straight initial rod, G warm-started
  * The shooting unknowns are found by Newton with a forward-difference Jacobian converged to 1e-12 (the
  * reference calls MINPACK hybrd with xtol 1.5e-8; same root - pinned against the reference's own trajectories
@@ -143,6 +144,45 @@ static void residual_euler(const derived* D, const double* G, double* y, double*
   for (int i = 0; i < 3; ++i) { res[i] = P->F_tip[i] - yl[7 + i]; res[3 + i] = P->M_tip[i] - yl[10 + i]; }
 }
 
+/* cosserat_oracle.residual_rk4: stages 2 and 3 take the midpoint histories (the mean of columns j and j + 1, formed by
+ * the time loop), stage 4 the history of column j + 1; z[:, j] is what stage 1 returns.  yhm[(N-1)*19], zhm[(N-1)*6]. */
+static void residual_rk4(const derived* D, const double* G, double* y, double* z, const double* yh, const double* zh,
+                         const double* yhm, const double* zhm, const double* tf, double* res) {
+  const orc_params* P = D->P;
+  const double ds = D->ds;
+  double* y0 = y;
+  for (int i = 0; i < 3; ++i) y0[i] = P->p0[i];
+  for (int i = 0; i < 4; ++i) y0[3 + i] = P->h0[i];
+  for (int i = 0; i < 6; ++i) y0[7 + i] = G[i];
+  for (int i = 0; i < 3; ++i) { y0[13 + i] = P->q0[i]; y0[16 + i] = P->w0[i]; }
+  for (int j = 0; j < D->N - 1; ++j) {
+    const double* yj = y + 19 * j;
+    double k1[19], k2[19], k3[19], k4[19], ya[19], zs[6];
+    ode(D, yj, yh + 19 * j, zh + 6 * j, tf, k1, z + 6 * j);
+    for (int r = 0; r < 19; ++r) ya[r] = yj[r] + k1[r] * ds / 2;
+    ode(D, ya, yhm + 19 * j, zhm + 6 * j, tf, k2, zs);
+    for (int r = 0; r < 19; ++r) ya[r] = yj[r] + k2[r] * ds / 2;
+    ode(D, ya, yhm + 19 * j, zhm + 6 * j, tf, k3, zs);
+    for (int r = 0; r < 19; ++r) ya[r] = yj[r] + k3[r] * ds;
+    ode(D, ya, yh + 19 * (j + 1), zh + 6 * (j + 1), tf, k4, zs);
+    for (int r = 0; r < 19; ++r) y[19 * (j + 1) + r] = yj[r] + ds * (k1[r] + 2 * (k2[r] + k3[r]) + k4[r]) / 6;
+  }
+  const double* yl = y + 19 * (D->N - 1);
+  for (int i = 0; i < 3; ++i) { res[i] = P->F_tip[i] - yl[7 + i]; res[3 + i] = P->M_tip[i] - yl[10 + i]; }
+}
+
+typedef struct {
+  const derived* D;
+  int rk4;
+  double *y, *z;
+  const double *yh, *zh, *yhm, *zhm, *tf;
+} sweep_ctx;
+
+static void sweep(const sweep_ctx* S, const double* G, double* res) {
+  if (S->rk4) residual_rk4(S->D, G, S->y, S->z, S->yh, S->zh, S->yhm, S->zhm, S->tf, res);
+  else residual_euler(S->D, G, S->y, S->z, S->yh, S->zh, S->tf, res);
+}
+
 static int solve6(double A[6][7], double* x) {
   for (int k = 0; k < 6; ++k) {
     int p = k;
@@ -162,17 +202,18 @@ static int solve6(double A[6][7], double* x) {
   return 0;
 }
 
-/* knode.py:55-102 with a Newton solve per step.  ctl[T][4]; tip_out[T][3] = tip after each solved step;
+/* knode.py:55-102 with a Newton solve per step.  scheme: 0 = Euler sweeps, 1 = RK4 sweeps.  ctl[T][4]; tip_out[T][3] = tip after each solved step;
  * traj_out (nullable) [T+1][25][N] in the reference's row order, entry 0 = initial state.
  * returns the number of steps whose Newton iteration did not converge (or -1 for bad parameters). */
-int orc_simulate(const orc_params* P, int T, const double* ctl, double* tip_out, double* traj_out) {
+int orc_simulate_scheme(const orc_params* P, int T, const double* ctl, double* tip_out, double* traj_out, int scheme) {
   derived D;
-  if (P->N < 2 || derive(P, &D)) return -1;
+  if (P->N < 2 || (scheme != 0 && scheme != 1) || derive(P, &D)) return -1;
   const int N = P->N;
   double* y = calloc((size_t)19 * N, sizeof(double));
   double* z = calloc((size_t)6 * N, sizeof(double));
   double* yp = malloc(sizeof(double) * 19 * N), *zp = malloc(sizeof(double) * 6 * N);
   double* yh = malloc(sizeof(double) * 19 * N), *zh = malloc(sizeof(double) * 6 * N);
+  double* yhm = malloc(sizeof(double) * 19 * N), *zhm = malloc(sizeof(double) * 6 * N);   /* RK4: midpoint histories */
   for (int j = 0; j < N; ++j) {                     /* knode.py:58-64 */
     y[19 * j + 2] = P->L * j / (N - 1);
     y[19 * j + 3] = 1.0;
@@ -193,20 +234,23 @@ int orc_simulate(const orc_params* P, int T, const double* ctl, double* tip_out,
     if (t == T) break;
     for (int i = 0; i < 19 * N; ++i) yh[i] = D.c1 * y[i] + D.c2 * yp[i];    /* knode.py:74-75 */
     for (int i = 0; i < 6 * N; ++i) zh[i] = D.c1 * z[i] + D.c2 * zp[i];
+    for (int i = 0; i < 19 * (N - 1); ++i) yhm[i] = 0.5 * (yh[i] + yh[i + 19]);
+    for (int i = 0; i < 6 * (N - 1); ++i) zhm[i] = 0.5 * (zh[i] + zh[i + 6]);
     memcpy(yp, y, sizeof(double) * 19 * N);
     memcpy(zp, z, sizeof(double) * 6 * N);
     double tf[3] = {0, 0, 0};                       /* cosserat_ode.py:195 */
     for (int k = 0; k < 4; ++k) for (int i = 0; i < 3; ++i) tf[i] += ctl[4 * t + k] * P->tendon_dirs[3 * k + i];
+    const sweep_ctx S = {&D, scheme, y, z, yh, zh, yhm, zhm, tf};
     int ok = 0;
     for (int it = 0; it < 50 && !ok; ++it) {
       double r0[6], A[6][7], d[6];
-      residual_euler(&D, G, y, z, yh, zh, tf, r0);
+      sweep(&S, G, r0);
       for (int c = 0; c < 6; ++c) {
         const double e = 1e-7 * fmax(fabs(G[c]), 1.0);
         double Gp[6], rc[6];
         memcpy(Gp, G, sizeof(Gp));
         Gp[c] += e;
-        residual_euler(&D, Gp, y, z, yh, zh, tf, rc);
+        sweep(&S, Gp, rc);
         for (int i = 0; i < 6; ++i) A[i][c] = (rc[i] - r0[i]) / e;
       }
       for (int i = 0; i < 6; ++i) A[i][6] = r0[i];
@@ -218,18 +262,24 @@ int orc_simulate(const orc_params* P, int T, const double* ctl, double* tip_out,
       for (int i = 0; i < 6; ++i) G[i] -= d[i];
     }
     double rf[6];
-    residual_euler(&D, G, y, z, yh, zh, tf, rf);    /* the sweep at the accepted G is the stored state */
+    sweep(&S, G, rf);   /* the sweep at the accepted G is the stored state */
     if (!ok) ++bad;
     for (int i = 0; i < 3; ++i) tip_out[3 * t + i] = y[19 * (N - 1) + i];
   }
-  free(y); free(z); free(yp); free(zp); free(yh); free(zh);
+  free(y); free(z); free(yp); free(zp); free(yh); free(zh); free(yhm); free(zhm);
   return bad;
+}
+
+/* Euler sweeps: the entry point as it has always been (callers built against it keep working). */
+int orc_simulate(const orc_params* P, int T, const double* ctl, double* tip_out, double* traj_out) {
+  return orc_simulate_scheme(P, T, ctl, tip_out, traj_out, 0);
 }
 
 #ifdef ORC_SELFTEST
 /* `make asan`: the same file as a standalone program under -fsanitize=address,undefined (SURVEY section 5 asks for a
  * sanitizer build of the CPU restatement).  setup_robot(None) parameters (knode.py:11-20), per-rod sine tensions, N = 10,
- * 20, 100, 400 with and without the trajectory buffer; exit code 1 on a non-finite tip or an unconverged step. */
+ * 20, 100, 400 with and without the trajectory buffer, N = 100, 400 also with RK4 sweeps; exit code 1 on a non-finite tip
+ * or an unconverged step. */
 #include <stdio.h>
 int main(void) {
   const int Ns[4] = {10, 20, 100, 400}, Ts[4] = {40, 40, 20, 8};
@@ -257,6 +307,13 @@ int main(void) {
       int finite = 1;
       for (int i = 0; i < 3 * T; ++i) finite &= isfinite(tip[i]) != 0;
       printf("N=%d T=%d traj=%d unconverged=%d tip=(%.6f %.6f %.6f)\n", Ns[c], T, with_traj, bad, tip[3 * T - 3], tip[3 * T - 2], tip[3 * T - 1]);
+      if (bad != 0 || !finite) fail = 1;
+    }
+    if (Ns[c] >= 100) {   /* RK4 sweeps, where the preset is solvable under them (not on a coarse grid) */
+      const int bad = orc_simulate_scheme(&P, T, ctl, tip, traj, 1);
+      int finite = 1;
+      for (int i = 0; i < 3 * T; ++i) finite &= isfinite(tip[i]) != 0;
+      printf("rk4: N=%d T=%d steps not converged: %d tip=(%.6f %.6f %.6f)\n", Ns[c], T, bad, tip[3 * T - 3], tip[3 * T - 2], tip[3 * T - 1]);
       if (bad != 0 || !finite) fail = 1;
     }
     free(ctl); free(tip); free(traj);

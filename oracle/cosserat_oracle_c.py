@@ -30,6 +30,8 @@ def load():
         _lib = C.CDLL(path)
         _lib.orc_simulate.restype = C.c_int
         _lib.orc_simulate.argtypes = [C.POINTER(OrcParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.orc_simulate_scheme.restype = C.c_int
+        _lib.orc_simulate_scheme.argtypes = _lib.orc_simulate.argtypes + [C.c_int]
     return _lib
 
 
@@ -43,10 +45,11 @@ def params_from(P) -> OrcParams:
     return o
 
 
-def simulate(P, ctl, traj=True, c2_scale=1.0):
+def simulate(P, ctl, traj=True, c2_scale=1.0, scheme="euler"):
     """-> (tip[T, 3], traj[T+1, 25, N] or None, n_unconverged).  Releases the GIL: call it from threads.
     c2_scale != 1 (a test of the tests: a BDF2 history coefficient that is slightly wrong) is a process-wide setting for
-    the duration of the call - not for threads."""
+    the duration of the call - not for threads.  ``scheme``: "euler" or "rk4" sweeps, as in ``cosserat_oracle.simulate``."""
+    code = {"euler": 0, "rk4": 1}[scheme]
     lib = load()
     scale = C.c_double.in_dll(lib, "orc_c2_scale")
     ctl = np.ascontiguousarray(ctl, dtype=np.float64).reshape(-1, 4)
@@ -56,7 +59,7 @@ def simulate(P, ctl, traj=True, c2_scale=1.0):
     o = params_from(P)
     scale.value = float(c2_scale)
     try:
-        bad = lib.orc_simulate(C.byref(o), T, ctl.ctypes.data, tip.ctypes.data, tr.ctypes.data if traj else None)
+        bad = lib.orc_simulate_scheme(C.byref(o), T, ctl.ctypes.data, tip.ctypes.data, tr.ctypes.data if traj else None, code)
     finally:
         scale.value = 1.0
     if bad < 0:

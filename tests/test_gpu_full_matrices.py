@@ -30,7 +30,8 @@ Consistency that needs no oracle: the tips of a 3-slot ring call and of the driv
 serves full matrices; the twin's driver calls on an overlapped kernel are held to the tip bound instead, see
 ``test_step_kernels`` - and on K2b and K2c rod b's result is bit-identical to that of its own B = 1 call.
 
-Scope: Euler sweeps.  RK4 sweeps with full matrices are not tested here.  Measured errors: LABBOOK.md (full material
+Scope: Euler sweeps.  RK4 sweeps, with full and with diagonal matrices, are held by tests/test_gpu_rk4_sweeps.py, which
+runs them through ``run`` and ``check`` below.  Measured errors: LABBOOK.md (full material
 matrices)."""
 import numpy as np
 import pytest
@@ -105,9 +106,10 @@ def _handle(monkeypatch, kernel, N, variant, net=None):
     return h
 
 
-def run(torch, h, ctl_np, form, dtype, ran, use_nn=False):
+def run(torch, h, ctl_np, form, dtype, ran, use_nn=False, scheme=0):
     """One run of ctl[B, T, 4] from the straight rod -> (tips [B, T, 3], status [B, T], {entry: states [B, 25, N]} of
-    every entry the form leaves behind: all of them, or T - 2 .. T of a ring); asserts the kernel after every call."""
+    every entry the form leaves behind: all of them, or T - 2 .. T of a ring); asserts the kernel after every call.
+    ``scheme``: KR_EULER (0) or KR_RK4 of every sweep."""
     B, T = ctl_np.shape[:2]
     dt = torch.float64 if dtype == "f64" else torch.float32
     tol = 1e-12 if dtype == "f64" else 0.0
@@ -124,7 +126,7 @@ def run(torch, h, ctl_np, form, dtype, ran, use_nn=False):
     h.init_straight(st[0])
     try:
         if form != "driver":
-            h.simulate(ctl, st, G, ring=form == "ring", tip=tip, status=status, tol=tol, use_nn=use_nn)
+            h.simulate(ctl, st, G, ring=form == "ring", tip=tip, status=status, tol=tol, use_nn=use_nn, scheme=scheme)
             torch.cuda.synchronize()
             check_kernel()
             slot = (lambda e: e) if form == "full" else (lambda e: e % 3)
@@ -137,7 +139,7 @@ def run(torch, h, ctl_np, form, dtype, ran, use_nn=False):
                 tp = torch.full((B, n, 3), float("nan"), dtype=dt, device=DEV)
                 sx = torch.full((B, n), -1, dtype=torch.int32, device=DEV)
                 h.simulate(ctl[:, a:a + n].contiguous(), st, G, ring=True, tip=tp, status=sx, prev_init=prev, tol=tol,
-                           use_nn=use_nn)
+                           use_nn=use_nn, scheme=scheme)
                 torch.cuda.synchronize()
                 check_kernel()
                 tip[:, a:a + n], status[:, a:a + n] = tp, sx
