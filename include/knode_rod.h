@@ -876,7 +876,7 @@ int kr_step_vjp_batch(kr_handle* h, int64_t B, int scheme,
  * g_states[t] += g_cur and g_states[t-1] += g_prev, in this order, in the element type of the arrays.  Step 0's g_prev
  * goes into g_states[0] when state_prev_init is NULL, otherwise it is written to g_prev_init[B][N][KR_SLOTS] (nullable).
  * g_ctl[B][T][4] = g_tensions of step t; g_bnd[B][KR_BND] = the sum over the steps, t = T-1 first (the handle's
- * boundary is constant in time); resid[B][T], status[B][T] per step.  g_prev_init, g_ctl, g_bnd, resid, status may be
+ * boundary is constant in time; kr_simulate_vjp_table_batch keeps it per step); resid[B][T], status[B][T] per step.  g_prev_init, g_ctl, g_bnd, resid, status may be
  * NULL.  A rod whose step t0 reports a nonzero status has NaN in g_ctl[b][t0] and, through g_states[t0], in every
  * earlier step's outputs; other rods are bit for bit the clean call.
  * One launch per step plus the accumulations; uses the handle's scratch (two state-sized buffers).
@@ -941,8 +941,9 @@ int kr_simulate_vjp_nn_batch(kr_handle* h, int64_t B, int64_t T, int scheme, con
  * are bit for bit those of the clean call.  The KR_F32 call is the KR_F64 call on the upcast inputs, rounded to float.
  * Refusals as for kr_step_vjp_batch (KR_E_UNSUPPORTED for scheme == KR_RK4; KR_E_ARG for a null handle, state, g_next or
  * tensions pointer, B < 1, a bad dtype), each with a message, nothing launched and no output byte written.
- * Not served: the MLP-on form (kr_step_vjp_nn_batch has no g_par); per-rod parameters (table, loads, boundary, bank: every
- * rod of a call shares the handle's parameters, and g_par is per rod only because the states are); RK4; del_t. */
+ * Not served: the MLP-on form (kr_step_vjp_nn_batch has no g_par); RK4; del_t.  Every rod of a call shares the handle's
+ * parameters, and g_par is per rod only because the states are: per-rod parameters (table, loads, boundary) are served by
+ * kr_step_vjp_table_batch / kr_simulate_vjp_table_batch below, a bank (the MLP on) by nothing yet. */
 #define KR_PAR 43
 int kr_step_vjp_par_batch(kr_handle* h, int64_t B, int scheme,
                           const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
@@ -960,6 +961,51 @@ int kr_step_vjp_par_batch(kr_handle* h, int64_t B, int scheme,
 int kr_simulate_vjp_par_batch(kr_handle* h, int64_t B, int64_t T, int scheme, const void* ctl, const void* states,
                               const void* state_prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd,
                               void* g_par, double* resid, int32_t* status, int dtype, void* stream);
+
+/* ---- the adjoint of a heterogeneous batch: per-rod parameters, per-step boundary data --------------------------------------
+ * kr_step_vjp_par_batch (one pass of the loop of knode.py:70-100 around the sweep of cosserat_ode.py:188-213, MLP off, Euler
+ * sweep) with rod b taking row b of a parameter table (kr_param_table_create) in place of the handle's parameters: the
+ * backward side of kr_simulate_batch_table / _loads / _boundary.  B is the table's B; every array is shaped as there.
+ * Rod b's outputs are the step adjoint stated at kr_step_vjp_batch and kr_step_vjp_par_batch with P = row b (c0, c1, c2,
+ * ds, the material constants, tendon_dirs) and, for g_par, row b's E, r, rho, vstar, g (kept by the table in one more device
+ * array of nine doubles per row; nothing a forward kernel receives changed).  Table rows are diagonal and 9 <= N <= 128
+ * (kr_param_table_check).  The call takes no bnd or loads array: record 0 of state_next holds the base values the step used
+ * exactly (kr_simulate_batch_boundary), they are read from there like every other state value, and the tip wrench enters
+ * no derivative - g_bnd[b] IS the gradient with respect to the KR_BND boundary values rod b's step used, wherever they came
+ * from (its row, loads[b][t], bnd[b][t]).
+ * Arithmetic is fp64 whatever `dtype`; the KR_F32 call is the KR_F64 call on the upcast inputs, rounded, bit for bit.  One
+ * wavefront per rod, no atomics, none of the handle's scratch; the row is read in place with scalar loads (the rod index is
+ * wavefront-uniform) and no row beyond the table's last is addressed.  A rod's outputs do not depend on the batch or on its
+ * position in it.  g_par[B][KR_PAR] is nullable: NULL skips the second launch, and with it every other output is bit for bit
+ * that of the call without it, written by the kernel without g_par, launched first (the rule of kr_step_vjp_par_batch).
+ * status, NaN rules and nullable outputs per rod as for kr_step_vjp_batch / kr_step_vjp_par_batch.
+ * Refusals, each with a message, nothing launched and no output byte written, in this order: KR_E_ARG for a null handle, a
+ * null table, a bad dtype, a null state, g_next or tensions pointer; KR_E_ARG for a table of another device or whose N or
+ * del_t differ from the handle's (the handle lends its device, its stream ordering and, for the rollout, its scratch: a
+ * "carrier"; its own parameters are not read); KR_E_UNSUPPORTED for scheme == KR_RK4.  There is no use_nn: the calls
+ * differentiate the physics alone and do not read the handle's network.
+ * Not served: the MLP-on form with a table or a bank; RK4; full matrices in a row; del_t. */
+int kr_step_vjp_table_batch(kr_handle* h, const kr_param_table* t, int scheme,
+                            const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
+                            const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd, void* g_par,
+                            double* resid, int32_t* status, int dtype, void* stream);
+
+/* kr_simulate_vjp_par_batch for the table form (knode.py:55-102): DEFINED as the same composition of
+ * kr_step_vjp_table_batch calls and equal to it bit for bit; g_par (nullable) = the sum over the steps of the step's,
+ * t = T-1 first, from zero.  g_bnd (nullable):
+ *   bnd_per_step == 0   g_bnd[B][KR_BND], the sum over the steps from zero, t = T-1 first: the gradient with respect to the
+ *                       row's constant boundary values (a kr_simulate_batch_table rollout)
+ *   bnd_per_step == 1   g_bnd[B][T][KR_BND], entry [b][t] = the g_bnd of step t, bit for bit: the gradient with respect to
+ *                       bnd[b][t] of kr_simulate_batch_boundary, and its last six columns the gradient with respect to
+ *                       loads[b][t] of kr_simulate_batch_loads
+ * A rod whose step t0 reports a nonzero status has NaN in g_bnd[b][t0] and, through g_states[t0], in every earlier step's
+ * outputs (bnd_per_step == 1; in all of g_bnd[b] otherwise).  Scratch: that of kr_simulate_vjp_par_batch.
+ * Refusals as for kr_step_vjp_table_batch, with KR_E_ARG for T < 1 after the dtype, for a null ctl, states or g_states, and
+ * for a bnd_per_step other than 0 or 1. */
+int kr_simulate_vjp_table_batch(kr_handle* h, const kr_param_table* t, int64_t T, int scheme, const void* ctl,
+                                const void* states, const void* state_prev_init, void* g_states, void* g_prev_init,
+                                void* g_ctl, void* g_bnd, int bnd_per_step, void* g_par, double* resid, int32_t* status,
+                                int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
 //   constexpr bool PAR   the gradient of the material parameters goes into Q.g_par; Q (AdjPar<T>) is read only where PAR holds
 //   constexpr bool NNON  the network's input Jacobian joins the per-point derivative and pass 2 emits the rows of the weight
 //                        gradient; NN (AdjNn<T>) is read only where NNON holds
+// The table kernels (kr_adj_tab.hip) include this text as it is: they bind P to the rod's row and Q to the rod's parameters
+// before the include, per rod instead of per launch, so the body needs no form for them.
 // A kernel without a form declares an empty Q / NN.  PAR and NNON are not dependent on T, so a discarded branch is still
 // type-checked (jc exists in every form), and whatever a form alone needs folds to a constant without it (q0, own): a
 // live declaration moves the register allocation of the kernels that never read it.

@@ -2,8 +2,9 @@
 // tangents of the physics on dual numbers, the network's and the parameters' additions to them, the 6 x 6 solve, the ONE
 // composition over a stored rollout with its accumulation kernel, and the ONE path from a C entry point to a launch
 // (adj_step_entry, adj_simulate_entry).  The forms are kr_adj.hip (MLP off), kr_adj_par.hip (MLP off, with the gradient of
-// the material parameters) and kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative); the mapping
-// is described in kr_adj.hip.  The recursion of one rod, the body of all three step kernels, is kr_adj_body.inc.
+// the material parameters), kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative) and kr_adj_tab.hip
+// (MLP off, rod b with row b of a parameter table, without and with the parameter gradient); the mapping is described in
+// kr_adj.hip.  The recursion of one rod, the body of all three step kernels, is kr_adj_body.inc.
 #pragma once
 #include "kr_internal.hpp"
 #include "kr_point_dual.hpp"
@@ -285,6 +286,11 @@ static int launch_add(T* dst, const T* src, int64_t n, hipStream_t s) {
   return KR_OK;
 }
 
+// dst[b][k] = src[b][k], k < KR_BND, the rows of dst `stride` elements apart: the step's boundary gradient put where a
+// per-step rollout keeps it (kr_adj_tab.hip: adj_put_kernel; n = B KR_BND)
+int launch_put(float* dst, const float* src, int64_t n, int64_t stride, hipStream_t s);
+int launch_put(double* dst, const double* src, int64_t n, int64_t stride, hipStream_t s);
+
 int launch_step_vjp_plain(kr_handle* h, const AdjArgs<float>& A, hipStream_t s);   // (kr_adj.hip: step_vjp_kernel)
 int launch_step_vjp_plain(kr_handle* h, const AdjArgs<double>& A, hipStream_t s);
 
@@ -292,13 +298,14 @@ int launch_step_vjp_plain(kr_handle* h, const AdjArgs<double>& A, hipStream_t s)
 //   step adjoint of (states[t - 1], states[t], states[t + 1], ctl[:, t]) with g_next = g_states[t + 1]
 //   g_states[t] += g_cur;  g_states[t - 1] += g_prev  (in this order, in the element type of the arrays)
 //   g_bnd += the step's, g_par += the step's (from zero, t = T - 1 first)
+//   bnd_per_step (the table form): g_bnd is [B][T][KR_BND] and g_bnd[b][t] = the step's, copied instead of added
 // The workspace is a T-typed head (w_cur, w_prev, w_bnd) and, at the next 256-byte boundary, the tail_bytes the form asks
 // for: w_par[B][KR_PAR] of T with g_par, the network's rows and Jacobians (doubles) with the MLP on.
 // launch(h, A, tail, t, s): the step adjoint of step t (tail: null when tail_bytes is 0)
 template <typename T, typename Launch>
 static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T* ctl, const T* states, const T* prev_init, T* g_states,
                               T* g_prev_init, T* g_ctl, T* g_bnd, T* g_par, double* resid, int32_t* status, size_t tail_bytes,
-                              hipStream_t s, Launch launch) {
+                              hipStream_t s, Launch launch, bool bnd_per_step = false) {
   const int64_t slot = B * h->params.N * KR_SLOTS;
   const size_t head = ((size_t)(2 * slot + B * KR_BND) * sizeof(T) + 255) / 256 * 256;
   if (int rc = ensure_ws(h, head + tail_bytes)) return rc;
@@ -307,7 +314,7 @@ static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T*
   T* w_bnd = w_prev + slot;
   void* tail = tail_bytes ? static_cast<char*>(h->ws) + head : nullptr;
   T* w_par = static_cast<T*>(tail);  // (read with g_par only)
-  if (g_bnd) KR_HIP(hipMemsetAsync(g_bnd, 0, (size_t)B * KR_BND * sizeof(T), s));
+  if (g_bnd && !bnd_per_step) KR_HIP(hipMemsetAsync(g_bnd, 0, (size_t)B * KR_BND * sizeof(T), s));
   if (g_par) KR_HIP(hipMemsetAsync(g_par, 0, (size_t)B * KR_PAR * sizeof(T), s));
   for (int64_t t = T_steps - 1; t >= 0; --t) {
     const bool into_init = t == 0 && prev_init != nullptr;
@@ -332,7 +339,9 @@ static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T*
     if (!into_init)
       if (int rc = launch_add<T>(g_states + (t > 0 ? t - 1 : 0) * slot, w_prev, slot, s)) return rc;
     if (g_bnd)
-      if (int rc = launch_add<T>(g_bnd, w_bnd, B * KR_BND, s)) return rc;
+      if (int rc = bnd_per_step ? launch_put(g_bnd + t * KR_BND, w_bnd, B * KR_BND, T_steps * KR_BND, s)
+                                : launch_add<T>(g_bnd, w_bnd, B * KR_BND, s))
+        return rc;
     if (g_par)
       if (int rc = launch_add<T>(g_par, w_par, B * KR_PAR, s)) return rc;
   }
@@ -375,7 +384,8 @@ static int adj_step_entry(const char* api, kr_handle* h, int64_t B, const void* 
 template <typename Refuse, typename Launch>
 static int adj_simulate_entry(const char* api, kr_handle* h, int64_t B, int64_t T_steps, const void* ctl, const void* states,
                               const void* prev_init, void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd, void* g_par,
-                              double* resid, int32_t* status, int dtype, void* stream, Refuse refuse, size_t tail_bytes, Launch launch) {
+                              double* resid, int32_t* status, int dtype, void* stream, Refuse refuse, size_t tail_bytes, Launch launch,
+                              bool bnd_per_step = false) {
   KR_ADJ_ARG(!h, "null handle");
   KR_ADJ_ARG(dtype != KR_F32 && dtype != KR_F64, "dtype must be KR_F32 or KR_F64");
   KR_ADJ_ARG(B < 1 || B > 0x7FFFFFFFll, std::string(api) + ": B must be in [1, 2^31 - 1]");
@@ -387,7 +397,7 @@ static int adj_simulate_entry(const char* api, kr_handle* h, int64_t B, int64_t 
   auto run = [&](auto* elem) {
     using T = std::remove_pointer_t<decltype(elem)>;
     return simulate_vjp_steps<T>(h, B, T_steps, (const T*)ctl, (const T*)states, (const T*)prev_init, (T*)g_states, (T*)g_prev_init,
-                                 (T*)g_ctl, (T*)g_bnd, (T*)g_par, resid, status, tail_bytes, s, launch);
+                                 (T*)g_ctl, (T*)g_bnd, (T*)g_par, resid, status, tail_bytes, s, launch, bnd_per_step);
   };
   return dtype == KR_F32 ? run((float*)nullptr) : run((double*)nullptr);
 }

@@ -1034,6 +1034,7 @@ int kr_param_table_destroy(kr_param_table* t) {
   if (t->rows_f) (void)hipFree(t->rows_f);
   if (t->rows_d) (void)hipFree(t->rows_d);
   if (t->L) (void)hipFree(t->L);
+  if (t->par) (void)hipFree(t->par);
   delete t;
   return KR_OK;
 }
@@ -1050,13 +1051,16 @@ int kr_param_table_create(kr_handle* h, int64_t B, const kr_params* rods_host, k
   }
   std::vector<RodConst<float>> rf((size_t)B);
   std::vector<RodConst<double>> rd((size_t)B);
-  std::vector<double> Ls((size_t)B);
+  std::vector<double> Ls((size_t)B), par((size_t)B * 9);
   for (int64_t b = 0; b < B; ++b) {
     kr_derived d{};
     if (int rc = derive(rods_host[b], d)) return rc;
     fill_consts(rods_host[b], d, rf[(size_t)b]);
     fill_consts(rods_host[b], d, rd[(size_t)b]);
     Ls[(size_t)b] = rods_host[b].L;
+    const kr_params& r = rods_host[b];
+    const double q[9] = {r.E, r.r, r.rho, r.vstar[0], r.vstar[1], r.vstar[2], r.g[0], r.g[1], r.g[2]};
+    for (int k = 0; k < 9; ++k) par[(size_t)b * 9 + k] = q[k];
   }
   kr_param_table* t = new kr_param_table();
   t->device = h->device;
@@ -1067,10 +1071,12 @@ int kr_param_table_create(kr_handle* h, int64_t B, const kr_params* rods_host, k
   hipError_t e = hipMalloc((void**)&t->rows_f, sizeof(RodConst<float>) * (size_t)B);
   if (e == hipSuccess) e = hipMalloc((void**)&t->rows_d, sizeof(RodConst<double>) * (size_t)B);
   if (e == hipSuccess) e = hipMalloc((void**)&t->L, sizeof(double) * (size_t)B);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->par, sizeof(double) * par.size());
   // (synchronous copies from pageable memory: the table is complete on the device when this returns)
   if (e == hipSuccess) e = hipMemcpy(t->rows_f, rf.data(), sizeof(RodConst<float>) * (size_t)B, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(t->rows_d, rd.data(), sizeof(RodConst<double>) * (size_t)B, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(t->L, Ls.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(t->par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     kr_param_table_destroy(t);
     return hip_fail(e, "kr_param_table_create");

@@ -129,6 +129,7 @@ struct kr_param_table {
   kr::RodConst<float>* rows_f = nullptr;   // [B], device
   kr::RodConst<double>* rows_d = nullptr;  // [B], device
   double* L = nullptr;                     // [B], device: rod lengths (kr_state_init_straight_table)
+  double* par = nullptr;                   // [B][9], device: E, r, rho, vstar[3], g[3] - what kr_derive consumed (kr_adj_tab.hip)
 };
 
 // Bank of K networks of one shape (kr_mlp_bank_create): every network packed like the handle's own (the gather plan

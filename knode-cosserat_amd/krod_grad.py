@@ -11,6 +11,10 @@ d(tension history) costs about one forward rollout instead of 4 T + 1 of them by
 * ``rollout_grad(..., physical=True)`` / ``simulate_tips_physical(robot, ctl, theta)``: also the gradient of the rod's
   material parameters E, r, rho, L, vstar, g, Bse, Bbt, C, tendon_dirs (``kr_simulate_vjp_par_batch``) - what a calibration
   of the rod against a recorded run needs, in place of 2 x 43 forward rollouts by finite differences.
+* ``rollout_grad(..., robots=[...])`` / ``simulate_tips_batch(robot, robots, ctl, theta, base_motion, tip_loads)``: the
+  backward side of a heterogeneous batch (``kr_simulate_vjp_table_batch``) - rod b with the parameters of ``robots[b]``, the
+  parameter gradients per rod (many rods, or many starting guesses of one rod, calibrated in one backward pass), and the
+  gradient with respect to a base trajectory or a tip-wrench history, step by step.
 * ``rollout_grad_nn`` / ``simulate_tips_nn``: the same for the KNODE model, physics plus the residual MLP in every sweep
   (``kr_simulate_vjp_nn_batch``) - and the gradient of a rollout loss with respect to the network's weights, which the
   reference never had (it trains one step ahead, physics_train.py:250-259).
@@ -98,7 +102,35 @@ def _rollout(h, vjp, ctl, states, g_states, g_tips, prev_init, dtype, **kw):
     return out, res
 
 
-def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None, dtype="f64", physical=False):
+def _check_robots(who, robots, B):
+    """one robot per rod, none with its MLP on (no library call, no device)"""
+    robots = list(robots)
+    if len(robots) != B:
+        raise kn.KrError(f"{who}: robots holds {len(robots)} rods, ctl {B}")
+    for b, r in enumerate(robots):
+        if getattr(r, "_use_nn", False):
+            raise kn.KrError(f"{who}: rod {b}: the adjoint of a table call differentiates the physics alone; a robot with its MLP on "
+                             "is not served (nothing falls back to the physics)")
+    return robots
+
+
+def _table_rows(who, robot, robots, B):
+    """The KrParams rows of ``robots`` for a table call of the adjoint, checked on the host without the library: one robot
+    per rod, none with its MLP on, N and del_t the carrier's.  (What a row may hold - diagonal matrices, 9 <= N <= 128 - is
+    checked by the library when the table is made.)"""
+    robots = _check_robots(who, robots, B)
+    base = robot._params()
+    rows = [r._params() for r in robots]
+    for b, p in enumerate(rows):
+        for f in ("N", "del_t"):
+            if getattr(p, f) != getattr(base, f):
+                raise kn.KrError(f"{who}: rod {b}: field {f} = {getattr(p, f)} differs from the carrier robot's {getattr(base, f)} "
+                                 "(N and del_t are shared by all rods of a launch)")
+    return rows
+
+
+def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None, dtype="f64", physical=False, robots=None,
+                 per_step_boundary=False):
     """Backward pass over a stored rollout of ``robot`` (MLP off): ``ctl[B, T, 4]`` and the FULL history
     ``states[T + 1, B, N, KR_SLOTS]`` of the forward call (host arrays or device tensors; a ring of three states does not
     hold what is needed and is refused).  The loss enters through ``g_states[T + 1, B, N, KR_SLOTS]`` = dL/dstates and / or
@@ -111,9 +143,27 @@ def rollout_grad(robot, ctl, states, g_states=None, g_tips=None, prev_init=None,
     6 x 6 adjoint solve; ``status`` [B, T] (nonzero: that rod's gradients are NaN from that step back).
     ``physical``: the dict also holds ``physical``, a dict of host arrays dL/d(material parameter) per rod, keyed ``E``,
     ``r``, ``rho``, ``L`` [B], ``vstar``, ``g``, ``C`` [B, 3], ``Bse``, ``Bbt`` [B, 3, 3] (every entry an independent
-    variable), ``tendon_dirs`` [B, 4, 3] (``kr_simulate_vjp_par_batch``; a rod with a nonzero status has NaN in all)."""
+    variable), ``tendon_dirs`` [B, 4, 3] (``kr_simulate_vjp_par_batch``; a rod with a nonzero status has NaN in all).
+    ``robots`` (one ``CosseratRod`` per rod, as for ``knode.simulate_batch(robots=...)``): the stored rollout is that of a
+    heterogeneous batch, rod b with the parameters of ``robots[b]``, and the call takes the table form
+    (``kr_simulate_vjp_table_batch``; ``robot`` carries N, del_t and the device handle): ``physical`` is then the gradient of
+    rod b's OWN parameters, and with ``per_step_boundary`` ``boundary`` is [B, T, KR_BND] - entry [b, t] the gradient with
+    respect to the boundary values rod b's step t used (``base_motion[b, t]``, then ``tip_loads[b, t]``) - instead of their
+    sum over the steps."""
     _check_robot(robot)
     _check_rollout("rollout_grad", ctl, states, g_states, g_tips)
+    if robots is None and per_step_boundary:
+        raise kn.KrError("rollout_grad: per_step_boundary needs robots=[...] (the handle's boundary is constant in time)")
+    if robots is not None:
+        rows = _table_rows("rollout_grad", robot, robots, tuple(ctl.shape)[0])
+        h = robot._native()
+        with h.param_table(rows) as table:
+            vjp = lambda *a, **kw: h.simulate_vjp_table(table, *a, **kw)
+            out, res = _rollout(h, vjp, ctl, states, g_states, g_tips, prev_init, dtype, need_par=bool(physical),
+                                bnd_per_step=bool(per_step_boundary))  # (the host copies of _rollout wait for the call)
+        if physical:
+            res["physical"] = {k: np.ascontiguousarray(v) for k, v in kn.split_par(out["g_par"].cpu().numpy()).items()}
+        return res
     h = robot._native()
     out, res = _rollout(h, h.simulate_vjp, ctl, states, g_states, g_tips, prev_init, dtype, need_par=bool(physical))
     if physical:
@@ -228,6 +278,111 @@ def simulate_tips_physical(robot, ctl, theta, dtype="f64", tol=1e-12):
     _check_theta(theta, "simulate_tips_physical")
     names = tuple(theta)
     return _SimulateTipsPhysical.apply(ctl, robot, _tdt(dtype), float(tol), names, *[theta[k] for k in names])
+
+
+# ---- a heterogeneous batch: per-rod parameters, a base trajectory and a wrench history as leaves ---------------------------
+def _check_theta_batch(theta, B, who):
+    if not isinstance(theta, dict):
+        raise kn.KrError(f"{who}: theta must be a dict of torch tensors keyed by parameter name ({', '.join(PHYSICAL_SHAPES)})")
+    for k, v in theta.items():
+        if k not in PHYSICAL_SHAPES:
+            raise kn.KrError(f"{who}: unknown parameter {k!r}; the differentiable ones are {', '.join(PHYSICAL_SHAPES)}")
+        if not isinstance(v, torch.Tensor):
+            raise kn.KrError(f"{who}: theta[{k!r}] must be a torch tensor (it is a leaf the gradient is connected to)")
+        if tuple(v.shape) != (B, *PHYSICAL_SHAPES[k]):
+            raise kn.KrError(f"{who}: theta[{k!r}] must have shape {(B, *PHYSICAL_SHAPES[k])} (one value per rod); got {tuple(v.shape)}")
+
+
+def _check_history(name, x, B, T, width, who):
+    shape = tuple(np.shape(x)) if not isinstance(x, torch.Tensor) else tuple(x.shape)
+    if shape != (B, T, width):
+        raise kn.KrError(f"{who}: {name} must be [B, T, {width}] = [{B}, {T}, {width}]; got {shape}")
+
+
+class _SimulateTipsBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, robot, robots, tdt, tol, names, base_motion, tip_loads, *values):
+        for b, r in enumerate(robots):  # theta[k][b] -> robots[b], which keeps it
+            _write_theta(r, names, [v[b] for v in values])
+        h = robot._native()
+        dev = f"cuda:{h.device}"
+        rows = _table_rows("simulate_tips_batch", robot, robots, ctl.shape[0])
+        table = h.param_table(rows)
+        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
+        B, T = ctl_t.shape[0], ctl_t.shape[1]
+        on_dev = lambda x: torch.as_tensor(x.detach() if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)).to(device=dev, dtype=tdt)
+        loads_t = bnd_t = None
+        if base_motion is not None:  # a boundary call: the base history, then the wrench history or each rod's own wrench
+            bnd_t = torch.empty((B, T, kn.KR_BND), dtype=tdt, device=dev)
+            bnd_t[:, :, :13] = on_dev(base_motion)
+            if tip_loads is not None:
+                bnd_t[:, :, 13:] = on_dev(tip_loads)
+            else:
+                own = np.array([list(p.F_tip[:]) + list(p.M_tip[:]) for p in rows], dtype=np.float64)
+                bnd_t[:, :, 13:] = torch.as_tensor(own, device=dev).to(tdt)[:, None, :]
+        elif tip_loads is not None:
+            loads_t = on_dev(tip_loads).contiguous()
+        states = h.new_state(B, tdt, n_slots=T + 1)
+        h.init_straight(states[0], table=table)
+        G = torch.zeros((B, 6), dtype=tdt, device=dev)
+        tip = torch.empty((B, T, 3), dtype=tdt, device=dev)
+        status = torch.zeros((B, T), dtype=torch.int32, device=dev)
+        h.simulate(ctl_t, states, G, ring=False, tip=tip, status=status, tol=tol, table=table, loads=loads_t, bnd=bnd_t)
+        bad = int((status != 0).sum())
+        if bad:
+            import warnings
+            warnings.warn(f"simulate_tips_batch: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the gradient of "
+                          "those rods is not that of the solved step", RuntimeWarning)
+        ctx.h, ctx.table, ctx.ctl_t, ctx.states, ctx.names = h, table, ctl_t, states, names
+        ctx.like, ctx.vlike, ctx.base_like, ctx.loads_like = ctl, values, base_motion, tip_loads
+        return tip.to(device=ctl.device, dtype=ctl.dtype)
+
+    @staticmethod
+    def backward(ctx, g_tips):
+        h, states = ctx.h, ctx.states
+        leaf = lambda x: isinstance(x, torch.Tensor) and x.requires_grad
+        need_bnd = leaf(ctx.base_like) or leaf(ctx.loads_like)
+        out = h.simulate_vjp_table(ctx.table, ctx.ctl_t, states, _tip_cotangent(h, states, g_tips), need_bnd=need_bnd,
+                                   bnd_per_step=True, need_par=bool(ctx.names))
+        like = lambda g, x: g.to(device=x.device, dtype=x.dtype)
+        by_name = kn.split_par(out["g_par"]) if ctx.names else {}  # per rod: [B, *shape], NOT summed
+        return (like(out["g_ctl"], ctx.like), None, None, None, None, None,
+                like(out["g_bnd"][:, :, :13], ctx.base_like) if leaf(ctx.base_like) else None,
+                like(out["g_bnd"][:, :, 13:], ctx.loads_like) if leaf(ctx.loads_like) else None,
+                *[like(by_name[k], v) for k, v in zip(ctx.names, ctx.vlike)])
+
+
+def simulate_tips_batch(robot, robots, ctl, theta=None, base_motion=None, tip_loads=None, dtype="f64", tol=1e-12):
+    """``simulate_tips_physical`` for a heterogeneous batch: rod b runs with the parameters of ``robots[b]`` (one
+    ``CosseratRod`` per rod, MLP off; ``robot`` carries N, del_t and the device handle) and ``tips[B, T, 3]`` comes back
+    connected in torch's graph to
+
+    * ``ctl[B, T, 4]``;
+    * every ``theta[k]``, a tensor ``[B, *PHYSICAL_SHAPES[k]]``: ``theta[k][b]`` is written into ``robots[b]`` (which keeps
+      it) before the table is built, and ``theta[k].grad`` is PER ROD, not summed - B rods, or B starting guesses of one
+      rod, calibrated by one backward pass;
+    * ``base_motion[B, T, 13]`` (``p0 h0 q0 w0`` per step) and ``tip_loads[B, T, 6]`` (``F_tip M_tip`` per step), as for
+      ``knode.simulate_batch``, where they are tensors that require grad: d(tip path)/d(base trajectory) and
+      d(tip path)/d(wrench history), step by step (arrays, or tensors that do not, are inputs only).
+
+    The forward run is the table / loads / boundary call with the full history at ``tol``; the backward pass is one
+    ``kr_simulate_vjp_table_batch``.  Raises ``KrError`` before anything runs for robots with the MLP on, wrong shapes,
+    unknown names and ``len(robots) != B``."""
+    who = "simulate_tips_batch"
+    _check_robot(robot)
+    if not isinstance(ctl, torch.Tensor):
+        raise kn.KrError(f"{who}: ctl must be a torch tensor (it is a leaf the gradient is connected to)")
+    B, T = _check_ctl(ctl)
+    theta = {} if theta is None else theta
+    _check_theta_batch(theta, B, who)
+    if base_motion is not None:
+        _check_history("base_motion", base_motion, B, T, 13, who)
+    if tip_loads is not None:
+        _check_history("tip_loads", tip_loads, B, T, 6, who)
+    robots = _check_robots(who, robots, B)
+    tdt = _tdt(dtype)
+    names = tuple(theta)
+    return _SimulateTipsBatch.apply(ctl, robot, robots, tdt, float(tol), names, base_motion, tip_loads, *[theta[k] for k in names])
 
 
 # ---- the KNODE model: physics plus the residual MLP in every sweep ----------------------------------------------------------

@@ -164,6 +164,8 @@ _PROTOS = {
     "kr_simulate_vjp_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "kr_step_vjp_par_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_simulate_vjp_par_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "kr_step_vjp_table_batch": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "kr_simulate_vjp_table_batch": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -817,6 +819,38 @@ class Handle:
                                                      _stream()))
         else:
             check(self.lib.kr_simulate_vjp_batch(self._h, B, T, scheme, *head, *tail, int(bool(use_nn)), dtype_code(ctl.dtype), _stream()))
+        return out
+
+    def step_vjp_table(self, table, prev, cur, nxt, tensions, g_next, need_bnd=True, need_par=False):
+        """``step_vjp`` of a heterogeneous batch (``kr_step_vjp_table_batch``, MLP off): rod b takes row b of ``table`` (a
+        ``ParamTable`` of B rows) in place of the handle's parameters.  The same dict; ``g_par[B, KR_PAR]`` with ``need_par``
+        is the gradient of row b's parameters.  ``g_bnd[b]`` is the gradient with respect to the boundary values rod b's
+        step used (record 0 of ``nxt`` holds them), whether they came from its row, a ``loads=`` or a ``bnd=`` history."""
+        if table is None or not isinstance(table, ParamTable):
+            raise KrError("step_vjp_table: table must be a ParamTable")
+        if cur.shape[0] != table.B:
+            raise KrError(f"step_vjp_table: cur holds {cur.shape[0]} rods, the parameter table {table.B}")
+        B, head, out = self._step_vjp_out("step_vjp_table", prev, cur, nxt, tensions, g_next, need_bnd, need_par)
+        check(self.lib.kr_step_vjp_table_batch(self._h, table._t, KR_EULER, *head, _ptr(out.get("g_par")), _ptr(out["resid"]),
+                                               _ptr(out["status"]), dtype_code(cur.dtype), _stream()))
+        return out
+
+    def simulate_vjp_table(self, table, ctl, states, g_states, prev_init=None, need_bnd=True, bnd_per_step=False, need_par=False):
+        """``simulate_vjp`` of a heterogeneous batch (``kr_simulate_vjp_table_batch``, MLP off): rod b takes row b of
+        ``table``.  The same dict; ``g_bnd`` is ``[B, KR_BND]``, summed over the steps, or - ``bnd_per_step`` -
+        ``[B, T, KR_BND]``: entry ``[b, t]`` is the gradient with respect to ``bnd[b, t]`` of ``simulate(..., bnd=)``, its
+        last six columns with respect to ``loads[b, t]`` of ``simulate(..., loads=)``.  ``g_par[B, KR_PAR]`` is per rod."""
+        import torch
+        if table is None or not isinstance(table, ParamTable):
+            raise KrError("simulate_vjp_table: table must be a ParamTable")
+        if ctl.dim() == 3 and ctl.shape[0] != table.B:
+            raise KrError(f"simulate_vjp_table: ctl holds {ctl.shape[0]} rods, the parameter table {table.B}")
+        B, T, head, out = self._simulate_vjp_out("simulate_vjp_table", ctl, states, g_states, prev_init, need_bnd, need_par)
+        if need_bnd and bnd_per_step:
+            out["g_bnd"] = torch.empty((B, T, KR_BND), dtype=ctl.dtype, device=ctl.device)
+            head = head[:-1] + (_ptr(out["g_bnd"]),)
+        check(self.lib.kr_simulate_vjp_table_batch(self._h, table._t, T, KR_EULER, *head, int(bool(bnd_per_step)), _ptr(out.get("g_par")),
+                                                   _ptr(out["resid"]), _ptr(out["status"]), dtype_code(ctl.dtype), _stream()))
         return out
 
     def step_vjp_nn(self, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, need_bnd=True, need_rows=True):
