@@ -943,7 +943,8 @@ int kr_simulate_vjp_nn_batch(kr_handle* h, int64_t B, int64_t T, int scheme, con
  * tensions pointer, B < 1, a bad dtype), each with a message, nothing launched and no output byte written.
  * Not served: the MLP-on form (kr_step_vjp_nn_batch has no g_par); RK4; del_t.  Every rod of a call shares the handle's
  * parameters, and g_par is per rod only because the states are: per-rod parameters (table, loads, boundary) are served by
- * kr_step_vjp_table_batch / kr_simulate_vjp_table_batch below, a bank (the MLP on) by nothing yet. */
+ * kr_step_vjp_table_batch / kr_simulate_vjp_table_batch below, a bank (the MLP on, without g_par) by
+ * kr_step_vjp_bank_batch / kr_simulate_vjp_bank_batch below them. */
 #define KR_PAR 43
 int kr_step_vjp_par_batch(kr_handle* h, int64_t B, int scheme,
                           const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
@@ -984,7 +985,8 @@ int kr_simulate_vjp_par_batch(kr_handle* h, int64_t B, int64_t T, int scheme, co
  * del_t differ from the handle's (the handle lends its device, its stream ordering and, for the rollout, its scratch: a
  * "carrier"; its own parameters are not read); KR_E_UNSUPPORTED for scheme == KR_RK4.  There is no use_nn: the calls
  * differentiate the physics alone and do not read the handle's network.
- * Not served: the MLP-on form with a table or a bank; RK4; full matrices in a row; del_t. */
+ * Not served: g_par with the MLP on (the MLP-on form of a table and a bank is kr_step_vjp_bank_batch below, without g_par);
+ * RK4; full matrices in a row; del_t. */
 int kr_step_vjp_table_batch(kr_handle* h, const kr_param_table* t, int scheme,
                             const void* state_prev, const void* state_cur, const void* state_next, const void* tensions,
                             const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd, void* g_par,
@@ -1006,6 +1008,49 @@ int kr_simulate_vjp_table_batch(kr_handle* h, const kr_param_table* t, int64_t T
                                 const void* states, const void* state_prev_init, void* g_states, void* g_prev_init,
                                 void* g_ctl, void* g_bnd, int bnd_per_step, void* g_par, double* resid, int32_t* status,
                                 int dtype, void* stream);
+
+/* ---- the adjoint of a heterogeneous batch with the MLP on: per-rod parameters AND per-rod networks -------------------------
+ * kr_step_vjp_nn_batch (knode.py:70-100 with the point map of cosserat_ode.py:178-184 inside the sweep of
+ * cosserat_ode.py:188-213) with rod b taking row b of a parameter table in place of the handle's parameters and network
+ * net_of_rod_host[b] of a bank (kr_mlp_bank_create) in place of the handle's network: the backward side of
+ * kr_simulate_batch_bank / kr_simulate_batch_bank_keypoints - the reference's experiment of model-mismatch variants, each with
+ * its own trained network (physics_multitrain.py:181-199), differentiated in one call.  B is the table's B;
+ * net_of_rod_host[B] is a HOST array of int32, every entry in [0, K), read before the call returns, as
+ * kr_simulate_batch_bank takes it.  Every other argument is that of kr_step_vjp_nn_batch; nn_x, nn_g[B][N-1][32] (nullable)
+ * are in ROD order: the rows of network k's weight gradient are those of the rods with net_of_rod_host[b] == k.  Like the
+ * table form the call takes no bnd or loads array - record 0 of state_next holds the base values the step used - and g_bnd[b]
+ * is the gradient with respect to the KR_BND boundary values rod b's step used, wherever they came from.
+ * Launches: the rows x of every stored point from the rod's own row, written in NETWORK order (the stable permutation of the
+ * rods by net_of_rod_host, computed on the host once per call and kept in the handle's scratch); the Jacobians on the fp64
+ * matrix cores, one launch of kr_mlp_input_jacobian_batch's kernel per network that has rods, on that network's contiguous
+ * range of rows (a network without rods launches nothing); the recursion with one wavefront per rod, the row read in place
+ * with scalar loads.  Scratch: that of kr_step_vjp_nn_batch plus B int32.  Arithmetic is fp64 whatever `dtype`; the KR_F32
+ * call is the KR_F64 call on the upcast inputs, rounded, bit for bit.  No atomics.  A rod's outputs depend neither on the
+ * batch, nor on its position in it, nor on which other networks are present.  status, NaN rules and nullable outputs per rod
+ * as for kr_step_vjp_nn_batch / kr_step_vjp_table_batch.
+ * Refusals, each with a message, nothing launched and no output byte written, in this order: KR_E_ARG for a null handle,
+ * table or bank; a bad dtype; a null state, g_next, tensions or net_of_rod_host pointer; a table or a bank of another device,
+ * or a table whose N or del_t differ from the handle's (a carrier, as for the table form); an entry of net_of_rod_host outside
+ * [0, K); then KR_E_UNSUPPORTED for scheme == KR_RK4, for a table of nn_input_history = 1 (the 53-wide input), for a bank
+ * whose shape kr_mlp_input_jacobian_batch does not serve, and for an activation on the last layer.  The calls read neither the
+ * handle's parameters nor the handle's network.
+ * Not served: g_par with the network on; full matrices in a row; RK4; the 53-wide input. */
+int kr_step_vjp_bank_batch(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank, const int32_t* net_of_rod_host,
+                           int scheme, const void* state_prev, const void* state_cur, const void* state_next,
+                           const void* tensions, const void* g_next, void* g_cur, void* g_prev, void* g_tensions, void* g_bnd,
+                           double* resid, int32_t* status, void* nn_x, void* nn_g, int dtype, void* stream);
+
+/* kr_simulate_vjp_nn_batch for the bank form (knode.py:55-102): DEFINED as the same composition of kr_step_vjp_bank_batch
+ * calls and equal to it bit for bit.  g_bnd (nullable) with bnd_per_step == 0 is [B][KR_BND], the sum over the steps from
+ * zero, t = T-1 first; with bnd_per_step == 1 it is [B][T][KR_BND], entry [b][t] = the g_bnd of step t, bit for bit - the
+ * gradient with respect to bnd[b][t] of kr_simulate_batch_bank_keypoints: a base trajectory and a wrench history per rod,
+ * with the network on.  nn_x, nn_g[T][B][N-1][32] (nullable): the rows of step t, in rod order.  Scratch: that of
+ * kr_simulate_vjp_nn_batch plus the permutation (B int32).  Refusals as for kr_step_vjp_bank_batch, with KR_E_ARG for T < 1
+ * after the dtype, for a null ctl, states or g_states, and for a bnd_per_step other than 0 or 1. */
+int kr_simulate_vjp_bank_batch(kr_handle* h, const kr_param_table* t, const kr_mlp_bank* bank, const int32_t* net_of_rod_host,
+                               int64_t T, int scheme, const void* ctl, const void* states, const void* state_prev_init,
+                               void* g_states, void* g_prev_init, void* g_ctl, void* g_bnd, int bnd_per_step, double* resid,
+                               int32_t* status, void* nn_x, void* nn_g, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

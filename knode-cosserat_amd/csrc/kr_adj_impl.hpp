@@ -2,9 +2,10 @@
 // tangents of the physics on dual numbers, the network's and the parameters' additions to them, the 6 x 6 solve, the ONE
 // composition over a stored rollout with its accumulation kernel, and the ONE path from a C entry point to a launch
 // (adj_step_entry, adj_simulate_entry).  The forms are kr_adj.hip (MLP off), kr_adj_par.hip (MLP off, with the gradient of
-// the material parameters), kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative) and kr_adj_tab.hip
-// (MLP off, rod b with row b of a parameter table, without and with the parameter gradient); the mapping is described in
-// kr_adj.hip.  The recursion of one rod, the body of all three step kernels, is kr_adj_body.inc.
+// the material parameters), kr_adj_nn.hip (the network's input Jacobian added to the per-point derivative), kr_adj_tab.hip
+// (MLP off, rod b with row b of a parameter table, without and with the parameter gradient) and kr_adj_bank.hip (MLP on, rod
+// b with row b of a table and network net_of_rod[b] of a bank); the mapping is described in kr_adj.hip.  The recursion of one
+// rod, the body of every step kernel, is kr_adj_body.inc.
 #pragma once
 #include "kr_internal.hpp"
 #include "kr_point_dual.hpp"
@@ -273,6 +274,36 @@ __device__ __forceinline__ double adj_nn_term(double u, bool own, const double (
   return r;
 }
 
+// The 47 inputs of the point map at the stored state of record `rec`: y of state_next, the history c1 cur + c2 prev on
+// its twelve leading slots, the tendon force (values only), for nn_rows_kernel (kr_adj_nn.hip) and nn_rows_bank_kernel
+// (kr_adj_bank.hip).  adj_point above assembles the same values and is left as it is: routed through this helper the compiler schedules step_vjp_kernel<float> differently,
+// and that kernel keeps its text.
+template <typename T>
+__device__ __forceinline__ void adj_point_values(const RodConst<double>& P, const AdjArgs<T>& A, int64_t rec, const double (&tf)[3],
+                                                 Dual (&in)[47]) {
+  const T* y = A.next + rec * KR_SLOTS;
+  const T* c = A.cur + rec * KR_SLOTS;
+  const T* p = A.prev + rec * KR_SLOTS;
+#pragma unroll
+  for (int k = 0; k < 19; ++k) in[k].v = (double)y[adj_yslot(k)];
+#pragma unroll
+  for (int k = 19; k < 32; ++k) in[k].v = 0.0;  // (history of p, h, n, m: no equation reads it)
+#pragma unroll
+  for (int k = 0; k < 12; ++k) in[32 + k].v = P.c1 * (double)c[k] + P.c2 * (double)p[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) in[44 + k].v = tf[k];
+}
+
+// ---- a rod's table row in place (kr_adj_tab.hip, kr_adj_bank.hip) ----
+// this wavefront's rod (the body's own statement: the same value, so the compiler keeps one)
+__device__ __forceinline__ int64_t adj_tab_rod() {
+  return (int64_t)blockIdx.x * ADJ_RODS_PER_WG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+__device__ __forceinline__ const RodConst<double>& adj_tab_row(const KR_CONSTANT_AS RodConst<double>* rows, int64_t rod) {
+  const int row = __builtin_amdgcn_readfirstlane((int)rod);
+  return *(const RodConst<double>*)(rows + row);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void adj_add_kernel(T* dst, const T* src, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -350,6 +381,8 @@ static int simulate_vjp_steps(kr_handle* h, int64_t B, int64_t T_steps, const T*
 
 // The refusals of the MLP-off forms: use_nn, then the scheme (the scheme half is the MLP-on form's too)
 int adj_refuse(const char* api, int scheme, int use_nn);  // (kr_adj.hip)
+// The refusals of the table forms: the table against the handle (device, N, del_t), then the scheme
+int adj_tab_refuse(const char* api, const kr_handle* h, const kr_param_table* t, int scheme);  // (kr_adj_tab.hip)
 
 // ---- from a C entry point to its launch ----
 // What a caller with two mistakes hears of first: handle, dtype, B, (T,) null pointers, the form's refusal, stream ordering.

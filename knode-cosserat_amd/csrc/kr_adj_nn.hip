@@ -26,26 +26,7 @@
 
 namespace kr {
 
-// The 47 inputs of the point map at the stored state of record `rec`: y of state_next, the history c1 cur + c2 prev on
-// its twelve leading slots, the tendon force (values only), for nn_rows_kernel.  adj_point (kr_adj_impl.hpp) assembles the
-// same values and is left as it is: routed through this helper the compiler schedules step_vjp_kernel<float> differently,
-// and that kernel keeps its text.
-template <typename T>
-__device__ __forceinline__ void adj_point_values(const RodConst<double>& P, const AdjArgs<T>& A, int64_t rec, const double (&tf)[3],
-                                                 Dual (&in)[47]) {
-  const T* y = A.next + rec * KR_SLOTS;
-  const T* c = A.cur + rec * KR_SLOTS;
-  const T* p = A.prev + rec * KR_SLOTS;
-#pragma unroll
-  for (int k = 0; k < 19; ++k) in[k].v = (double)y[adj_yslot(k)];
-#pragma unroll
-  for (int k = 19; k < 32; ++k) in[k].v = 0.0;  // (history of p, h, n, m: no equation reads it)
-#pragma unroll
-  for (int k = 0; k < 12; ++k) in[32 + k].v = P.c1 * (double)c[k] + P.c2 * (double)p[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) in[44 + k].v = tf[k];
-}
-
+// (adj_point_values, the 47 inputs of the point map at a stored record: kr_adj_impl.hpp, shared with kr_adj_bank.hip)
 // x of every stored point of every rod, one thread per point
 template <typename T>
 __global__ __launch_bounds__(256) void nn_rows_kernel(const RodConst<double> P, const AdjArgs<T> A, double* __restrict__ xrows) {

@@ -33,14 +33,7 @@ struct AdjTab {
   T* g_par;                                     // [B][KR_PAR]; written by the PAR kernel only
 };
 
-// this wavefront's rod (the body's own statement: the same value, so the compiler keeps one)
-__device__ __forceinline__ int64_t adj_tab_rod() {
-  return (int64_t)blockIdx.x * ADJ_RODS_PER_WG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-}
-__device__ __forceinline__ const RodConst<double>& adj_tab_row(const KR_CONSTANT_AS RodConst<double>* rows, int64_t rod) {
-  const int row = __builtin_amdgcn_readfirstlane((int)rod);
-  return *(const RodConst<double>*)(rows + row);
-}
+// (adj_tab_rod, adj_tab_row - this wavefront's rod and its row in place: kr_adj_impl.hpp, shared with kr_adj_bank.hip)
 
 template <typename T>
 __global__ __launch_bounds__(64 * ADJ_RODS_PER_WG) void step_vjp_tab_kernel(const AdjTab<T> TB, const AdjArgs<T> A) {
@@ -110,7 +103,7 @@ int launch_put(double* dst, const double* src, int64_t n, int64_t stride, hipStr
 
 // The refusals of the table form: the table against the handle, then the scheme.  (No use_nn: the calls differentiate the
 // physics alone and do not read the handle's network, so nn_input_history is not compared.)
-static int adj_tab_refuse(const char* api, const kr_handle* h, const kr_param_table* t, int scheme) {
+int adj_tab_refuse(const char* api, const kr_handle* h, const kr_param_table* t, int scheme) {
   const char* f = t->device != h->device ? "device" : t->N != h->params.N ? "N" : t->del_t != h->params.del_t ? "del_t" : nullptr;
   if (f) {
     set_error(std::string(api) + ": parameter table: " + f + " of the table differs from the handle's");

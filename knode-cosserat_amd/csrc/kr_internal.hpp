@@ -514,6 +514,11 @@ void fused_set_debug(void* dev_u64x48);  // diagnostic build: where the fused ke
 int nnjac_check(const kr_handle* h, const char* api);
 template <typename T>
 int launch_nnjac(kr_handle* h, int64_t Q, const T* x, int64_t x_stride, T* jac, int transposed, hipStream_t s);
+// The same for a descriptor that is not the handle's - network k of a bank, the bank's fp64 descriptor moved by k * stride
+// (kr_adj_bank.hip; the descriptor form is instantiated for double only)
+int nnjac_check(const MlpDev<double>& M, int nn_input_history, const char* api);
+template <typename T>
+int launch_nnjac(const MlpDev<double>& M, int64_t Q, const T* x, int64_t x_stride, T* jac, int transposed, hipStream_t s);
 
 // kr_ode.hip
 template <typename T>

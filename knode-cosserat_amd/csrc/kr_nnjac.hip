@@ -280,17 +280,20 @@ __global__ __launch_bounds__(64 * NJ_WAVES) void mlp_input_jacobian3_kernel(cons
 
 // The shapes served, and the refusals that come before anything is launched
 int nnjac_check(const kr_handle* h, const char* api) {
-  const MlpDev<double>& M = h->mlp_d;
-  const std::string who = std::string(api) + ": ";
-  if (M.n_layers <= 0) {
-    set_error(who + "no MLP was set (kr_set_mlp)");
+  if (h->mlp_d.n_layers <= 0) {
+    set_error(std::string(api) + ": no MLP was set (kr_set_mlp)");
     return KR_E_STATE;
   }
+  return nnjac_check(h->mlp_d, h->params.nn_input_history, api);
+}
+// (the same for a descriptor that is not the handle's: a network of a bank)
+int nnjac_check(const MlpDev<double>& M, int nn_input_history, const char* api) {
+  const std::string who = std::string(api) + ": ";
   auto refuse = [&](const std::string& why) {
     set_error(who + why + "; nothing falls back to another evaluator");
     return KR_E_UNSUPPORTED;
   };
-  if (h->params.nn_input_history != 0) return refuse("nn_input_history = 1 (the 53-wide input) is not served");
+  if (nn_input_history != 0) return refuse("nn_input_history = 1 (the 53-wide input) is not served");
   const int n = M.n_layers;
   if (n != 2 && n != 3) return refuse("a network of " + std::to_string(n) + " layers is not served (one or two hidden layers only)");
   if (M.dims[0] != NJ_IN || M.dims[n] != NJ_OUT) return refuse("the network must map 28 inputs to 25 outputs");
@@ -306,7 +309,10 @@ int nnjac_check(const kr_handle* h, const char* api) {
 // x rows (stride x_stride) -> jac rows of 700; the caller has passed nnjac_check
 template <typename T>
 int launch_nnjac(kr_handle* h, int64_t Q, const T* x, int64_t x_stride, T* jac, int transposed, hipStream_t s) {
-  const MlpDev<double>& M = h->mlp_d;
+  return launch_nnjac<T>(h->mlp_d, Q, x, x_stride, jac, transposed, s);
+}
+template <typename T>
+int launch_nnjac(const MlpDev<double>& M, int64_t Q, const T* x, int64_t x_stride, T* jac, int transposed, hipStream_t s) {
   NjArgs<T> A{Q, x, x_stride, jac, transposed};
   if (M.n_layers == 2) {
     const int64_t groups = (Q + NJ_WAVES * NJ_ROWS - 1) / (NJ_WAVES * NJ_ROWS);
@@ -319,6 +325,7 @@ int launch_nnjac(kr_handle* h, int64_t Q, const T* x, int64_t x_stride, T* jac, 
 }
 template int launch_nnjac<float>(kr_handle*, int64_t, const float*, int64_t, float*, int, hipStream_t);
 template int launch_nnjac<double>(kr_handle*, int64_t, const double*, int64_t, double*, int, hipStream_t);
+template int launch_nnjac<double>(const MlpDev<double>&, int64_t, const double*, int64_t, double*, int, hipStream_t);
 
 }  // namespace kr
 

@@ -15,6 +15,9 @@ d(tension history) costs about one forward rollout instead of 4 T + 1 of them by
   backward side of a heterogeneous batch (``kr_simulate_vjp_table_batch``) - rod b with the parameters of ``robots[b]``, the
   parameter gradients per rod (many rods, or many starting guesses of one rod, calibrated in one backward pass), and the
   gradient with respect to a base trajectory or a tip-wrench history, step by step.
+* ``rollout_grad_bank`` / ``simulate_tips_bank``: the heterogeneous batch with the MLP on (``kr_simulate_vjp_bank_batch``) -
+  rod b with the parameters of ``robots[b]`` and network ``net_of_rod[b]`` of K, the weight gradient per network: the
+  reference's model-mismatch variants, each with its own trained network, differentiated in one backward pass.
 * ``rollout_grad_nn`` / ``simulate_tips_nn``: the same for the KNODE model, physics plus the residual MLP in every sweep
   (``kr_simulate_vjp_nn_batch``) - and the gradient of a rollout loss with respect to the network's weights, which the
   reference never had (it trains one step ahead, physics_train.py:250-259).
@@ -102,23 +105,24 @@ def _rollout(h, vjp, ctl, states, g_states, g_tips, prev_init, dtype, **kw):
     return out, res
 
 
-def _check_robots(who, robots, B):
-    """one robot per rod, none with its MLP on (no library call, no device)"""
+def _check_robots(who, robots, B, nn_ok=False):
+    """one robot per rod, none with its MLP on (no library call, no device; ``nn_ok``: a bank call, whose networks are the
+    call's own - the robots supply the rods alone)"""
     robots = list(robots)
     if len(robots) != B:
         raise kn.KrError(f"{who}: robots holds {len(robots)} rods, ctl {B}")
     for b, r in enumerate(robots):
-        if getattr(r, "_use_nn", False):
+        if not nn_ok and getattr(r, "_use_nn", False):
             raise kn.KrError(f"{who}: rod {b}: the adjoint of a table call differentiates the physics alone; a robot with its MLP on "
                              "is not served (nothing falls back to the physics)")
     return robots
 
 
-def _table_rows(who, robot, robots, B):
+def _table_rows(who, robot, robots, B, nn_ok=False):
     """The KrParams rows of ``robots`` for a table call of the adjoint, checked on the host without the library: one robot
     per rod, none with its MLP on, N and del_t the carrier's.  (What a row may hold - diagonal matrices, 9 <= N <= 128 - is
     checked by the library when the table is made.)"""
-    robots = _check_robots(who, robots, B)
+    robots = _check_robots(who, robots, B, nn_ok)
     base = robot._params()
     rows = [r._params() for r in robots]
     for b, p in enumerate(rows):
@@ -522,3 +526,149 @@ def simulate_tips_nn(robot, ctl, params, dtype="f64", tol=1e-12):
     _check_ctl(ctl)
     _check_params(params, "simulate_tips_nn")
     return _SimulateTipsNn.apply(ctl, robot, _tdt(dtype), float(tol), *params)
+
+
+# ---- a heterogeneous batch with a bank of networks: per-rod parameters AND per-rod networks ---------------------------------
+def _check_bank(who, params, net_of_rod, B):
+    """``params``: K lists of one network's tensors each (nn.Linear order), all of one shape; ``net_of_rod``: one index in
+    [0, K) per rod.  Host only.  Returns (K, the int32 index array)."""
+    if not isinstance(params, (list, tuple)) or not params or not all(isinstance(p, (list, tuple)) for p in params):
+        raise kn.KrError(f"{who}: params must be a list of K per-network lists W1, b1, W2, b2, ... (nn.Linear order)")
+    for k, p in enumerate(params):
+        _check_params(p, f"{who}: network {k}")
+        if [tuple(t.shape) for t in p] != [tuple(t.shape) for t in params[0]]:
+            raise kn.KrError(f"{who}: network {k} has another shape than network 0 (all networks of a bank share one shape)")
+    nets = np.asarray(net_of_rod)
+    if nets.ndim != 1 or nets.size != B or not np.issubdtype(nets.dtype, np.integer):
+        raise kn.KrError(f"{who}: net_of_rod must hold one integer per rod ({B}); got shape {tuple(nets.shape)} {nets.dtype}")
+    if nets.min() < 0 or nets.max() >= len(params):
+        raise kn.KrError(f"{who}: net_of_rod must lie in [0, {len(params)}); got {int(nets.min())} .. {int(nets.max())}")
+    return len(params), nets.astype(np.int32)
+
+
+def _bank_networks(robot, h, params, who):
+    """The K networks as ``MlpBank`` reads them from the device: float32 device copies (which the caller keeps alive until the
+    stream has reached the pack launches), with the carrier robot's activations.  Returns (p32 per network, acts, networks)."""
+    acts = _acts_of(robot)
+    if len(acts) != len(params[0]) // 2:
+        raise kn.KrError(f"{who}: the robot's network has {len(acts)} layers, params describe {len(params[0]) // 2}")
+    dev = f"cuda:{h.device}"
+    p32 = [[t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in p] for p in params]
+    return p32, acts, [(p[0::2], p[1::2], acts) for p in p32]
+
+
+def bank_weight_grads(h, p32, acts, nets, nn_x, nn_g):
+    """Per network k: ``weight_grads`` over the rows of the rods with ``nets[b] == k``, gathered in rod order, step-major
+    (``nn_x``, ``nn_g`` ``[T, B, N - 1, 32]`` in rod order); zeros for a network without rods."""
+    grads = []
+    for k, pk in enumerate(p32):
+        rods = torch.as_tensor(np.flatnonzero(nets == k), dtype=torch.long, device=nn_x.device)
+        if rods.numel() == 0:
+            grads.append([torch.zeros_like(t) for t in pk])
+            continue
+        grads.append(weight_grads(h, pk, acts, nn_x.index_select(1, rods).contiguous(), nn_g.index_select(1, rods).contiguous()))
+    return grads
+
+
+def rollout_grad_bank(robot, robots, ctl, states, params, net_of_rod, g_states=None, g_tips=None, prev_init=None, dtype="f64",
+                      per_step_boundary=False):
+    """``rollout_grad(robots=, per_step_boundary=)`` for a stored rollout of ``knode.simulate_bank`` /
+    ``Handle.simulate(..., table=, bank=, net_of_rod=)``: rod b with the parameters of ``robots[b]`` and network
+    ``net_of_rod[b]`` of ``params``, a list of K per-network tensor lists in nn.Linear order (the weights the stored rollout
+    was run with; they go into a bank from the device).  ``robot`` carries N, del_t, the device handle and the networks'
+    activations; its own weights are not read.  The dict of ``rollout_grad`` (``boundary`` [B, KR_BND] or, with
+    ``per_step_boundary``, [B, T, KR_BND]), and ``params``: per network k the list of host arrays dL/dW1, dL/db1, ... summed
+    over the grid points and steps of ITS rods (``bank_weight_grads``), zeros for a network no rod runs.  One
+    ``kr_simulate_vjp_bank_batch``.  Not served: ``physical`` (the parameter gradient with the network on)."""
+    who = "rollout_grad_bank"
+    _check_rollout(who, ctl, states, g_states, g_tips)
+    B = tuple(ctl.shape)[0]
+    K, nets = _check_bank(who, params, net_of_rod, B)
+    rows = _table_rows(who, robot, robots, B, nn_ok=True)
+    _tdt(dtype)
+    h = robot._native(push_mlp=False)  # (the handle's own network is neither read nor replaced: the robot keeps its weights)
+    p32, acts, networks = _bank_networks(robot, h, params, who)
+    with h.param_table(rows) as table, h.mlp_bank(networks) as bank:
+        vjp = lambda *a, **kw: h.simulate_vjp_bank(table, bank, nets, *a, **kw)
+        out, res = _rollout(h, vjp, ctl, states, g_states, g_tips, prev_init, dtype, bnd_per_step=bool(per_step_boundary))
+    res["params"] = [[t.cpu().numpy() for t in g] for g in bank_weight_grads(h, p32, acts, nets, out["nn_x"], out["nn_g"])]
+    return res
+
+
+class _SimulateTipsBank(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, robot, robots, tdt, tol, nets, base_motion, tip_loads, n_per, *flat):
+        who = "simulate_tips_bank"
+        params = [list(flat[k:k + n_per]) for k in range(0, len(flat), n_per)]
+        h = robot._native(push_mlp=False)  # (the handle's own network is neither read nor replaced: the robot keeps its weights)
+        dev = f"cuda:{h.device}"
+        rows = _table_rows(who, robot, robots, ctl.shape[0], nn_ok=True)
+        p32, acts, networks = _bank_networks(robot, h, params, who)
+        table, bank = h.param_table(rows), h.mlp_bank(networks)
+        ctl_t = ctl.detach().to(device=dev, dtype=tdt).contiguous()
+        B, T = ctl_t.shape[0], ctl_t.shape[1]
+        on_dev = lambda x: torch.as_tensor(x.detach() if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)).to(device=dev, dtype=tdt)
+        bnd_t = None
+        if base_motion is not None or tip_loads is not None:  # per-step data beside a bank is a boundary call
+            own = np.array([list(p.p0[:]) + list(p.h0[:]) + list(p.q0[:]) + list(p.w0[:]) + list(p.F_tip[:]) + list(p.M_tip[:])
+                            for p in rows], dtype=np.float64)
+            bnd_t = torch.as_tensor(own, device=dev).to(tdt)[:, None, :].repeat(1, T, 1)
+            if base_motion is not None:
+                bnd_t[:, :, :13] = on_dev(base_motion)
+            if tip_loads is not None:
+                bnd_t[:, :, 13:] = on_dev(tip_loads)
+            bnd_t = bnd_t.contiguous()
+        states = h.new_state(B, tdt, n_slots=T + 1)
+        h.init_straight(states[0], table=table)
+        G = torch.zeros((B, 6), dtype=tdt, device=dev)
+        tip = torch.empty((B, T, 3), dtype=tdt, device=dev)
+        status = torch.zeros((B, T), dtype=torch.int32, device=dev)
+        h.simulate(ctl_t, states, G, ring=False, tip=tip, status=status, tol=tol, table=table, bank=bank, net_of_rod=nets, bnd=bnd_t)
+        bad = int((status != 0).sum())
+        if bad:
+            import warnings
+            warnings.warn(f"{who}: {bad} of {status.numel()} rod-steps did not converge to tol = {tol:g}; the gradient of those rods is "
+                          "not that of the solved step", RuntimeWarning)
+        ctx.h, ctx.table, ctx.bank, ctx.nets, ctx.ctl_t, ctx.states = h, table, bank, nets, ctl_t, states
+        ctx.p32, ctx.acts, ctx.networks = p32, acts, networks
+        ctx.like, ctx.plike, ctx.base_like, ctx.loads_like = ctl, flat, base_motion, tip_loads
+        return tip.to(device=ctl.device, dtype=ctl.dtype)
+
+    @staticmethod
+    def backward(ctx, g_tips):
+        h, states = ctx.h, ctx.states
+        leaf = lambda x: isinstance(x, torch.Tensor) and x.requires_grad
+        need_bnd = leaf(ctx.base_like) or leaf(ctx.loads_like)
+        ctx.bank.repack(ctx.networks)  # (the forward's weights, whatever the bank's arena was asked to hold since)
+        out = h.simulate_vjp_bank(ctx.table, ctx.bank, ctx.nets, ctx.ctl_t, states, _tip_cotangent(h, states, g_tips),
+                                  need_bnd=need_bnd, bnd_per_step=True)
+        grads = bank_weight_grads(h, ctx.p32, ctx.acts, ctx.nets, out["nn_x"], out["nn_g"])
+        like = lambda g, x: g.to(device=x.device, dtype=x.dtype)
+        flat = [g for gk in grads for g in gk]
+        return (like(out["g_ctl"], ctx.like), None, None, None, None, None,
+                like(out["g_bnd"][:, :, :13], ctx.base_like) if leaf(ctx.base_like) else None,
+                like(out["g_bnd"][:, :, 13:], ctx.loads_like) if leaf(ctx.loads_like) else None, None,
+                *[like(g, p) for g, p in zip(flat, ctx.plike)])
+
+
+def simulate_tips_bank(robot, robots, ctl, params, net_of_rod, base_motion=None, tip_loads=None, dtype="f64", tol=1e-12):
+    """``simulate_tips_batch`` with the MLP on and a network per rod: rod b runs with the parameters of ``robots[b]`` and
+    network ``net_of_rod[b]`` of ``params`` (K per-network tensor lists in nn.Linear order; ``robot`` carries N, del_t, the
+    device handle and the activations, and keeps its own weights).  ``tips[B, T, 3]`` comes back connected to ``ctl``, to
+    every ``params[k][i]`` (its ``.grad`` the sum over the rods that run network k; zeros for a network without rods), and
+    to ``base_motion[B, T, 13]`` / ``tip_loads[B, T, 6]`` where they are tensors that require grad - with the network on, the
+    gradient with respect to a base trajectory that no other call gives.  The forward is the bank call with the full history
+    at ``tol`` (a boundary call when either history is given, a rod's own base or wrench where one is not); the backward
+    pass is one ``kr_simulate_vjp_bank_batch``, then the MLP backward pass per network over the rows it emits."""
+    who = "simulate_tips_bank"
+    if not isinstance(ctl, torch.Tensor):
+        raise kn.KrError(f"{who}: ctl must be a torch tensor (it is a leaf the gradient is connected to)")
+    B, T = _check_ctl(ctl)
+    K, nets = _check_bank(who, params, net_of_rod, B)
+    if base_motion is not None:
+        _check_history("base_motion", base_motion, B, T, 13, who)
+    if tip_loads is not None:
+        _check_history("tip_loads", tip_loads, B, T, 6, who)
+    robots = _check_robots(who, robots, B, nn_ok=True)
+    flat = [t for p in params for t in p]
+    return _SimulateTipsBank.apply(ctl, robot, robots, _tdt(dtype), float(tol), nets, base_motion, tip_loads, len(params[0]), *flat)

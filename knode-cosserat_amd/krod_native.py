@@ -166,6 +166,9 @@ _PROTOS = {
     "kr_simulate_vjp_par_batch": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_step_vjp_table_batch": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "kr_simulate_vjp_table_batch": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp]),
+    "kr_step_vjp_bank_batch": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "kr_simulate_vjp_bank_batch": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int,
+                                          _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -868,6 +871,47 @@ class Handle:
         B, T, head, out = self._simulate_vjp_out("simulate_vjp_nn", ctl, states, g_states, prev_init, need_bnd, need_rows=bool(need_rows))
         check(self.lib.kr_simulate_vjp_nn_batch(self._h, B, T, scheme, *head, _ptr(out["resid"]), _ptr(out["status"]), _ptr(out["nn_x"]),
                                                 _ptr(out["nn_g"]), dtype_code(ctl.dtype), _stream()))
+        return out
+
+    def _bank_args(self, who, table, bank, net_of_rod, B):
+        """The checks the two bank adjoints share -> the int32 index array (kept alive by the caller) and its pointer."""
+        if table is None or not isinstance(table, ParamTable):
+            raise KrError(f"{who}: table must be a ParamTable")
+        if bank is None or not isinstance(bank, MlpBank) or net_of_rod is None:
+            raise KrError(f"{who}: bank must be an MlpBank, with net_of_rod")
+        if B != table.B:
+            raise KrError(f"{who}: the states hold {B} rods, the parameter table {table.B}")
+        nets = np.ascontiguousarray(np.asarray(net_of_rod).reshape(-1), dtype=np.int32)
+        if nets.size != B:
+            raise KrError(f"{who}: the states hold {B} rods, net_of_rod {nets.size}")
+        return nets, nets.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def step_vjp_bank(self, table, bank, net_of_rod, prev, cur, nxt, tensions, g_next, scheme=KR_EULER, need_bnd=True, need_rows=True):
+        """``step_vjp_nn`` of a heterogeneous batch (``kr_step_vjp_bank_batch``): rod b takes row b of ``table`` and network
+        ``net_of_rod[b]`` of ``bank`` (an ``MlpBank``) in place of the handle's parameters and network.  The dict of
+        ``step_vjp_nn``; ``nn_x``, ``nn_g`` ``[B, N - 1, 32]`` are in rod order - the rows of network k's weight gradient are
+        those of the rods with ``net_of_rod[b] == k``."""
+        nets, nets_p = self._bank_args("step_vjp_bank", table, bank, net_of_rod, cur.shape[0])
+        B, head, out = self._step_vjp_out("step_vjp_bank", prev, cur, nxt, tensions, g_next, need_bnd, need_rows=bool(need_rows))
+        check(self.lib.kr_step_vjp_bank_batch(self._h, table._t, bank._b, nets_p, scheme, *head, _ptr(out["resid"]), _ptr(out["status"]),
+                                              _ptr(out["nn_x"]), _ptr(out["nn_g"]), dtype_code(cur.dtype), _stream()))
+        return out
+
+    def simulate_vjp_bank(self, table, bank, net_of_rod, ctl, states, g_states, prev_init=None, scheme=KR_EULER, need_bnd=True,
+                          bnd_per_step=False, need_rows=True):
+        """``simulate_vjp_nn`` of a heterogeneous batch (``kr_simulate_vjp_bank_batch``): the backward side of
+        ``simulate(..., bank=, net_of_rod=)`` without and with ``bnd=``.  The dict of ``simulate_vjp_nn``; ``g_bnd`` is
+        ``[B, KR_BND]``, summed over the steps, or - ``bnd_per_step`` - ``[B, T, KR_BND]`` as in ``simulate_vjp_table``;
+        ``nn_x``, ``nn_g`` ``[T, B, N - 1, 32]`` are in rod order."""
+        import torch
+        B, T, head, out = self._simulate_vjp_out("simulate_vjp_bank", ctl, states, g_states, prev_init, need_bnd, need_rows=bool(need_rows))
+        nets, nets_p = self._bank_args("simulate_vjp_bank", table, bank, net_of_rod, B)
+        if need_bnd and bnd_per_step:
+            out["g_bnd"] = torch.empty((B, T, KR_BND), dtype=ctl.dtype, device=ctl.device)
+            head = head[:-1] + (_ptr(out["g_bnd"]),)
+        check(self.lib.kr_simulate_vjp_bank_batch(self._h, table._t, bank._b, nets_p, T, scheme, *head, int(bool(bnd_per_step)),
+                                                  _ptr(out["resid"]), _ptr(out["status"]), _ptr(out["nn_x"]), _ptr(out["nn_g"]),
+                                                  dtype_code(ctl.dtype), _stream()))
         return out
 
     # -- evaluation metrics ------------------------------------------------------
