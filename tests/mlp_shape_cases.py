@@ -211,11 +211,84 @@ class _Frozen:
         return a
 
 
+def newton_steps(D, ctl, tol, fd_eps, mlp=None, scheme="euler", fd_hist=None, fd_mid=None, fd_point=None, start=None,
+                 on_sweep=None):
+    """The BDF2 loop of orc.simulate with ``orc.newton_shoot`` at every step, counted: dict(iters=per-step iterations,
+    ok=per-step convergence, base=per-step base / line-search sweeps, traj=float64[T + 1, 25, N], entry t the state after
+    step t).  A step without backtracking has base == iters + 1 (the first residual, one full step per iteration but the
+    last, the final sweep).  The hooks change the six PERTURBED sweeps of an iteration (``fun_fd``) or the start of a
+    step, never a base sweep: the root stays what it is (tests/sweep_count_cases.py builds its mutants from them).
+
+    * ``fd_hist(yh, zh, y_cur, z_cur, y_old, z_old) -> (yh, zh)``: the histories a perturbed sweep reads;
+    * ``fd_mid(yh, zh) -> (yh_int, zh_int)``: RK4, the midpoint histories of a perturbed sweep (default: knode.simulate's
+      means of neighbours, of the histories the perturbed sweep reads).  With either of the two the Jacobian is that of the
+      ALTERED sweep: its columns are the altered sweep's difference quotients against the altered sweep at the base point
+      (one more sweep per iteration), put on the true residual - what a solver whose Jacobian sweeps all read the wrong
+      history computes.  (Against the true base sweep the difference of the two sweeps would be divided by the step.);
+    * ``fd_point(G_base, G_perturbed) -> G``: the point a perturbed sweep starts from (the quotient keeps its step);
+    * ``start(t, Gs) -> G``: the start of step t from ``Gs``, the (n, m) at the base of states t, t - 1, .. 0 (``Gs[0]``
+      is also the G the previous step accepted: a sweep writes its G there); default: the warm start ``Gs[0]``;
+    * ``on_sweep(perturbed)``: called before every sweep."""
+    import cosserat_oracle as orc
+    own_base = fd_hist is not None or fd_mid is not None
+    y, z = orc.straight_state(D)
+    y_prev, z_prev = y.copy(), z.copy()
+    G = np.zeros(6)
+    Gs = [G.copy()]
+    iters, oks, bases, traj = [], [], [], [np.vstack([y, z])]
+    mids = lambda a, c: (0.5 * (a[:, :-1] + a[:, 1:]), 0.5 * (c[:, :-1] + c[:, 1:]))   # knode.py:80-81
+    for t, tensions in enumerate(ctl):
+        yh = D.c1 * y + D.c2 * y_prev
+        zh = D.c1 * z + D.c2 * z_prev
+        yh_fd, zh_fd = (yh, zh) if fd_hist is None else fd_hist(yh, zh, y.copy(), z.copy(), y_prev, z_prev)
+        y_prev, z_prev = y.copy(), z.copy()
+        if scheme == "rk4":
+            yi, zi = mids(yh, zh)
+            yi_fd, zi_fd = (fd_mid or mids)(yh_fd, zh_fd)
+        elif scheme != "euler":
+            raise ValueError(scheme)
+        n_base, at = [0], [None, None, None, None]  # (at: base point, its residual; the altered sweep's base point, residual)
+
+        def sweep(g, yh, zh, yi, zi):
+            if scheme == "euler":
+                return orc.residual_euler(D, g, y, z, yh, zh, tensions, mlp)
+            return orc.residual_rk4(D, g, y, z, yh, yi, zh, zi, tensions, mlp)
+
+        def base(g):
+            n_base[0] += 1
+            at[0] = np.array(g, float)
+            if on_sweep is not None:
+                on_sweep(False)
+            at[1] = sweep(g, yh, zh, *((yi, zi) if scheme == "rk4" else (None, None)))
+            return at[1]
+
+        def perturbed(g):
+            if on_sweep is not None:
+                on_sweep(True)
+            if fd_point is not None:
+                g = fd_point(at[0], g)
+            r = sweep(g, yh_fd, zh_fd, *((yi_fd, zi_fd) if scheme == "rk4" else (None, None)))
+            if own_base:  # the quotient of the altered sweep against ITS OWN value at the base point
+                if at[2] is not at[0]:
+                    at[2], at[3] = at[0], sweep(at[0], yh_fd, zh_fd, *((yi_fd, zi_fd) if scheme == "rk4" else (None, None)))
+                r = at[1] + (r - at[3])
+            return r
+
+        if start is not None:
+            G = np.array(start(t, Gs), float)
+        G, ok, it = orc.newton_shoot(base, G, tol=tol, fd_eps=fd_eps, fun_fd=perturbed)
+        Gs.insert(0, np.array(G))
+        iters.append(it)
+        oks.append(bool(ok))
+        bases.append(n_base[0])
+        traj.append(np.vstack([y, z]))
+    return dict(iters=tuple(iters), ok=tuple(oks), base=tuple(bases), traj=np.array(traj))
+
+
 @functools.lru_cache(maxsize=None)
 def sweep_counts(cid, b, dtype, frozen, N=20):
     """dict(iters=per-step newton_shoot iterations, ok=per-step convergence, base=per-step base / line-search sweeps):
-    the BDF2 loop of orc.simulate from the reference's warm start, at the stopping rule of ``dtype``.  A step without
-    backtracking has base == iters + 1 (the first residual, one full step per iteration but the last, the final sweep)."""
+    ``newton_steps`` from the reference's warm start, at the stopping rule of ``dtype``."""
     import copy
 
     import cosserat_oracle as orc
@@ -224,32 +297,9 @@ def sweep_counts(cid, b, dtype, frozen, N=20):
     mlp = copy.copy(count_mlp(cid))
     tap = _Frozen(orc) if frozen else None
     mlp.tap = tap
-    y, z = orc.straight_state(D)
-    y_prev, z_prev = y.copy(), z.copy()
-    G = np.zeros(6)
-    iters, oks, bases = [], [], []
-    for tensions in controls(T_COUNT)[b]:
-        yh = D.c1 * y + D.c2 * y_prev
-        zh = D.c1 * z + D.c2 * z_prev
-        y_prev, z_prev = y.copy(), z.copy()
-        n_base = [0]
-
-        def base(g):
-            n_base[0] += 1
-            if tap is not None:
-                tap.start(False)
-            return orc.residual_euler(D, g, y, z, yh, zh, tensions, mlp)
-
-        def perturbed(g):
-            if tap is not None:
-                tap.start(True)
-            return orc.residual_euler(D, g, y, z, yh, zh, tensions, mlp)
-
-        G, ok, it = orc.newton_shoot(base, G, tol=rule["tol"], fd_eps=rule["fd_eps"], fun_fd=perturbed)
-        iters.append(it)
-        oks.append(bool(ok))
-        bases.append(n_base[0])
-    return dict(iters=tuple(iters), ok=tuple(oks), base=tuple(bases))
+    out = newton_steps(D, controls(T_COUNT)[b], rule["tol"], rule["fd_eps"], mlp=mlp,
+                       on_sweep=None if tap is None else tap.start)
+    return dict(iters=out["iters"], ok=out["ok"], base=out["base"])
 
 
 def count_sums(cid, b, dtype):
