@@ -803,6 +803,58 @@ int kr_fastdtw_batch(kr_handle* h, int64_t B,
                      int radius, double* dist, int32_t* path, int32_t* path_len, void* ws,
                      int dtype, void* stream);
 
+/* Soft-DTW (M. Cuturi, M. Blondel 2017) between 3-vectors and its gradient with respect to a: the differentiable form of
+ * kr_dtw_batch's metric - a loss on a simulated tip path against a recorded one that is not sample-aligned with it, and
+ * its cotangent written where kr_simulate_vjp_* reads it.  A training loss, not a reported metric.  It is what
+ * krod_eval.softdtw_grad(a, b, gamma, cost) states; 1-based table indices, all arithmetic fp64 whatever dtype:
+ *   cost      c(i,j) = (|dx| + |dy|) + |dz| (cost = 0, the metric's own point distance, kr_dtw_batch's order) or
+ *             (dx dx + dy dy) + dz dz (cost = 1), d = a_i - b_j
+ *   forward   R(0,0) = 0, every other cell of row 0 and column 0 +inf;  R(i,j) = c(i,j) + softmin(R(i-1,j), R(i,j-1),
+ *             R(i-1,j-1)),  softmin(r) = m - gamma log(sum_k exp((m - r_k) / gamma)), m = min r, an infinite entry
+ *             contributing 0;  value = R(Ta,Tb)
+ *   backward  E(Ta+1,Tb+1) = 1, R(Ta+1,Tb+1) = R(Ta,Tb); row Ta+1 and column Tb+1 otherwise R = -inf, E = 0, and c = 0
+ *             there;  E(i,j) = sum over (p,q) in {(i+1,j), (i,j+1), (i+1,j+1)} of E(p,q) exp((R(p,q) - R(i,j) - c(p,q)) / gamma)
+ *             (every exponent <= 0)
+ *   gradient  g_a[i][k] = sum_j E(i,j) dc(i,j)/da_ik,  dc/da = sign(a_ik - b_jk) with sign(0) = 0 (cost = 0), 2 (a_ik - b_jk)
+ *             (cost = 1)
+ * The device is held to the statement by derived bounds, not bit for bit (exp and log are the device's): with n = Ta + Tb - 1
+ * and eps = 2^-52, |value - exact| <= tolR = 16 n eps (max |R| + gamma ln 3) and |g_a[i][k] - exact| <= n (3 tolR / gamma +
+ * 8 eps) sum_j E(i,j) |dc/da_ik| (tests/test_gpu_softdtw.py; measured ratios in LABBOOK.md).  As gamma -> 0 the value tends
+ * to kr_dtw_batch's distance from below: dtw - n gamma ln 3 <= value <= dtw up to tolR.  A 1 x 1 table is exact: value =
+ * c(1,1) and g_a = dc/da bit for bit.  The kernel forms a weight's exponent as (Q(p,q) - R(i,j)) / gamma with Q = R - c the
+ * softmin the forward sweep kept BEFORE adding c, which is the statement's exponent without the rounding of adding c and
+ * taking it off again (ulp(R) / gamma per cell): in a hard table (gamma far below the gaps between warp paths) E is 1 on the
+ * path and g_a a sum of signs to the last bit, where the statement evaluated in fp64 drifts by n ulp(R) / gamma.
+ * a, b and their strides: exactly as for kr_dtw_batch (in ELEMENTS, >= 0, b's rod stride 0 = one reference for all rods).
+ * value[B], double.  g_a (nullable; element type = dtype): sample i of rod r is WRITTEN - not added to - as the 3
+ * consecutive elements at g_a + r*g_rod_stride + i*g_step_stride (strides in elements, > 0), nothing else: one call writes
+ * straight into slots 12..14 of the last record of g[t + 1] of a zeroed cotangent history g[T+1][B][N][KR_SLOTS] (pointer
+ * to slot 12 of record N - 1 of g[1]; rod N*KR_SLOTS, step B*N*KR_SLOTS), which kr_simulate_vjp_* takes as g_states: no
+ * trajectory and no table leaves the device between the forward rollout and the backward pass.  g_a == NULL: value only,
+ * nothing of the backward sweep runs; value has the bits of the call with the gradient.
+ * A rod with a sample that is not finite in either sequence gets value = NaN and NaN in all its g_a entries; the call
+ * returns KR_OK and every other rod's outputs are bit for bit those of the clean call.  The sums of the gradient are formed
+ * in a fixed order without atomics: a rod's outputs are the same bits from run to run, for any B and wherever it stands.
+ * That order is the DEVICE's: the sum over j of a row is taken in DECREASING j (the backward sweep meets the columns that
+ * way), where krod_eval.softdtw_grad, the definition, sums in increasing j - a difference within the rounding of a sum of
+ * Tb terms, inside the bound above, and the reason g_a is held to the statement by a bound and not bit for bit.
+ * ws: caller-owned device scratch of kr_softdtw_ws_bytes(B, Ta, Tb, need_grad) bytes (the table of the cells for the backward
+ * sweep where it does not fit the LDS; 0 for value only and for short sequences - ws may then be NULL; always a multiple
+ * of 16).  The call uses none of the handle's scratch and reads no parameter; two calls in flight need two workspaces.
+ * Nothing outside the Ta, Tb samples of a rod, its outputs and its slice of ws is touched.
+ * KR_E_ARG: a null handle, a, b or value; B, Ta or Tb < 1; a negative stride of a or b; a stride of g_a <= 0 with g_a given;
+ * gamma not finite or <= 0; cost not 0 or 1; a bad dtype; ws NULL while the size is nonzero.  KR_E_UNSUPPORTED: a length
+ * > KR_SOFTDTW_MAX_LEN.  In every refusal nothing is launched and no output byte is written.
+ * One wavefront per rod: kr_dtw_batch's sweep with the longer cell, every R kept, and the mirrored sweep back. */
+#define KR_SOFTDTW_MAX_LEN 1024
+size_t kr_softdtw_ws_bytes(int64_t B, int64_t Ta, int64_t Tb, int need_grad);
+int kr_softdtw_batch(kr_handle* h, int64_t B,
+                     const void* a, int64_t Ta, int64_t a_rod_stride, int64_t a_step_stride,
+                     const void* b, int64_t Tb, int64_t b_rod_stride, int64_t b_step_stride,
+                     double gamma, int cost, double* value,
+                     void* g_a, int64_t g_rod_stride, int64_t g_step_stride,
+                     void* ws, int dtype, void* stream);
+
 /* physics_multitrain.py:215-222 per rod: mse[b] = 1000 * mean over the first T states and the handle's N grid points
  * of the 3 squared position errors and the 3 squared zyx-Euler-angle errors (6*T*N terms).
  * states[T][B][N][KR_SLOTS] (the first T slots of a full history), ref_states[T][ref_B][N][KR_SLOTS], ref_B = 1 or B;

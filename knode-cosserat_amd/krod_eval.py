@@ -66,6 +66,87 @@ def dtw_distance(a, b, p=1):
     return float(D[Ta, Tb])
 
 
+SOFTDTW_COSTS = {"l1": 0, "sq": 1}  # the point costs of the soft form -> the `cost` argument of kr_softdtw_batch
+
+
+def _softdtw_args(a, b, gamma, cost):
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != 3 or b.shape[1] != 3 or len(a) < 1 or len(b) < 1:
+        raise ValueError(f"softdtw: sequences must be [Ta, 3] and [Tb, 3] with Ta, Tb >= 1; got {a.shape} and {b.shape}")
+    gamma = float(gamma)
+    if not (np.isfinite(gamma) and gamma > 0.0):
+        raise ValueError(f"softdtw: gamma must be finite and > 0; got {gamma}")
+    if cost not in SOFTDTW_COSTS:
+        raise ValueError(f"softdtw: cost must be one of {sorted(SOFTDTW_COSTS)}; got {cost!r}")
+    return a, b, gamma
+
+
+def _softdtw_forward(a, b, gamma, cost):
+    """(d[Ta, Tb, 3], c padded to [Ta + 2, Tb + 2] with zeros, R[Ta + 2, Tb + 2]) of the forward sweep, 1-based cells."""
+    Ta, Tb = len(a), len(b)
+    d = a[:, None, :] - b[None, :, :]
+    c = np.zeros((Ta + 2, Tb + 2))
+    if cost == "l1":
+        c[1:Ta + 1, 1:Tb + 1] = (np.abs(d[..., 0]) + np.abs(d[..., 1])) + np.abs(d[..., 2])
+    else:
+        c[1:Ta + 1, 1:Tb + 1] = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    R = np.full((Ta + 2, Tb + 2), np.inf)
+    R[0, 0] = 0.0
+    for k in range(2, Ta + Tb + 1):  # cells (i, j), 1-based, with i + j = k
+        i = np.arange(max(1, k - Tb), min(Ta, k - 1) + 1)
+        j = k - i
+        up, left, diag = R[i - 1, j], R[i, j - 1], R[i - 1, j - 1]
+        m = np.minimum(np.minimum(up, left), diag)  # finite: every cell of the table has a finite predecessor
+        s = (np.exp((m - up) / gamma) + np.exp((m - left) / gamma)) + np.exp((m - diag) / gamma)  # exp(-inf) = 0
+        R[i, j] = c[i, j] + (m - gamma * np.log(s))
+    return d, c, R
+
+
+def softdtw_distance(a, b, gamma, cost="l1"):
+    """Soft-DTW (Cuturi & Blondel 2017) of the paths a[Ta, 3], b[Tb, 3]: DTW's recurrence with ``min`` replaced by
+    ``softmin(r) = m - gamma log(sum_k exp((m - r_k) / gamma))``, m = min r, over (up, left, diagonal), an infinite entry
+    contributing 0.  ``cost``: ``"l1"``, the metric's own point distance ``(|dx| + |dy|) + |dz|``, or ``"sq"``,
+    ``(dx dx + dy dy) + dz dz``.  fp64; the statement ``kr_softdtw_batch`` is held to (include/knode_rod.h).  As gamma -> 0
+    the value tends to ``dtw_distance(a, b)`` from below, by at most ``gamma ln 3`` per cell of a warp path."""
+    a, b, gamma = _softdtw_args(a, b, gamma, cost)
+    return float(_softdtw_forward(a, b, gamma, cost)[2][len(a), len(b)])
+
+
+def softdtw_grad(a, b, gamma, cost="l1"):
+    """``(value, g_a[Ta, 3])``: ``softdtw_distance`` and its gradient with respect to a, by the backward sweep over the
+    table: E(Ta + 1, Tb + 1) = 1, R(Ta + 1, Tb + 1) = R(Ta, Tb), the rest of row Ta + 1 and column Tb + 1 R = -inf, E = 0,
+    c = 0; ``E(i, j) = sum over (p, q) in ((i + 1, j), (i, j + 1), (i + 1, j + 1)) of E(p, q) exp((R(p, q) - R(i, j) -
+    c(p, q)) / gamma)`` (every exponent <= 0); ``g_a[i] = sum_j E(i, j) dc(i, j)/da_i`` in increasing j, with dc/da =
+    sign(a - b) (sign(0) = 0) for ``"l1"`` and 2 (a - b) for ``"sq"``."""
+    a, b, gamma = _softdtw_args(a, b, gamma, cost)
+    d, R, E = _softdtw_tables(a, b, gamma, cost)
+    dc = np.sign(d) if cost == "l1" else 2.0 * d
+    g = np.zeros((len(a), 3))
+    for j in range(len(b)):  # (increasing j)
+        g += E[1:-1, j + 1, None] * dc[:, j, :]
+    return float(R[len(a), len(b)]), g
+
+
+def _softdtw_tables(a, b, gamma, cost):
+    """(d[Ta, Tb, 3] = a_i - b_j, R[Ta + 2, Tb + 2], E[Ta + 2, Tb + 2]) of both sweeps, 1-based cells, borders as defined"""
+    Ta, Tb = len(a), len(b)
+    d, c, R = _softdtw_forward(a, b, gamma, cost)
+    R[Ta + 1, :] = -np.inf
+    R[:, Tb + 1] = -np.inf
+    R[Ta + 1, Tb + 1] = R[Ta, Tb]
+    E = np.zeros((Ta + 2, Tb + 2))
+    E[Ta + 1, Tb + 1] = 1.0
+    for k in range(Ta + Tb, 1, -1):
+        i = np.arange(max(1, k - Tb), min(Ta, k - 1) + 1)
+        j = k - i
+        r = R[i, j]
+        E[i, j] = (E[i + 1, j] * np.exp((R[i + 1, j] - r - c[i + 1, j]) / gamma)
+                   + E[i, j + 1] * np.exp((R[i, j + 1] - r - c[i, j + 1]) / gamma)) \
+            + E[i + 1, j + 1] * np.exp((R[i + 1, j + 1] - r - c[i + 1, j + 1]) / gamma)
+    return d, R, E
+
+
 def _l1(a, b):
     return float(np.abs(a - b).sum())
 

@@ -22,6 +22,15 @@ d(tension history) costs about one forward rollout instead of 4 T + 1 of them by
   (``kr_simulate_vjp_nn_batch``) - and the gradient of a rollout loss with respect to the network's weights, which the
   reference never had (it trains one step ahead, physics_train.py:250-259).
 
+* ``softdtw_loss(robot, tips, ref, gamma)``: the loss these gradients were missing - the soft-DTW of every rod's tip path
+  to a recorded path that is not sample-aligned with it (``kr_softdtw_batch``), the differentiable form of the DTW the runs
+  are scored by; an ``autograd.Function`` that composes with every ``simulate_tips*``.  A caller of ``rollout_grad*`` who
+  holds ``states`` seeds the cotangent history in the same launch, and no trajectory leaves the device::
+
+      g = torch.zeros_like(states)                                     # [T + 1, B, N, KR_SLOTS]
+      value, _ = h.softdtw(states[1:, :, N - 1, 12:15].permute(1, 0, 2), ref, gamma, g_out=g[1:, :, N - 1, 12:15].permute(1, 0, 2))
+      grads = rollout_grad(robot, ctl, states, g_states=g)            # h = robot._native()
+
 Euler sweeps, the handle's parameters; anything else is refused by the library (no fall-back).  The adjoint is
 that of the EXACT root of the shooting equations: solve the forward pass tightly (``tol = 1e-12``, the default of
 ``simulate_tips``) - the distance to the root enters the gradient at first order."""
@@ -672,3 +681,49 @@ def simulate_tips_bank(robot, robots, ctl, params, net_of_rod, base_motion=None,
     robots = _check_robots(who, robots, B, nn_ok=True)
     flat = [t for p in params for t in p]
     return _SimulateTipsBank.apply(ctl, robot, robots, _tdt(dtype), float(tol), nets, base_motion, tip_loads, len(params[0]), *flat)
+
+
+# ---- a loss on the tip path that needs no sample alignment ----------------------------------------------------------------
+class _SoftDtwLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tips, ref, h, gamma, cost):
+        dev = f"cuda:{h.device}"
+        a = tips.detach().to(device=dev)
+        b = ref.detach().to(device=dev, dtype=a.dtype)
+        need = ctx.needs_input_grad[0]
+        out = h.softdtw(a, b, gamma, cost=cost, grad=need)  # (one launch: the value and, where asked for, its gradient)
+        value, ctx.g_a = out if need else (out, None)
+        return value.to(device=tips.device)
+
+    @staticmethod
+    def backward(ctx, g_value):
+        g = ctx.g_a * g_value.to(device=ctx.g_a.device, dtype=ctx.g_a.dtype)[:, None, None]
+        return g.to(device=g_value.device), None, None, None, None
+
+
+def softdtw_loss(robot, tips, ref, gamma, cost="l1"):
+    """Soft-DTW of every rod's tip path ``tips[B, T, 3]`` (a torch tensor of float32 or float64 on any device, what every
+    ``simulate_tips*`` returns) to the recorded path ``ref[B, Tr, 3]`` or ``[Tr, 3]`` (one for all rods; tensor or array,
+    taken in the dtype of ``tips``): ``value[B]`` in float64 on the device of ``tips``, connected to ``tips`` in torch's graph.
+    ``krod_eval.softdtw_grad`` states value and gradient; ``cost`` is ``"l1"``, the point distance of the DTW the runs are
+    scored by, or ``"sq"``; as ``gamma`` -> 0 the value tends to ``krod_eval.dtw_distance`` from below.  ``robot`` supplies the
+    device handle, as for the neighbouring functions; none of its parameters is read.  The forward is one
+    ``kr_softdtw_batch`` that returns the gradient with the value, the backward multiplies it by the incoming cotangent:
+    ``softdtw_loss(robot, simulate_tips(robot, ctl), ref, 1e-2).sum().backward()`` fills ``ctl.grad``.  The recorded path is
+    data: no gradient with respect to ``ref`` is formed, and a ``ref`` that requires one is refused."""
+    who = "softdtw_loss"
+    if not isinstance(tips, torch.Tensor):
+        raise kn.KrError(f"{who}: tips must be a torch tensor (it is what the gradient is connected to)")
+    if tips.dim() != 3 or tips.shape[2] != 3 or tips.shape[0] < 1 or tips.shape[1] < 1:
+        raise kn.KrError(f"{who}: tips must be [B, T, 3] with B, T >= 1; got {tuple(tips.shape)}")
+    if tips.dtype not in (torch.float32, torch.float64):
+        raise kn.KrError(f"{who}: tips must be float32 or float64; got {tips.dtype}")
+    if isinstance(ref, torch.Tensor) and ref.requires_grad:
+        raise kn.KrError(f"{who}: ref requires grad; the gradient with respect to the recorded path is not served")
+    if not isinstance(ref, torch.Tensor):
+        ref = torch.as_tensor(np.asarray(ref, dtype=np.float64))
+    B = tips.shape[0]
+    if not ((ref.dim() == 2 or (ref.dim() == 3 and ref.shape[0] == B)) and ref.shape[-1] == 3 and ref.shape[-2] >= 1):
+        raise kn.KrError(f"{who}: ref must be [{B}, Tr, 3] or [Tr, 3] with Tr >= 1; got {tuple(ref.shape)}")
+    gamma, _ = kn.softdtw_args(gamma, cost, tips.shape[1], ref.shape[-2])
+    return _SoftDtwLoss.apply(tips, ref, robot._native(), gamma, cost)

@@ -26,6 +26,8 @@ ST_CONVERGED, ST_MAXIT, ST_NONFINITE = 0, 1, 2
 KR_MAX_LAYERS = 8
 KR_DTW_MAX_LEN = 4096
 KR_FASTDTW_MAX_LEN, KR_FASTDTW_MAX_RADIUS = 1024, 8  # kr_fastdtw_batch: samples per sequence, radius
+KR_SOFTDTW_MAX_LEN = 1024  # kr_softdtw_batch: samples per sequence
+SOFTDTW_COSTS = {"l1": 0, "sq": 1}  # kr_softdtw_batch's point costs (krod_eval.SOFTDTW_COSTS)
 KR_BND = 19  # p0 (3), h0 (4), q0 (3), w0 (3), F_tip (3), M_tip (3) per rod and step (kr_simulate_batch_boundary)
 KR_PAR = 43  # material parameters a step adjoint can differentiate (kr_step_vjp_par_batch), in the order of PAR_BLOCKS
 # name, shape, offset into g_par[..., KR_PAR]: the order and row-major layout of struct kr_params (del_t and N are not differentiated)
@@ -156,6 +158,8 @@ _PROTOS = {
     "kr_dtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp]),
     "kr_fastdtw_ws_bytes": (C.c_size_t, [_i64, _i64, _i64, _int]),
     "kr_fastdtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp]),
+    "kr_softdtw_ws_bytes": (C.c_size_t, [_i64, _i64, _i64, _int]),
+    "kr_softdtw_batch": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _dbl, _int, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
     "kr_pose_mse_batch": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
     "kr_pose_mse_points_batch": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _int, _vp]),
     "kr_step_vjp_nn_batch": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
@@ -257,6 +261,24 @@ def _dtw_view(t, B, name):
     if comp != 1 or rod < 0 or step < 0:
         raise KrError(f"dtw: sequence {name}: the 3 components must be adjacent and the strides >= 0 (strides {t.stride()})")
     return (0 if B == 1 else rod), (0 if t.shape[1] == 1 else step), t.shape[1]
+
+
+def softdtw_args(gamma, cost, Ta=1, Tb=1):
+    """(gamma, cost code) of a soft-DTW call, checked on the host as ``kr_softdtw_batch`` checks them (no device, no
+    library): gamma finite and > 0, cost ``"l1"`` or ``"sq"``, at most ``KR_SOFTDTW_MAX_LEN`` samples per sequence."""
+    try:
+        gamma = float(gamma)
+    except (TypeError, ValueError):
+        raise KrError(f"softdtw: gamma must be a number; got {gamma!r}") from None
+    if not (np.isfinite(gamma) and gamma > 0.0):
+        raise KrError(f"softdtw: gamma must be finite and > 0; got {gamma}")
+    if not isinstance(cost, str) or cost not in SOFTDTW_COSTS:
+        raise KrError(f"softdtw: cost must be one of {sorted(SOFTDTW_COSTS)}; got {cost!r}")
+    if Ta > KR_SOFTDTW_MAX_LEN or Tb > KR_SOFTDTW_MAX_LEN:
+        err = KrError(f"softdtw: sequences of {Ta} and {Tb} samples: at most {KR_SOFTDTW_MAX_LEN} samples per sequence are served")
+        err.code = KR_E_UNSUPPORTED
+        raise err
+    return gamma, SOFTDTW_COSTS[cost]
 
 
 def derive(params: KrParams) -> KrDerived:
@@ -961,6 +983,45 @@ class Handle:
         check(self.lib.kr_fastdtw_batch(self._h, B, C.c_void_p(a.data_ptr()), Ta, ars, ass, C.c_void_p(b.data_ptr()), Tb, brs, bss,
                                         radius, _ptr(out), _ptr(steps), _ptr(plen), _ptr(ws), dtype_code(a.dtype), _stream()))
         return (out, steps, plen) if path else out
+
+    def softdtw(self, a, b, gamma, cost="l1", grad=False, g_out=None):
+        """Soft-DTW of every rod's path ``a[b]`` to ``b[b]`` (``kr_softdtw_batch``; ``krod_eval.softdtw_grad`` is its
+        statement): the sequences are given as for ``dtw`` (views are read in place), ``cost`` is ``"l1"`` (the metric's own
+        point distance) or ``"sq"``.  Returns ``value``, float64 ``[B]`` on the device; with ``grad=True`` or a ``g_out``
+        ``(value, g_a)``, ``g_a[B, Ta, 3]`` = d value[b] / d a[b] in the dtype of ``a``.  ``g_out``: a ``[B, Ta, 3]`` view
+        the gradient is WRITTEN into through its strides (3 adjacent components; nothing else of its storage is touched) -
+        ``g[1:, :, N - 1, 12:15].permute(1, 0, 2)`` of a zeroed ``g[T + 1, B, N, KR_SLOTS]`` seeds ``simulate_vjp*`` with
+        the loss's cotangent in the same launch.  A rod with a non-finite sample gets NaN in both.  The workspace is
+        allocated here (``kr_softdtw_ws_bytes``)."""
+        import torch
+        if a.dim() != 3:
+            raise KrError(f"softdtw: sequence a must be [B, Ta, 3]; got {tuple(a.shape)}")
+        if a.dtype != b.dtype:
+            raise KrError(f"softdtw: a is {a.dtype}, b {b.dtype}")
+        B = a.shape[0]
+        ars, ass, Ta = _dtw_view(a, B, "a")
+        brs, bss, Tb = _dtw_view(b, B, "b")
+        gamma, code = softdtw_args(gamma, cost, Ta, Tb)
+        want = bool(grad) or g_out is not None
+        grs = gss = 0
+        if want:
+            if g_out is None:
+                g_out = torch.empty((B, Ta, 3), dtype=a.dtype, device=a.device)
+            if not g_out.is_cuda or g_out.device != a.device or g_out.dtype != a.dtype or tuple(g_out.shape) != (B, Ta, 3):
+                raise KrError(f"softdtw: g_out must be a [{B}, {Ta}, 3] view of {a.dtype} on {a.device}; got "
+                              f"{tuple(g_out.shape)} of {g_out.dtype} on {g_out.device}")
+            grs, gss, comp = g_out.stride()
+            # (a stride torch leaves arbitrary for an extent of 1 is not used by the kernel either)
+            grs, gss = (grs if B > 1 else max(grs, 1)), (gss if Ta > 1 else max(gss, 1))
+            if comp != 1 or grs <= 0 or gss <= 0:
+                raise KrError(f"softdtw: g_out: the 3 components must be adjacent and the strides > 0 (strides {g_out.stride()})")
+        value = torch.empty((B,), dtype=torch.float64, device=a.device)
+        nbytes = int(self.lib.kr_softdtw_ws_bytes(B, Ta, Tb, int(want)))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=a.device) if nbytes else None
+        check(self.lib.kr_softdtw_batch(self._h, B, C.c_void_p(a.data_ptr()), Ta, ars, ass, C.c_void_p(b.data_ptr()), Tb, brs, bss,
+                                        gamma, code, _ptr(value), C.c_void_p(g_out.data_ptr()) if want else None, grs, gss,
+                                        _ptr(ws), dtype_code(a.dtype), _stream()))
+        return (value, g_out) if want else value
 
     def pose_mse(self, states, ref_states):
         """Position + zyx-Euler MSE x 1000 of every rod over packed states ``[T, B, N, KR_SLOTS]`` (the first T slots of a
